@@ -2,7 +2,18 @@
 """bench.py -- the reference's headline metric on MI355X: Mpix/s of compute_ssim (global SSIM,
 no map) on 4096x4096 uint8 pairs, with the achieved-vs-roofline figures and a CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--workload ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--workload ...] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: set-up, the known-answer gate, the clock-settle loop, W warm-up
+steps, K timed steps, the outputs of the last timed step (--dump-outputs) and one JSON line (value, ms_per_step, config,
+exchange, and launches_timed: the batched launches rank 0's library counted during the timed steps, one per step).
+`--full` adds everything else below: the roofline / VALU figures and the box probe, the sustained leg, the opt-in modes,
+the single-pair and cold-start legs, the other BASELINE configs, plan_regret and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the batched path receives it: DIR/sums.npy
+(float64, the per-pair SSIM sums of all pairs of all ranks), DIR/ssim.npy (float32, the per-pair global SSIM) and, for a
+workload with a map, DIR/map_sample.npy (float32, a fixed seeded sample of rank 0's per-pixel maps, MAP_SAMPLE_MAX
+values at most).  The inputs are the seeded synthetic pairs, so the same arguments give the same inputs on every run.
 
 `--gpus N` with N > 1 is self-contained, like the reference's rmgr_ssim_compute_ssim_openmp builds its
 own pool (src/ssim-openmp.c:40-47): when no launcher has set WORLD_SIZE, this process -- before it
@@ -27,10 +38,10 @@ Timing: barrier + synchronize on both sides of exactly K steps, max over ranks; 
 all ranks / that time.  Before any timing the results are gated on the reference's known answers
 (FMA path float bits) -- on every rank's first pairs.
 
-After the headline a single-GPU run times the other BASELINE.json configs (8192^2 + map exact
+With --full, after the headline a single-GPU run times the other BASELINE.json configs (8192^2 + map exact
 and separable, 128 x 1080p, fp64 internals 4096^2 + map), each KAT-gated, into `configs`.
 
-Only the cpu_baseline leg touches oracle/: it times the real reference kernels (oracle/_ref,
+Only the cpu_baseline leg (--full) touches oracle/: it times the real reference kernels (oracle/_ref,
 kind "reference") or, where that prebuilt library is absent, the C restatement (kind "port").
 """
 import argparse
@@ -133,10 +144,10 @@ def cpu_baseline_in_child(budget_s=10.0):
     """Runs cpu_baseline() in a CHILD process (never exec: this process has initialised the GPU) whose OpenMP runtime starts
     with its threads pinned -- OMP_PROC_BIND=close, OMP_PLACES=cores: one thread per physical core, neighbouring cores
     first -- because the OpenMP runtime reads those variables once, when it is loaded, and this process loaded one long
-    ago (torch).  Unpinned, the 64-thread baseline varied 1.9x between its best and its median run (round 3)."""
+    ago (torch).  Unpinned, the 64-thread baseline varied 1.9x between its best and its median run (round 3).  An
+    OMP_NUM_THREADS set by whoever started the bench is kept: on a shared host it is the share of the cores this run may use."""
     env = dict(os.environ)
     env.update(CPU_BASELINE_ENV)
-    env.pop("OMP_NUM_THREADS", None)
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", str(budget_s)], env=env, stdout=subprocess.PIPE, timeout=600)
     if r.returncode != 0:
         raise SystemExit("the cpu_baseline child failed (exit %d)" % r.returncode)
@@ -157,6 +168,8 @@ def cpu_baseline(budget_s=10.0):
         kind = "port"
         cores = oracle.oracle_lib().oracle_max_threads()
         run = lambda a, b, threads, want_map=False, out_map=None: oracle.ssim_f32(a, b, want_map=want_map, fused=True, threads=threads, out_map=out_map)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        cores = min(cores, int(os.environ["OMP_NUM_THREADS"]))      # the launcher's share of a shared host (both libraries count every processor)
 
     def timed(fn, budget, min_runs=3, max_runs=100000):
         ts = []
@@ -508,6 +521,30 @@ def shard_table(args, world):
     return {"scaling": "strong", "total": total, "shards": [list(x) for x in sharding.split_batch(total, world)]}
 
 
+MAP_SAMPLE_MAX = 1 << 22       # map values --dump-outputs keeps (16 MB of float32): a whole 8192^2 map alone is 256 MB
+MAP_SAMPLE_SEED = 0x5EED
+
+
+def map_sample_index(np, pixels, count):
+    """The positions map_sample.npy holds, the same on every run: MAP_SAMPLE_MAX draws (seed MAP_SAMPLE_SEED) over the elements of
+    `count` maps of `pixels` elements each, in pair order, duplicates dropped, ascending.  [(pair, element indices within its map)]"""
+    idx = np.unique(np.random.default_rng(MAP_SAMPLE_SEED).integers(0, pixels * count, MAP_SAMPLE_MAX, dtype=np.int64))
+    return [(i, idx[(idx >= i * pixels) & (idx < (i + 1) * pixels)] - i * pixels) for i in range(count)]
+
+
+def dump_outputs(out_dir, np, torch, sums, w, h, maps):
+    """--dump-outputs: the last timed step's results (module docstring).  `sums` = the device vector of per-pair fp64 sums the
+    step delivered, `maps` = rank 0's device maps (None without a map), sampled at map_sample_index()."""
+    import ssim_amd
+    os.makedirs(out_dir, exist_ok=True)
+    s = sums.cpu().numpy().astype(np.float64)
+    np.save(os.path.join(out_dir, "sums.npy"), s)
+    np.save(os.path.join(out_dir, "ssim.npy"), ssim_amd.finalize(s, w, h))
+    if maps:
+        parts = [maps[i].reshape(-1)[torch.from_numpy(sel).to(maps[i].device)].cpu().numpy() for i, sel in map_sample_index(np, w * h, len(maps))]
+        np.save(os.path.join(out_dir, "map_sample.npy"), np.concatenate(parts).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -524,17 +561,22 @@ def main():
                          "the C ABI; rank 0's communicator id travels over the launcher's process group); torch = torch.distributed.all_reduce; "
                          "auto (default) = native when its communicator comes up on every rank within the deadline, else torch -- the line says which")
     ap.add_argument("--sustain", type=float, default=6.0, metavar="SECONDS",
-                    help="after the timed region: the same step repeated for about SECONDS on every rank (the same number of steps on all of them), "
+                    help="--full, after the timed region: the same step repeated for about SECONDS on every rank (the same number of steps on all of them), "
                          "reported as `sustained` -- throughput at thermal / clock steady state, and long enough for an outside utilisation sampler "
                          "to see the GPUs busy (0: off; never part of `value`)")
     ap.add_argument("--watchdog", type=float, default=900.0, metavar="SECONDS", help="dump all Python stacks and exit non-zero if the run takes longer than this (0: off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cold-start", action="store_true", help="skip the cold-start / concurrent-caller child processes of single_pair")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configs after the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline / VALU figures with the box probe, the sustained leg, the "
+                         "opt-in modes, single-pair and cold-start legs, the other BASELINE configs, plan_regret, the CPU baseline (off: a plain run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (sums, ssim and, with a map, map_sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-cold-start", action="store_true", help="--full: skip the cold-start / concurrent-caller child processes of single_pair")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the other BASELINE configs and plan_regret after the headline")
     ap.add_argument("--print-launch", action="store_true", help="print the rank launcher command for --gpus N and exit (no GPU needed)")
     ap.add_argument("--print-shards", action="store_true", help="print the shard table (JSON: which global pairs each rank owns) for --gpus N and exit (no GPU needed)")
     ap.add_argument("--cpu-baseline-only", type=float, default=0.0, metavar="SECONDS",
-                    help="internal: time the CPU baseline for about SECONDS and print its JSON object (the child process of the default run)")
+                    help="internal: time the CPU baseline for about SECONDS and print its JSON object (the child process of a --full run)")
     args = ap.parse_args()
     if args.cpu_baseline_only > 0:
         print(json.dumps(cpu_baseline(args.cpu_baseline_only)))
@@ -714,9 +756,9 @@ def main():
     # The box's own VALU peak (rmgr_ssim_hip_probe_valu), the yardstick the kernel's lane-operations per second are divided by: probed BEFORE the clock-settle
     # loop and again right after the timed steps.  Not between the settle loop and the timed steps: a pure packed-FMA stream at full occupancy draws more power than
     # the SSIM kernel, and the steps that follow it must be the kernel's own steady state, not the probe's aftermath ($SSIM_BENCH_PROBE=late puts it there for the A/B,
-    # off skips it).  Local to the rank, no collective.
+    # off skips it; a plain run, without --full, has no VALU figures and skips it too).  Local to the rank, no collective.
     occupancies = (2, 3, 8)
-    probe_when = os.environ.get("SSIM_BENCH_PROBE", "early")
+    probe_when = os.environ.get("SSIM_BENCH_PROBE", "early") if args.full else "off"
     box_samples = [b for b in [probe_box_or_none(ctx, occupancies)] if b] if probe_when == "early" else []
     t_settle = time.perf_counter()
     while True:
@@ -749,6 +791,8 @@ def main():
     last = work if dist is not None else sums_all
     if not np.array_equal(last.cpu().numpy().view(np.uint64), full_bits):
         raise SystemExit("rank %d: the timed steps returned different sums than the gated step" % rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, torch, last, W, H, [m for _, _, m in batch.imgs] if want_map else None)
     launches, kernel_ms = ctx.get_profile()
     kernel_avg_ms = kernel_ms / max(launches, 1)
     kernel_clock = ctx.get_profile_clock()[:2]
@@ -778,7 +822,7 @@ def main():
     # --- sustained rate: the same step (kernel + exchange) for about --sustain seconds, the same number of steps on every rank
     #     (derived from the all-reduced elapsed time, so the collectives pair up); never `value` ---
     sustained = {}
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         n_sus = max(args.steps, int(args.sustain / max(elapsed / args.steps, 1e-6)))
         fence()
         power = PowerSampler() if rank == 0 else None      # rocm-smi in a side thread (a child process per sample): what the package draws and clocks under this very load
@@ -807,7 +851,7 @@ def main():
 
     # --- the two opt-in modes on the same batch (kernel time only; never `value`) ---
     other = {}
-    if args.mode == 0 and rank == 0 and mine:
+    if args.full and args.mode == 0 and rank == 0 and mine:
         for key, m in (("fast_mode", 1), ("separable_mode", 4)):
             ctx.set_mode(m)
             plan_m = ssim_amd.get_plan(W, H, mine, ctx)
@@ -835,7 +879,7 @@ def main():
 
     # --- single-pair latency/throughput (BASELINE.json configs[1] literally: one pair per call) ---
     single = {}
-    if rank == 0 and mine:
+    if args.full and rank == 0 and mine:
         imgs = batch.imgs
         p0 = ssim_amd.make_params(W, H, imgs[0][0].data_ptr(), 1, W, imgs[0][1].data_ptr(), 1, W)   # global-only
         one = (ssim_amd.Params * 1)(p0)
@@ -945,7 +989,7 @@ def main():
 
     # --- the other BASELINE configs, rank 0 only, after the timed region (kernel time from HIP events) ---
     configs = {}
-    if rank == 0 and world == 1 and not args.no_configs and args.mode == 0 and args.variant == 0 and args.strip_rows == 0:
+    if args.full and rank == 0 and world == 1 and not args.no_configs and args.mode == 0 and args.variant == 0 and args.strip_rows == 0:
         del batch                                  # free the headline batch first
         torch.cuda.empty_cache()
         ksteps = min(max(args.steps // 2, 5), 100)
@@ -962,7 +1006,7 @@ def main():
     # --- plan_regret: is the untuned default plan the best of its candidates on THIS box?  rmgr_ssim_hip_tune on a context of its own (the timed
     #     context above ran, and stays on, the untuned default): kernel time of the default plan / of the best candidate, candidates interleaved ---
     plan_regret = {}
-    if rank == 0 and world == 1 and not args.no_configs and args.variant == 0 and args.strip_rows == 0:
+    if args.full and rank == 0 and world == 1 and not args.no_configs and args.variant == 0 and args.strip_rows == 0:
         with ssim_amd.Context(dev_index, ctypes.c_void_p(stream.cuda_stream), mode=args.mode) as tctx:
             try:
                 for key, (tw, th, tn, tmap) in (("headline", (W, H, mine, want_map)), ("1080p x128", (1920, 1080, 128, False)), ("8k-map x2", (8192, 8192, 2, True)), ("4k x1", (4096, 4096, 1, False))):
@@ -978,12 +1022,12 @@ def main():
                                "rounds on synthetic pairs of the shape; regret = default / best kernel time (1.0: the default is the best; a candidate replaces it only beyond 0.5 %)")
 
     attainable = None
-    if rank == 0:
+    if rank == 0 and args.full:
         attainable = attainable_hbm_gbs(torch, dev)
     if rank == 0:
         pixels = float(total) * W * H * args.steps
         value = pixels / elapsed / 1e6
-        roof, valu = figures(args.mode, mine, W, H, want_map, kernel_avg_ms) if mine else ({}, {})
+        roof, valu = figures(args.mode, mine, W, H, want_map, kernel_avg_ms) if mine and args.full else ({}, {})
         if roof:
             traffic, traffic_note = measured_traffic(args.mode, args.workload, mine, ssim_amd.kernel_source_id())
             roof.update({"traffic": traffic, "traffic_note": traffic_note,
@@ -1004,7 +1048,7 @@ def main():
         line = {
             "metric": "Mpix/s (global SSIM, no map) on 4K pairs; achieved HBM GB/s vs roofline",
             "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "launches_timed": int(launches), "higher_is_better": True, "scaling": args.scaling,
             "vs_baseline": None, "dtype": "f64" if args.mode == 2 else "f32", "data": "synthetic",
             "config": {"workload": "%s, %s, sharded by image, %s"
                                    % (workload_desc,
@@ -1015,20 +1059,23 @@ def main():
                        "pairs_per_gpu": mine, "pairs_total": total, "width": W, "height": H, "strip_rows": args.strip_rows, "variant": args.variant,
                        "results_digest": result_digest},
             "exchange": exchange,
-            "roofline": roof,
-            "valu": valu,
-            "sustained": sustained,
-            "single_pair": single,
-            "fast_mode": other.get("fast_mode", {}),
-            "separable_mode": other.get("separable_mode", {}),
-            "configs": configs,
-            "plan_regret": plan_regret,
-            "device": ctx.describe(),
         }
+        if args.full:
+            line.update({
+                "roofline": roof,
+                "valu": valu,
+                "sustained": sustained,
+                "single_pair": single,
+                "fast_mode": other.get("fast_mode", {}),
+                "separable_mode": other.get("separable_mode", {}),
+                "configs": configs,
+                "plan_regret": plan_regret,
+            })
+        line["device"] = ctx.describe()
         if shared_device:
             line["test_mode"] = ("SSIM_BENCH_SHARED_DEVICE=1: all %d ranks ran on ONE GPU with gloo as the carrier -- a functional run of the N > 1 code path; "
                                  "`value` is NOT a scaling result" % world)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_in_child()
             # the CPU figure of each BASELINE config beside its GPU line (all host threads, best run; the same image, the same arithmetic contract)
             per = line["cpu_baseline"].get("per_config", {})

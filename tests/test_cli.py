@@ -1,7 +1,7 @@
 """The rmgr-ssim command-line tool (reference src/ssim-cli.cpp).
 
-CPU: the built-in image codecs decode what PIL encodes (PNG incl. the reference's own test images
-when present, PNM, BMP, TGA) and the argument handling mirrors the reference.
+CPU: the built-in image codecs decode what PIL encodes (PNG incl. the reference's own test images,
+copied under tests/golden/images, PNM, BMP, TGA) and the argument handling mirrors the reference.
 GPU: printed values and written maps agree with the golden vectors / the oracle.
 """
 import os
@@ -115,11 +115,10 @@ def test_codecs_roundtrip(tmp_path, manifest):
         assert got.shape == want.shape and np.array_equal(got, want), path
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tests/images"), reason="reference tree not present")
 def test_decodes_reference_test_pngs(tmp_path):
     from PIL import Image
     for name in ("einstein.png", "blur.png", "big_buck_bunny_360_07806.png"):
-        src = "/root/reference/tests/images/" + name
+        src = os.path.join(GOLDEN, "images", name)
         out = str(tmp_path / "d.raw")
         r = run("--decode", src, out)
         assert r.returncode == 0, r.stderr
@@ -162,10 +161,9 @@ def test_jpeg_decoder_matches_libjpeg(tmp_path, manifest):
         im.convert("L").save(p, "JPEG", quality=80, progressive=True)
         assert np.array_equal(decode_with_cli(tmp_path, p), np.asarray(Image.open(p))), size
     assert n >= 100
-    if os.path.isdir("/root/reference/tests/images"):
-        for name in ("big_buck_bunny_360_07806_00.jpg", "big_buck_bunny_360_07806_50.jpg", "big_buck_bunny_360_07806_100.jpg"):
-            p = "/root/reference/tests/images/" + name
-            assert np.array_equal(decode_with_cli(tmp_path, p), np.asarray(Image.open(p))), name
+    for name in ("big_buck_bunny_360_07806_00.jpg", "big_buck_bunny_360_07806_50.jpg", "big_buck_bunny_360_07806_100.jpg"):
+        p = os.path.join(GOLDEN, "images", name)
+        assert np.array_equal(decode_with_cli(tmp_path, p), np.asarray(Image.open(p))), name
     # refused, not mis-decoded: arithmetic coding / 12-bit / CMYK are outside the decoder
     bad = bytearray(open(str(tmp_path / "g.jpg"), "rb").read())
     i = bad.index(b"\xff\xc2")

@@ -1,20 +1,32 @@
-"""CPU, build container only: the oracle against the REAL reference kernels in oracle/_ref.
+"""CPU: the oracle against the REAL reference kernels.
 
-oracle/_ref is compiled from /root/reference (oracle/Makefile).  Where it is absent (a machine
-without the reference tree and without the prebuilt .so) these tests skip; the golden-vector
-tests in test_oracle_golden.py still pin the oracle there.
+The reference's outputs on these inputs are recorded in tests/golden/ref_outputs.json (tests/tools/make_ref_outputs.py, run with
+oracle/_ref, which is compiled from the reference tree by oracle/Makefile): the oracle must reproduce them bit for bit.  Where
+oracle/_ref is built, the live reference kernels are held to the same recording as well.
 """
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
 import oracle as o
-from conftest import f32_hex
-
-pytestmark = pytest.mark.skipif(not o.have_ref(), reason="oracle/_ref/libssim_ref.so not built")
+from conftest import GOLDEN, f32_hex
 
 
-@pytest.mark.parametrize("impl,fused", [(5, True), (4, False)])
-def test_random_images_bit_exact(impl, fused):
+@pytest.fixture(scope="module")
+def recorded():
+    with open(os.path.join(GOLDEN, "ref_outputs.json")) as f:
+        return json.load(f)
+
+
+def digest(v, s, m):
+    """float bits of the global value, the fp64 sum exactly, sha256 of the map's bytes"""
+    return {"ssim_hex": f32_hex(v), "sum": float(s).hex(), "map_sha256": hashlib.sha256(np.ascontiguousarray(m).tobytes()).hexdigest() if m is not None else None}
+
+
+def random_pairs():
     rng = np.random.default_rng(1234)
     for (h, w) in ((1, 1), (5, 7), (63, 255), (64, 256), (65, 257), (130, 600), (300, 301)):
         a = rng.integers(0, 256, (h, w), dtype=np.uint8)
@@ -25,35 +37,56 @@ def test_random_images_bit_exact(impl, fused):
             b = np.clip(a.astype(np.int32) + rng.integers(-9, 10, (h, w)), 0, 255).astype(np.uint8)
         else:
             b = (a // 2 + 40).astype(np.uint8)
-        v, s, m = o.ssim_f32(a, b, want_map=True, fused=fused)
-        rv, rs, rm = o.ref_ssim(a, b, want_map=True, impl=impl)
-        assert f32_hex(v) == f32_hex(rv), (h, w)
-        assert s == rs, (h, w)
-        assert np.array_equal(m.view(np.uint32), rm.view(np.uint32)), (h, w)
+        yield a, b
 
 
-def test_flat_and_extreme_images_bit_exact():
+def flat_pairs():
     for va, vb in ((0, 0), (255, 255), (0, 255), (17, 18)):
-        a = np.full((70, 300), va, np.uint8)
-        b = np.full((70, 300), vb, np.uint8)
-        v, s, m = o.ssim_f32(a, b, want_map=True)
-        rv, rs, rm = o.ref_ssim(a, b, want_map=True)
-        assert f32_hex(v) == f32_hex(rv) and s == rs
-        assert np.array_equal(m.view(np.uint32), rm.view(np.uint32))
+        yield np.full((70, 300), va, np.uint8), np.full((70, 300), vb, np.uint8)
 
 
-def test_naive_f64_identical():
+def naive_pair():
     rng = np.random.default_rng(5)
     a = rng.integers(0, 256, (97, 131), dtype=np.uint8)
     b = np.clip(a.astype(np.int32) + rng.integers(-20, 21, a.shape), 0, 255).astype(np.uint8)
+    return a, b
+
+
+@pytest.mark.parametrize("impl,fused", [(5, True), (4, False)])
+def test_random_images_bit_exact(recorded, impl, fused):
+    want = recorded["random_images"][str(impl)]
+    pairs = list(random_pairs())
+    assert len(want) == len(pairs)
+    for (a, b), ref in zip(pairs, want):
+        assert digest(*o.ssim_f32(a, b, want_map=True, fused=fused)) == ref, a.shape
+        if o.have_ref():
+            assert digest(*o.ref_ssim(a, b, want_map=True, impl=impl)) == ref, a.shape
+
+
+def test_flat_and_extreme_images_bit_exact(recorded):
+    want = recorded["flat_images"]
+    pairs = list(flat_pairs())
+    assert len(want) == len(pairs)
+    for (a, b), ref in zip(pairs, want):
+        assert digest(*o.ssim_f32(a, b, want_map=True)) == ref, (a[0, 0], b[0, 0])
+        if o.have_ref():
+            assert digest(*o.ref_ssim(a, b, want_map=True)) == ref, (a[0, 0], b[0, 0])
+
+
+def test_naive_f64_identical(recorded):
+    a, b = naive_pair()
     v, _, m = o.ssim_naive_f64(a, b, want_map=True)
-    rv, rm = o.ref_naive_f64(a, b, want_map=True)
-    assert v == rv and np.array_equal(m, rm)
+    assert digest(v, v, m) == recorded["naive_f64"]         # "sum": the double value itself, exactly
+    if o.have_ref():
+        rv, rm = o.ref_naive_f64(a, b, want_map=True)
+        assert digest(rv, rv, rm) == recorded["naive_f64"]
 
 
-def test_reference_openmp_path_same_float():
+def test_reference_openmp_path_same_float(recorded):
     a, b = o.synth_pair(1920, 1080, 0x5EED)
-    v1, _, _ = o.ref_ssim(a, b, threads=1)
-    v8, _, _ = o.ref_ssim(a, b, threads=8)
-    ov, _, _ = o.ssim_f32(a, b, threads=8)
-    assert f32_hex(v1) == f32_hex(v8) == f32_hex(ov) == "0x3f64bb1f"
+    want = recorded["openmp_1080p_5eed"]
+    assert want["1"] == want["8"] == "0x3f64bb1f"
+    for t in (1, 8):
+        assert f32_hex(o.ssim_f32(a, b, threads=t)[0]) == want[str(t)]
+        if o.have_ref():
+            assert f32_hex(o.ref_ssim(a, b, threads=t)[0]) == want[str(t)]

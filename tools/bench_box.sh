@@ -1,11 +1,11 @@
 #!/bin/bash
-# Runs ON THE GPU BOX: `python bench.py` alone (the driver's command plus the default step count), for the box spread of tools/pick_median_box.py.
+# Runs ON THE GPU BOX: `python bench.py --full` alone (every leg, the default step count), for the box spread of tools/pick_median_box.py.
 # usage: tools/bench_box.sh <out-subdir-of-gpurun_out>
 cd "$(dirname "$0")/.."
 OUT=gpurun_out/${1:-box}; mkdir -p "$OUT"
-timeout 900 python3 bench.py > "$OUT/bench_4k.log" 2>&1
+timeout 900 python3 bench.py --full > "$OUT/bench_4k.log" 2>&1
 grep '"metric"' "$OUT/bench_4k.log" > "$OUT/bench_4k.json"
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-cold-start --no-configs > "$OUT/bench_driver_flags.log" 2>&1
+timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-cold-start --no-configs > "$OUT/bench_driver_flags.log" 2>&1
 grep '"metric"' "$OUT/bench_driver_flags.log" > "$OUT/bench_driver_flags.json"
 python3 -c "
 import json

@@ -20,16 +20,16 @@ for cfg in "4k 32 3 0 0 4096 4096" "8kmap 2 3 0 1 8192 8192" "1080p 128 3 0 0 19
 done
 python3 tools/make_traffic_json.py "$OUT" r06 profiles/traffic.json > "$OUT/traffic_ratios.json" && cp profiles/traffic.json "$OUT/traffic.json"
 for wl in 4k 8k-map 1080p; do
-  timeout 600 python3 bench.py --workload $wl > "$OUT/bench_$wl.log" 2>&1
+  timeout 600 python3 bench.py --full --workload $wl > "$OUT/bench_$wl.log" 2>&1
   grep '"metric"' "$OUT/bench_$wl.log" > "$OUT/bench_$wl.json"
 done
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- python3 bench.py --no-cpu-baseline --no-cold-start --sustain 0 > "$OUT/bench_under_rocprof.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- python3 bench.py --full --no-cpu-baseline --no-cold-start --sustain 0 > "$OUT/bench_under_rocprof.log" 2>&1
 # the exchange step on a 1-rank communicator: the product's own carrier (--exchange native), torch's, and configs[3] whole
-SSIM_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --no-cpu-baseline --no-cold-start --no-configs --sustain 0 --exchange native > "$OUT/bench_rccl_1rank.log" 2>&1
+SSIM_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --full --no-cpu-baseline --no-cold-start --no-configs --sustain 0 --exchange native > "$OUT/bench_rccl_1rank.log" 2>&1
 grep '"metric"' "$OUT/bench_rccl_1rank.log" > "$OUT/bench_rccl_1rank.json"
-SSIM_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --no-cpu-baseline --no-cold-start --no-configs --sustain 0 --exchange torch > "$OUT/bench_rccl_1rank_torch.log" 2>&1
+SSIM_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --full --no-cpu-baseline --no-cold-start --no-configs --sustain 0 --exchange torch > "$OUT/bench_rccl_1rank_torch.log" 2>&1
 grep '"metric"' "$OUT/bench_rccl_1rank_torch.log" > "$OUT/bench_rccl_1rank_torch.json"
-SSIM_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --no-cpu-baseline --no-cold-start --no-configs --sustain 0 --workload 1080p --scaling strong > "$OUT/bench_c4_strong.log" 2>&1
+SSIM_BENCH_FORCE_DIST=1 timeout 600 python3 bench.py --full --no-cpu-baseline --no-cold-start --no-configs --sustain 0 --workload 1080p --scaling strong > "$OUT/bench_c4_strong.log" 2>&1
 grep '"metric"' "$OUT/bench_c4_strong.log" > "$OUT/bench_c4_strong.json"
 for m in single absent-peer shards; do RMGR_SSIM_HIP_COMM_TIMEOUT_S=10 timeout 100 python3 tools/rccl_selftest.py $m 2>&1 | grep "rccl_selftest\|rmgr-ssim comm"; done > "$OUT/rccl_selftest.txt"
 timeout 150 python3 tools/rccl_selftest.py single --with-torch 2>&1 | grep "rccl_selftest\|rmgr-ssim comm" >> "$OUT/rccl_selftest.txt"

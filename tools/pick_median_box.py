@@ -28,7 +28,7 @@ def main():
     lines.sort(key=lambda x: x[2]["value"])
     med = lines[(len(lines) - 1) // 2]                      # the lower median for an even count: never the flattering one
     shutil.copyfile(med[1], os.path.join(ROOT, "profiles", "%s_final_bench.json" % tag))
-    out = ["# Round %s: `python bench.py` of the final library on %d boxes (one gpurun call each = a fresh box).  The published line, `profiles/%s_final_bench.json`, is the MEDIAN by `value`" % (tag[1:].lstrip("0"), len(lines), tag),
+    out = ["# Round %s: `python bench.py --full` of the final library on %d boxes (a fresh box each).  The published line, `profiles/%s_final_bench.json`, is the MEDIAN by `value`" % (tag[1:].lstrip("0"), len(lines), tag),
            "# (marked); round 5 published its fastest of seven.  `valu.frac_of_box_peak_at_kernel_occupancy` divides the kernel's lane-operations per second by the SAME box's forced-occupancy",
            "# v_pk_fma_f32 rate (rmgr_ssim_hip_probe_valu, probed in-process before the warm-up and after the timed steps): boxes differ in `value`, the fraction should not.", "",
            "| collection | `value` Mpix/s | headline kernel ms | box peak 2 waves / 8 waves (T lane-ops/s) | shader MHz under the kernel (slowest XCD) / under the probe | kernel / box two-wave peak | the same PER CLOCK | / 78.6 T data sheet | 128 x 1080p exact Mpix/s (fraction of box peak; per clock) | separable 32 x 4096^2 Mpix/s | plan_regret headline / 1080p x128 |",
