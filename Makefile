@@ -29,7 +29,7 @@ lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr
 # a group of the same signature (anything using std::make_shared, std::thread, ...) makes the final link discard the
 # archive's copy and leaves its now-local references dangling ("defined in discarded section").  Allocated into ordinary
 # sections here, the archive's copies are private to it and always kept.
-$(OUT)/librmgr-ssim.a: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_dropin.o
+$(OUT)/librmgr-ssim.a: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_dropin.o
 	@mkdir -p $(OUT)
 	ld -r --force-group-allocation -o $(OBJ)/rmgr_ssim_api.o $^
 	objcopy --wildcard --keep-global-symbol='rmgr_ssim_*' --keep-global-symbol='_ZN4rmgr4ssim12compute_ssimE*' --keep-global-symbol='_ZN4rmgr4ssim11select_implE*' $(OBJ)/rmgr_ssim_api.o
@@ -57,7 +57,12 @@ $(OBJ)/ssim_probe.o: $(SRC)/ssim_probe.hip $(SRC)/ssim_kernels.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJ)/ssim_hip_abi.o: $(SRC)/ssim_hip_abi.cpp $(SRC)/ssim_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+# Multi-scale SSIM (rmgr_ssim_hip_compute_msssim_*): its own file for the same reason.
+$(OBJ)/msssim_kernels.o: $(SRC)/msssim_kernels.hip $(SRC)/msssim_kernels.h $(SRC)/ssim_kernels.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(OBJ)/ssim_hip_abi.o: $(SRC)/ssim_hip_abi.cpp $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
@@ -69,7 +74,7 @@ $(OBJ)/ssim_dropin.o: $(SRC)/ssim_dropin.cpp $(SRC)/ssim_internal.h include/rmgr
 # Only the API leaves the shared libraries: $(SRC)/exports.map (the reference's archive exposes only its API as well).
 EXPORTS := -Wl,--version-script=$(SRC)/exports.map
 
-$(OUT)/librmgr-ssim-hip.so: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_dropin.o $(OBJ)/ssim_openmp.o $(SRC)/exports.map
+$(OUT)/librmgr-ssim-hip.so: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_dropin.o $(OBJ)/ssim_openmp.o $(SRC)/exports.map
 	@mkdir -p $(OUT)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(EXPORTS) -o $@ $(filter %.o,$^)
 
@@ -77,11 +82,11 @@ $(OUT)/librmgr-ssim-hip.so: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/ssi
 # flavour of the same library: identical kernels and drop-in layer, only the C ABI's default arithmetic differs (fp64
 # internals for every unchanged rmgr_ssim_compute_ssim call; BASELINE.json configs[4]).  `make DOUBLE=1` gives the same
 # thing under the main name.
-$(OBJ)/ssim_hip_abi_double.o: $(SRC)/ssim_hip_abi.cpp $(SRC)/ssim_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+$(OBJ)/ssim_hip_abi_double.o: $(SRC)/ssim_hip_abi.cpp $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRMGR_SSIM_USE_DOUBLE=1 -x hip -c $< -o $@
 
-$(OUT)/librmgr-ssim-hip-double.so: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/ssim_hip_abi_double.o $(OBJ)/ssim_dropin.o $(OBJ)/ssim_openmp.o $(SRC)/exports.map
+$(OUT)/librmgr-ssim-hip-double.so: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim_hip_abi_double.o $(OBJ)/ssim_dropin.o $(OBJ)/ssim_openmp.o $(SRC)/exports.map
 	@mkdir -p $(OUT)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(EXPORTS) -o $@ $(filter %.o,$^)
 

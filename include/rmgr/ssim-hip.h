@@ -19,6 +19,7 @@
  *   rmgr_ssim_hip_compute_ssim_luminance_host  RGB -> BT.601 Y, then SSIM        src/ssim-cli.cpp:145-195
  *   rmgr_ssim_hip_luminance_device             the conversion loop alone          src/ssim-cli.cpp:158-186
  *   rmgr_ssim_hip_set_mode             select_impl() / RMGR_SSIM_USE_DOUBLE   src/ssim.cpp:808-896, src/ssim_internal.h:26-37
+ *   rmgr_ssim_hip_compute_msssim_device / _host   multi-scale SSIM: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -301,6 +302,46 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssim_luminance_host(rmgr_ssim_hip_Context* ct
 rmgr_int32_t rmgr_ssim_hip_luminance_device(rmgr_ssim_hip_Context* ctx, rmgr_uint8_t* dstY, ptrdiff_t dstStride,
                                             const rmgr_uint8_t* src, ptrdiff_t srcStep, ptrdiff_t srcStride,
                                             rmgr_uint32_t width, rmgr_uint32_t height) RMGR_NOEXCEPT;
+
+/*
+ * Multi-scale SSIM (MS-SSIM; Wang, Simoncelli & Bovik, "Multi-scale structural similarity for image quality assessment", 2003) of
+ * `count` uint8 pairs of one size.  No reference counterpart: the definition is pinned down here, and tests/msssim_model.py restates it
+ * in float64.
+ *
+ *   Inputs   params[0 .. count-1]: width, height (the same for every pair), imgA / imgB with any step / stride in bytes, negative ones
+ *            included.  ssimMap must be NULL (MS-SSIM has no per-pixel map); alloc / dealloc are not used.
+ *   Scales   1 <= scales <= RMGR_SSIM_HIP_MSSSIM_MAX_SCALES.  Scale 0 is the input; scale s+1 is ceil(W_s/2) x ceil(H_s/2) with
+ *              P_{s+1}(x,y) = ((P_s(2x,2y) + P_s(2x+1,2y)) + (P_s(2x,2y+1) + P_s(2x+1,2y+1))) * 0.25,
+ *            coordinates outside scale s clamped to its last row / column (the 2x2 box filter + decimation of Wang's msssim.m; TF's
+ *            symmetric pad + avg_pool).  In fp32 this pyramid is EXACT up to scale 8: scale s holds multiples of 4^-s below 256, and the
+ *            sum of four needs at most 10 + 2s <= 24 significand bits.
+ *   Per scale for every pixel, the blurred moments mu_a, mu_b, sigma_a^2, sigma_b^2, sigma_ab: the separable 11 + 11 tap Gaussian
+ *            (sigma 1.5, normalised over the 11 taps, fp32 taps) with CLAMPED edges, as everywhere in this library, so the statistics
+ *            are same-size: every pixel of the scale counts.  This differs from the "valid" window of TensorFlow's ssim_multiscale and
+ *            pytorch-msssim, which drop a 5-pixel border at every scale: values are close but not equal, most of all on small scales.
+ *              cs = (2 sigma_ab + C2) / (sigma_a^2 + sigma_b^2 + C2),  l = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1),  ssim = l * cs,
+ *            C1 = 6.5025f, C2 = 58.5225f (the engine's).  mcs_s and mssim_s are fp64 sums of cs and ssim over the scale divided by W_s * H_s.
+ *   Result   MS-SSIM = prod_{s < M-1} max(mcs_s, 0)^w_s * max(mssim_{M-1}, 0)^w_{M-1} in double (M = scales; the ReLU of TF and
+ *            pytorch-msssim keeps negative means from producing NaN), returned as float in msssim[i].
+ *            weights == NULL: Wang's {0.0448, 0.2856, 0.3001, 0.2363, 0.1333}, and scales must be 5.  Otherwise `scales` finite weights >= 0.
+ *   Arithmetic  fp32 with centred moments as in MODE_SEPARABLE, but centred on an integer per 64 x 16 tile (the floor of the tile's
+ *            middle pixel, per image) instead of 128: still exact, and much smaller cancellation on few-pixel scales.  The context's mode
+ *            does not change MS-SSIM.
+ *   Determinism  each image's sums run over fixed tiles of each scale in a fixed order: a pair gives the same bits alone or anywhere in a
+ *            batch of any size, through either entry point, on every call.
+ *   Outputs  msssim: count floats (host memory).  scaleMeans: NULL, or count x scales x 2 doubles (host memory), [image][scale]{mcs, mssim}.
+ *
+ * _device: the image pointers are device memory; ctx must not be NULL.  _host: host memory, copied to the device as it is (ctx NULL: a
+ * default context, as rmgr_ssim_hip_compute_ssim_host).  Both block.  Device scratch: about 2.7 bytes per scale-0 pixel for the pyramid
+ * (plus the staged images for _host); a batch is run in sub-batches that keep it under about 1 GB -- results do not depend on the split.
+ * EINVAL: count == 0, a NULL pointer (params, msssim, an image), a zero or differing size, a non-NULL ssimMap, scales out of range, weights
+ * NULL with scales != 5, a weight that is negative or not finite -- all checked before any device is touched.  ENODEV: no device.
+ */
+#define RMGR_SSIM_HIP_MSSSIM_MAX_SCALES 8
+rmgr_int32_t rmgr_ssim_hip_compute_msssim_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_Params* params,
+                                                 rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_Params* params,
+                                               rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

@@ -91,6 +91,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_rows", "rmgr_ssim_hip_reduce_cells", "rmgr_ssim_hip_probe_valu",
     "rmgr_ssim_hip_trim", "rmgr_ssim_hip_trim_default_pool", "rmgr_ssim_hip_get_default_pool_memory", "rmgr_ssim_hip_get_memory_info",
     "rmgr_ssim_hip_tune", "rmgr_ssim_hip_clear_tuned", "rmgr_ssim_hip_get_tuned", "rmgr_ssim_hip_set_tuned", "rmgr_ssim_hip_get_profile_clock",
+    "rmgr_ssim_hip_compute_msssim_device", "rmgr_ssim_hip_compute_msssim_host",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -162,6 +163,8 @@ def load_library(path=None):
         "rmgr_ssim_hip_trim_default_pool": [],
         "rmgr_ssim_hip_get_default_pool_memory": [ctypes.POINTER(ctypes.c_uint64)] * 3,
         "rmgr_ssim_hip_get_memory_info": [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+        "rmgr_ssim_hip_compute_msssim_device": [vp, u32, PP, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssim_host": [vp, u32, PP, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
     }
     for name, args in sig.items():
         if path is None and os.environ.get("RMGR_SSIM_LIB") and not hasattr(lib, name):
@@ -347,6 +350,46 @@ def compute_ssim_luminance(a, b, want_map=False):
     return np.float32(out.value), m
 
 
+MSSSIM_MAX_SCALES = 8     # RMGR_SSIM_HIP_MSSSIM_MAX_SCALES
+MSSSIM_WANG_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def _msssim_call(fn_name, handle, params, count, scales, weights, per_scale):
+    lib = load_library()
+    w = None
+    if weights is not None:
+        w = (ctypes.c_double * max(len(weights), 1))(*[float(x) for x in weights])
+    out = (ctypes.c_float * max(count, 1))()
+    means = (ctypes.c_double * max(count * scales * 2, 1))() if per_scale else None
+    _check(fn_name, getattr(lib, fn_name)(handle, count, params, scales, w, out, means))
+    vals = np.array(out[:count], np.float32)
+    if not per_scale:
+        return vals
+    return vals, np.array(means[:count * scales * 2], np.float64).reshape(count, scales, 2)
+
+
+def compute_msssim(a, b, scales=5, weights=None, per_scale=False, ctx=None):
+    """Multi-scale SSIM of two H x W uint8 host arrays (any strides numpy can express, negative ones included) through
+    rmgr_ssim_hip_compute_msssim_host.  weights None: Wang's five (scales must be 5).  Returns a float32, and with
+    per_scale=True also a (scales, 2) float64 array of [scale]{mcs, mssim}."""
+    assert a.shape == b.shape and a.ndim == 2 and a.dtype == np.uint8 and b.dtype == np.uint8
+    h, w = a.shape
+    params = (Params * 1)()
+    params[0] = make_params(w, h, a.ctypes.data, a.strides[1], a.strides[0], b.ctypes.data, b.strides[1], b.strides[0])
+    r = _msssim_call("rmgr_ssim_hip_compute_msssim_host", ctx.handle if ctx is not None else None, params, 1, scales, weights, per_scale)
+    return (r[0][0], r[1][0]) if per_scale else r[0]
+
+
+def compute_msssim_batch(pairs, scales=5, weights=None, per_scale=False, ctx=None):
+    """compute_msssim() of many host pairs of one size in one call: a float32 array (and a (count, scales, 2) array with per_scale)."""
+    n = len(pairs)
+    params = (Params * max(n, 1))()
+    for i, (a, b) in enumerate(pairs):
+        h, w = a.shape
+        params[i] = make_params(w, h, a.ctypes.data, a.strides[1], a.strides[0], b.ctypes.data, b.strides[1], b.strides[0])
+    return _msssim_call("rmgr_ssim_hip_compute_msssim_host", ctx.handle if ctx is not None else None, params, n, scales, weights, per_scale)
+
+
 class DeviceBuffer(object):
     def __init__(self, ctx, nbytes):
         self.ctx, self.nbytes = ctx, nbytes
@@ -460,6 +503,11 @@ class Context(object):
         rc = self.lib.rmgr_ssim_hip_compute_ssim_device(self.handle, ctypes.byref(out) if want_global else None, ctypes.byref(params))
         _check("rmgr_ssim_hip_compute_ssim_device", rc)
         return np.float32(out.value)
+
+    def msssim_device(self, params_array, count, scales=5, weights=None, per_scale=False):
+        """MS-SSIM of `count` device-resident pairs (a Params array) through rmgr_ssim_hip_compute_msssim_device: a float32 array,
+        and with per_scale=True also a (count, scales, 2) float64 array of [image][scale]{mcs, mssim}."""
+        return _msssim_call("rmgr_ssim_hip_compute_msssim_device", self.handle, params_array, count, scales, weights, per_scale)
 
     def enqueue_batch(self, params_array, count, sums_dev_ptr):
         _check("rmgr_ssim_hip_enqueue_batch", self.lib.rmgr_ssim_hip_enqueue_batch(self.handle, count, params_array, sums_dev_ptr))

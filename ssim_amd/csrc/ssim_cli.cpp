@@ -919,7 +919,8 @@ void print_help(FILE* file)
                   "  -#  Compute SSIM only for channel #\n"
                   "  -y  Compute SSIM on luminance\n"
                   "      For images with <= 2 channels, only channel 0's SSIM will be computed\n"
-                  "      For images with >= 3 channels, first three channels are converted from RGB to Y\n\n");
+                  "      For images with >= 3 channels, first three channels are converted from RGB to Y\n"
+                  "  -m  Compute multi-scale SSIM (5 scales, Wang's weights) of every channel; no map\n\n");
 }
 
 int report(rmgr_int32_t rc)
@@ -930,10 +931,11 @@ int report(rmgr_int32_t rc)
 }
 
 // ---- the command, as data ----
-// What to compare: every channel (the default), one channel (-0 .. -3) or the BT.601 luminance (-y).  Behaviour and
+// What to compare: every channel (the default), one channel (-0 .. -3), the BT.601 luminance (-y) or MS-SSIM of every channel (-m, this
+// tool's own addition: include/rmgr/ssim-hip.h).  Behaviour and
 // printed text are the reference tool's (src/ssim-cli.cpp:130-213, :216-389); the structure is this file's own.
 struct Selection {
-    enum Kind { EVERY_CHANNEL, ONE_CHANNEL, LUMA } kind;
+    enum Kind { EVERY_CHANNEL, ONE_CHANNEL, LUMA, MSSSIM } kind;
     int channel;
 };
 
@@ -945,7 +947,7 @@ struct Command {
 
 const struct { const char* flag; Selection sel; } kFlags[] = {
     {"-0", {Selection::ONE_CHANNEL, 0}}, {"-1", {Selection::ONE_CHANNEL, 1}}, {"-2", {Selection::ONE_CHANNEL, 2}},
-    {"-3", {Selection::ONE_CHANNEL, 3}}, {"-y", {Selection::LUMA, 0}},
+    {"-3", {Selection::ONE_CHANNEL, 3}}, {"-y", {Selection::LUMA, 0}}, {"-m", {Selection::MSSSIM, 0}},
 };
 
 // argv -> Command.  false: usage error (the message has been printed).
@@ -965,6 +967,10 @@ bool parse_command(int argc, char* argv[], Command& cmd)
     cmd.file[0] = argv[first];
     cmd.file[1] = argv[first + 1];
     cmd.mapFile = (argc - first == 3) ? argv[first + 2] : NULL;
+    if (cmd.what.kind == Selection::MSSSIM && cmd.mapFile) {
+        fprintf(stderr, "MS-SSIM has no per-pixel map: -m takes no map argument\n");
+        return false;
+    }
     return true;
 }
 
@@ -982,7 +988,8 @@ int compare(const Image& a, const Image& b, Selection what, float* map, int mapC
     const ptrdiff_t pitch = ptrdiff_t(w) * ch;
     if (what.kind == Selection::LUMA && ch < 3)            // nothing to weigh: the first channel is the luminance
         what.kind = Selection::ONE_CHANNEL, what.channel = 0;
-    std::vector<float> value(what.kind == Selection::EVERY_CHANNEL ? ch : 1u);
+    const bool perChannel = what.kind == Selection::EVERY_CHANNEL || what.kind == Selection::MSSSIM;
+    std::vector<float> value(perChannel ? ch : 1u);
     rmgr_int32_t rc;
     switch (what.kind) {
     case Selection::ONE_CHANNEL: {
@@ -995,6 +1002,18 @@ int compare(const Image& a, const Image& b, Selection what, float* map, int mapC
         rc = rmgr_ssim_compute_ssim(&value[0], &p, NULL);
         break;
     }
+    case Selection::MSSSIM: {
+        // every channel in one call: Wang's five scales and weights (include/rmgr/ssim-hip.h)
+        std::vector<rmgr_ssim_Params> p(ch);
+        memset(&p[0], 0, sizeof(rmgr_ssim_Params) * ch);
+        for (rmgr_uint32_t c = 0; c < ch; ++c) {
+            p[c].width = w; p[c].height = h;
+            rmgr_ssim_init_interleaved(&p[c].imgA, &a.px[0], pitch, ch, c);
+            rmgr_ssim_init_interleaved(&p[c].imgB, &b.px[0], pitch, ch, c);
+        }
+        rc = rmgr_ssim_hip_compute_msssim_host(NULL, ch, &p[0], 5, NULL, &value[0], NULL);
+        break;
+    }
     case Selection::LUMA:
         rc = rmgr_ssim_hip_compute_ssim_luminance_host(NULL, &value[0], &a.px[0], pitch, &b.px[0], pitch, w, h, ch, map);
         break;
@@ -1003,7 +1022,7 @@ int compare(const Image& a, const Image& b, Selection what, float* map, int mapC
         break;
     }
     if (rc != 0) return report(rc);
-    if (what.kind != Selection::EVERY_CHANNEL) {
+    if (!perChannel || (what.kind == Selection::MSSSIM && ch == 1)) {
         printf("% 7.4f\n", value[0]);
         return EXIT_SUCCESS;
     }

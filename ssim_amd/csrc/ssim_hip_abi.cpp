@@ -6,12 +6,14 @@
 // no gfx950 device is usable every entry point fails loudly with ENODEV.
 #include <rmgr/ssim-hip.h>
 #include "ssim_kernels.h"
+#include "msssim_kernels.h"
 #include <rccl/rccl.h>      // types only: the library is dlopen()ed on first use, never linked
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +71,12 @@ struct rmgr_ssim_hip_Context_ {
     uint8_t*  h_stage;      size_t h_stage_cap;    // bytes: small image pairs are gathered here for one DMA
     float*    h_map[2];     size_t h_map_cap[2];   // floats: bounce buffers for the map copy-back
     hipEvent_t map_ev[2];
+    // multi-scale SSIM (rmgr_ssim_hip_compute_msssim_*): pyramid planes + tile partials, descriptor table, per-scale sums
+    uint8_t*  ms_scratch;   size_t ms_scratch_cap;  // bytes
+    PairDesc* ms_desc;      size_t ms_desc_cap;     // entries (device)
+    PairDesc* ms_desc_pin;  size_t ms_desc_pin_cap; // entries (pinned mirror)
+    double*   ms_sums;      size_t ms_sums_cap;     // doubles (device)
+    double*   ms_sums_pin;  size_t ms_sums_pin_cap; // doubles (pinned)
 
     bool profiling;
     uint64_t* clock_dev;      // kClockWords device counters the profiled strip launches' first workgroups (one per XCD) add their shader cycles / reference ticks to (ssim_kernels.hip clock_begin); NULL until profiling is first enabled
@@ -732,6 +740,8 @@ void context_held(const rmgr_ssim_hip_Context* c, uint64_t& dev, uint64_t& pin)
         + c->slot_dev_cap[0] + c->slot_dev_cap[1] + (uint64_t)c->batch_sums_cap * sizeof(double);
     pin = (uint64_t)c->h_sums_cap * sizeof(double) + c->slot_pin_cap[0] + c->slot_pin_cap[1] + c->h_stage_cap
         + ((uint64_t)c->h_map_cap[0] + c->h_map_cap[1]) * sizeof(float);
+    dev += c->ms_scratch_cap + (uint64_t)c->ms_desc_cap * sizeof(PairDesc) + (uint64_t)c->ms_sums_cap * sizeof(double);
+    pin += (uint64_t)c->ms_desc_pin_cap * sizeof(PairDesc) + (uint64_t)c->ms_sums_pin_cap * sizeof(double);
     for (int i = 0; i < rmgr_ssim_hip_Context_::kDescSlots; ++i) {
         dev += (uint64_t)c->desc_slots[i].dev_cap * sizeof(PairDesc);
         pin += (uint64_t)c->desc_slots[i].host_cap * sizeof(PairDesc);
@@ -773,6 +783,11 @@ int context_trim(rmgr_ssim_hip_Context* c)
         Drop::pin(c->h_map[i]); c->h_map[i] = NULL; c->h_map_cap[i] = 0;
     }
     Drop::dev(c->batch_sums); c->batch_sums = NULL; c->batch_sums_cap = 0;
+    Drop::dev(c->ms_scratch); c->ms_scratch = NULL; c->ms_scratch_cap = 0;
+    Drop::dev(c->ms_desc); c->ms_desc = NULL; c->ms_desc_cap = 0;
+    Drop::pin(c->ms_desc_pin); c->ms_desc_pin = NULL; c->ms_desc_pin_cap = 0;
+    Drop::dev(c->ms_sums); c->ms_sums = NULL; c->ms_sums_cap = 0;
+    Drop::pin(c->ms_sums_pin); c->ms_sums_pin = NULL; c->ms_sums_pin_cap = 0;
     (void)hipGetLastError();
     return rc;
 }
@@ -879,6 +894,11 @@ rmgr_int32_t rmgr_ssim_hip_create(rmgr_ssim_hip_Context** out, rmgr_int32_t devi
     for (int i = 0; i < rmgr_ssim_hip_Context_::kMaxBands; ++i) c->band_copied[i] = c->band_done[i] = NULL;
     c->h_map[0] = c->h_map[1] = NULL; c->h_map_cap[0] = c->h_map_cap[1] = 0;
     c->map_ev[0] = c->map_ev[1] = NULL;
+    c->ms_scratch = NULL; c->ms_scratch_cap = 0;
+    c->ms_desc = NULL; c->ms_desc_cap = 0;
+    c->ms_desc_pin = NULL; c->ms_desc_pin_cap = 0;
+    c->ms_sums = NULL; c->ms_sums_cap = 0;
+    c->ms_sums_pin = NULL; c->ms_sums_pin_cap = 0;
     c->comm = NULL;
     c->comm_nonblocking = false;
     c->comm_ranks = 0;
@@ -933,6 +953,11 @@ rmgr_int32_t rmgr_ssim_hip_destroy(rmgr_ssim_hip_Context* c) RMGR_NOEXCEPT
         if (c->slot_done[i]) (void)hipEventDestroy(c->slot_done[i]);
     }
     if (c->batch_sums) (void)hipFree(c->batch_sums);
+    if (c->ms_scratch) (void)hipFree(c->ms_scratch);
+    if (c->ms_desc) (void)hipFree(c->ms_desc);
+    if (c->ms_desc_pin) (void)hipHostFree(c->ms_desc_pin);
+    if (c->ms_sums) (void)hipFree(c->ms_sums);
+    if (c->ms_sums_pin) (void)hipHostFree(c->ms_sums_pin);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->out_stream) (void)hipStreamDestroy(c->out_stream);
     for (int i = 0; i < rmgr_ssim_hip_Context_::kMaxBands; ++i) {
@@ -1382,6 +1407,158 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssim_host(rmgr_ssim_hip_Context* c, float* ss
     if (ssim)
         *ssim = mean_of(c->h_sums[0], W, H);
     return 0;
+}
+
+// ---- multi-scale SSIM (rmgr_ssim_hip_compute_msssim_*) ------------------------------------------------------------------------------------------
+// The definition is in include/rmgr/ssim-hip.h, the kernels in msssim_kernels.hip.  A batch runs in sub-batches whose device scratch (pyramid,
+// tile partials and, for host pointers, the staged images) stays under kMsScratchCap; every image's statistics are summed over fixed tiles in a
+// fixed order, so the split changes nothing in the results.
+namespace {
+
+const double   kWangWeights[5] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};     // msssim.m (Wang, Simoncelli & Bovik 2003)
+const uint64_t kMsScratchCap = uint64_t(1) << 30;
+
+// Every check of the two entry points, before any device is touched.
+int msssim_validate(rmgr_uint32_t count, const rmgr_ssim_Params* params, rmgr_uint32_t scales, const double* weights, const float* msssim)
+{
+    if (count == 0 || params == NULL || msssim == NULL) return EINVAL;
+    if (scales < 1 || scales > RMGR_SSIM_HIP_MSSSIM_MAX_SCALES) return EINVAL;
+    if (weights == NULL) {
+        if (scales != 5) return EINVAL;
+    } else {
+        for (uint32_t s = 0; s < scales; ++s)
+            if (!std::isfinite(weights[s]) || weights[s] < 0.0) return EINVAL;
+    }
+    const uint32_t W = params[0].width, H = params[0].height;
+    if (W == 0 || H == 0) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i) {
+        const rmgr_ssim_Params& p = params[i];
+        if (p.width != W || p.height != H) return EINVAL;
+        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL || p.ssimMap != NULL) return EINVAL;
+    }
+    if (ssim_hip::msssim_max_count(W, H, scales) == 0) return EINVAL;      // one pair beyond a launch grid (tens of gigapixels)
+    return 0;
+}
+
+// prod_{s < M-1} max(mcs_s, 0)^w_s * max(mssim_{M-1}, 0)^w_{M-1}, in double; means = [scale]{mcs, mssim}
+float msssim_combine(const double* means, uint32_t scales, const double* w)
+{
+    double r = 1.0;
+    for (uint32_t s = 0; s < scales; ++s) {
+        const double v = means[2 * s + (s + 1 == scales ? 1 : 0)];
+        r *= std::pow(v > 0.0 ? v : 0.0, w[s]);
+    }
+    return (float)r;
+}
+
+// n pairs (device descriptors in d) -> their n x scales x 2 means.  Blocks.
+int msssim_run(rmgr_ssim_hip_Context* c, uint32_t n, const PairDesc* d, uint32_t W, uint32_t H, uint32_t scales, double* means)
+{
+    int rc;
+    const size_t ns = (size_t)n * scales * 2;
+    if ((rc = grow_pinned(c->ms_desc_pin, c->ms_desc_pin_cap, n))) return rc;
+    if ((rc = grow_device(c->ms_desc, c->ms_desc_cap, n))) return rc;
+    if ((rc = grow_device(c->ms_scratch, c->ms_scratch_cap, ssim_hip::msssim_scratch_bytes(W, H, n, scales)))) return rc;
+    if ((rc = grow_device(c->ms_sums, c->ms_sums_cap, ns))) return rc;
+    if ((rc = grow_pinned(c->ms_sums_pin, c->ms_sums_pin_cap, ns))) return rc;
+    memcpy(c->ms_desc_pin, d, n * sizeof(PairDesc));
+    HIP_TRY(hipMemcpyAsync(c->ms_desc, c->ms_desc_pin, n * sizeof(PairDesc), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ssim_hip::launch_msssim(c->ms_desc, n, W, H, scales, c->ms_scratch, c->ms_sums, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ms_sums_pin, c->ms_sums, ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t s = 0; s < scales; ++s) {
+        const double px = (double)ssim_hip::ms_dim(W, s) * (double)ssim_hip::ms_dim(H, s);
+        for (uint32_t i = 0; i < n; ++i)
+            for (int k = 0; k < 2; ++k) means[((size_t)i * scales + s) * 2 + k] = c->ms_sums_pin[((size_t)i * scales + s) * 2 + k] / px;
+    }
+    return 0;
+}
+
+// The whole batch, sub-batch by sub-batch; stage: the images are host memory, copied (plain copies of each image's byte range) into c->stage_a first.
+int msssim_batches(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_Params* params, uint32_t scales, const double* w,
+                   float* msssim, double* scaleMeans, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const uint64_t per = ssim_hip::msssim_scratch_bytes(W, H, 1, scales);
+    const uint32_t nmax = (uint32_t)std::min<uint64_t>(ssim_hip::msssim_max_count(W, H, scales), std::max<uint64_t>(1, kMsScratchCap / per));
+    try {
+        std::vector<PairDesc> d;
+        std::vector<int64_t> lo, off;           // stage: byte range start of A, B per pair, and where it goes in c->stage_a
+        std::vector<double> means;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint32_t n = 0;
+            uint64_t staged = 0;
+            lo.clear(); off.clear();
+            while (i0 + n < count && n < nmax) {
+                uint64_t bytes = 0;
+                int64_t l[2] = {0, 0}, hi[2] = {0, 0};
+                if (stage) {
+                    extent(params[i0 + n].imgA, W, H, l[0], hi[0]);
+                    extent(params[i0 + n].imgB, W, H, l[1], hi[1]);
+                    bytes = (uint64_t)((hi[0] - l[0] + 64) & ~int64_t(63)) + (uint64_t)((hi[1] - l[1] + 64) & ~int64_t(63));
+                }
+                if (n > 0 && per * (n + 1) + staged + bytes > kMsScratchCap) break;
+                if (stage) {
+                    lo.push_back(l[0]); off.push_back((int64_t)staged);
+                    lo.push_back(l[1]); off.push_back((int64_t)staged + ((hi[0] - l[0] + 64) & ~int64_t(63)));
+                }
+                staged += bytes;
+                ++n;
+            }
+            d.resize(n);
+            int rc;
+            if (stage && (rc = grow_device(c->stage_a, c->stage_a_cap, (size_t)staged))) return rc;
+            for (uint32_t i = 0; i < n; ++i) {
+                rmgr_ssim_Params p = params[i0 + i];
+                p.ssimMap = NULL;
+                if (stage) {
+                    for (int k = 0; k < 2; ++k) {
+                        const rmgr_ssim_ImgParams& im = k ? p.imgB : p.imgA;
+                        int64_t l, hi;
+                        extent(im, W, H, l, hi);
+                        HIP_TRY(hipMemcpyAsync(c->stage_a + off[2 * i + k], im.topLeft + l, (size_t)(hi - l + 1), hipMemcpyHostToDevice, c->stream));
+                    }
+                    p.imgA.topLeft = c->stage_a + off[2 * i] - lo[2 * i];
+                    p.imgB.topLeft = c->stage_a + off[2 * i + 1] - lo[2 * i + 1];
+                }
+                d[i] = make_desc(p);
+            }
+            means.resize((size_t)n * scales * 2);
+            if ((rc = msssim_run(c, n, &d[0], W, H, scales, &means[0]))) return rc;
+            for (uint32_t i = 0; i < n; ++i) {
+                msssim[i0 + i] = msssim_combine(&means[(size_t)i * scales * 2], scales, w);
+                if (scaleMeans) memcpy(scaleMeans + (size_t)(i0 + i) * scales * 2, &means[(size_t)i * scales * 2], scales * 2 * sizeof(double));
+            }
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+} // namespace
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssim_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_Params* params,
+                                                 rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    if (!c) return EINVAL;
+    int rc = msssim_validate(count, params, scales, weights, msssim);
+    if (rc) return rc;
+    USE_DEVICE(c);
+    return msssim_batches(c, count, params, scales, weights ? weights : kWangWeights, msssim, scaleMeans, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssim_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_Params* params,
+                                               rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    int rc = msssim_validate(count, params, scales, weights, msssim);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    c = lease.c;
+    USE_DEVICE(c);
+    return msssim_batches(c, count, params, scales, weights ? weights : kWangWeights, msssim, scaleMeans, true);
 }
 
 // ---- one process, several devices ------------------------------------------------------------------------------------
