@@ -19,7 +19,12 @@ all: lib oracle
 
 lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr-ssim.a $(OUT)/librmgr-ssim-openmp.a $(BIN)/rmgr-ssim
 
-# Static flavour under the reference's archive name (CMakeLists.txt:205): the same three objects, linked into ONE relocatable
+# The objects both flavours share: kernels, the C ABI's host layer apart from ssim_context (the only one that reads
+# RMGR_SSIM_USE_DOUBLE: $(OBJ)/ssim_context.o / ssim_context_double.o), the drop-in layer.
+ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
+HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+
+# Static flavour under the reference's archive name (CMakeLists.txt:205): the same objects, linked into ONE relocatable
 # object whose only global symbols are the API (the shared libraries' export list has no counterpart for archives: the
 # internal ssim_hip:: interface between the ABI layer and the kernels would otherwise be visible to -- and collide with --
 # whatever else the program links; the reference's archive exposes its API only).  A program that links it also needs the
@@ -29,7 +34,7 @@ lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr
 # a group of the same signature (anything using std::make_shared, std::thread, ...) makes the final link discard the
 # archive's copy and leaves its now-local references dangling ("defined in discarded section").  Allocated into ordinary
 # sections here, the archive's copies are private to it and always kept.
-$(OUT)/librmgr-ssim.a: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_dropin.o
+$(OUT)/librmgr-ssim.a: $(ABI_OBJS) $(OBJ)/ssim_context.o
 	@mkdir -p $(OUT)
 	ld -r --force-group-allocation -o $(OBJ)/rmgr_ssim_api.o $^
 	objcopy --wildcard --keep-global-symbol='rmgr_ssim_*' --keep-global-symbol='_ZN4rmgr4ssim12compute_ssimE*' --keep-global-symbol='_ZN4rmgr4ssim11select_implE*' $(OBJ)/rmgr_ssim_api.o
@@ -62,7 +67,8 @@ $(OBJ)/msssim_kernels.o: $(SRC)/msssim_kernels.hip $(SRC)/msssim_kernels.h $(SRC
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJ)/ssim_hip_abi.o: $(SRC)/ssim_hip_abi.cpp $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+# The C ABI's host layer.
+$(OBJ)/ssim_context.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o: $(OBJ)/%.o: $(SRC)/%.cpp $(HOST_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
@@ -74,19 +80,19 @@ $(OBJ)/ssim_dropin.o: $(SRC)/ssim_dropin.cpp $(SRC)/ssim_internal.h include/rmgr
 # Only the API leaves the shared libraries: $(SRC)/exports.map (the reference's archive exposes only its API as well).
 EXPORTS := -Wl,--version-script=$(SRC)/exports.map
 
-$(OUT)/librmgr-ssim-hip.so: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_dropin.o $(OBJ)/ssim_openmp.o $(SRC)/exports.map
+$(OUT)/librmgr-ssim-hip.so: $(ABI_OBJS) $(OBJ)/ssim_context.o $(OBJ)/ssim_openmp.o $(SRC)/exports.map
 	@mkdir -p $(OUT)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(EXPORTS) -o $@ $(filter %.o,$^)
 
 # The reference's RMGR_SSIM_USE_DOUBLE build configuration (CMakeLists.txt:53, src/ssim_internal.h:26-37) as a second
-# flavour of the same library: identical kernels and drop-in layer, only the C ABI's default arithmetic differs (fp64
-# internals for every unchanged rmgr_ssim_compute_ssim call; BASELINE.json configs[4]).  `make DOUBLE=1` gives the same
-# thing under the main name.
-$(OBJ)/ssim_hip_abi_double.o: $(SRC)/ssim_hip_abi.cpp $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+# flavour of the same library: identical kernels, drop-in layer and host layer but for ssim_context, the only place the C ABI's
+# default arithmetic is decided (fp64 internals for every unchanged rmgr_ssim_compute_ssim call; BASELINE.json configs[4]).
+# `make DOUBLE=1` gives the same thing under the main name.
+$(OBJ)/ssim_context_double.o: $(SRC)/ssim_context.cpp $(HOST_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRMGR_SSIM_USE_DOUBLE=1 -x hip -c $< -o $@
 
-$(OUT)/librmgr-ssim-hip-double.so: $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim_hip_abi_double.o $(OBJ)/ssim_dropin.o $(OBJ)/ssim_openmp.o $(SRC)/exports.map
+$(OUT)/librmgr-ssim-hip-double.so: $(ABI_OBJS) $(OBJ)/ssim_context_double.o $(OBJ)/ssim_openmp.o $(SRC)/exports.map
 	@mkdir -p $(OUT)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(EXPORTS) -o $@ $(filter %.o,$^)
 

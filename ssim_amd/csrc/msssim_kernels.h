@@ -1,4 +1,4 @@
-// msssim_kernels.h -- internal interface between the C ABI (ssim_hip_abi.cpp) and the multi-scale SSIM kernels
+// msssim_kernels.h -- internal interface between the C ABI (ssim_hip_abi.cpp, MS-SSIM) and the multi-scale SSIM kernels
 // (msssim_kernels.hip).  Not installed.  The definition the kernels implement is written out in include/rmgr/ssim-hip.h
 // (rmgr_ssim_hip_compute_msssim_device).
 #ifndef SSIM_AMD_MSSSIM_KERNELS_H

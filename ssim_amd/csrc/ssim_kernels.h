@@ -1,4 +1,4 @@
-// ssim_kernels.h -- internal interface between the C ABI (ssim_hip_abi.cpp) and the gfx950
+// ssim_kernels.h -- internal interface between the C ABI (ssim_context.h and its .cpp files) and the gfx950
 // kernels (ssim_kernels.hip).  Not installed; nothing here is visible through include/rmgr/.
 #ifndef SSIM_AMD_KERNELS_H
 #define SSIM_AMD_KERNELS_H
