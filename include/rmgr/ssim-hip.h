@@ -20,6 +20,8 @@
  *   rmgr_ssim_hip_luminance_device             the conversion loop alone          src/ssim-cli.cpp:158-186
  *   rmgr_ssim_hip_set_mode             select_impl() / RMGR_SSIM_USE_DOUBLE   src/ssim.cpp:808-896, src/ssim_internal.h:26-37
  *   rmgr_ssim_hip_compute_msssim_device / _host   multi-scale SSIM: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssim16, rmgr_ssim_hip_compute_ssim16_device / _host   SSIM of 9- to 16-bit samples: no reference
+ *                                      counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -342,6 +344,61 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssim_device(rmgr_ssim_hip_Context* ctx, rmg
                                                  rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
 rmgr_int32_t rmgr_ssim_hip_compute_msssim_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_Params* params,
                                                rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+
+/*
+ * SSIM of `count` pairs of 8- to 16-bit images of one size (10- and 12-bit video, 16-bit PNG, medical and scientific images).  No
+ * reference counterpart: the definition is pinned down here, and tests/ssim16_model.py restates it in float64.
+ *
+ *   Samples  unsigned 16-bit, host byte order, LSB-aligned (rmgr_ssim_hip_uint16_t).  bitDepth, one value per call, 8 <= bitDepth <= 16;
+ *            L = 2^bitDepth - 1.  Samples are used as stored: values above L are not rejected.  Depth 8 lets 8-bit data in 16-bit
+ *            containers be cross-checked against the 8-bit engine.
+ *   Inputs   params[0 .. count-1]: width, height (the same for every pair), imgA / imgB with any step / stride in SAMPLES (not bytes),
+ *            negative ones included; ssimMap NULL (no map) or a float map with ssimStep / ssimStride in floats -- per pair.
+ *   Constants  C1 = float((0.01 L) * (0.01 L)), C2 = float((0.03 L) * (0.03 L)), products in double: at depth 8 the engine's 6.5025f
+ *            and 58.5225f.
+ *   Per pixel  the blurred moments mu_a, mu_b, sigma_a^2, sigma_b^2, sigma_ab of the engine's 11-tap Gaussian (sigma 1.5, normalised
+ *            over the 11 taps, fp32 taps), separable, with CLAMPED edges; variances and covariance as E[x y] - mu_x mu_y; then
+ *              ssim = (2 mu_a mu_b + C1)(2 sigma_ab + C2) / ((mu_a^2 + mu_b^2 + C1)(sigma_a^2 + sigma_b^2 + C2))
+ *            (SURVEY.md A.3).
+ *   Global   the mean of the per-pixel values: an fp64 sum divided by double(W) * double(H), a 64-bit product.  The 32-bit
+ *            width * height of rmgr_ssim_hip_finalize (the reference's quirk) does NOT apply here.
+ *   Arithmetic  fp32 with centred samples as in MODE_SEPARABLE, but the centre is an integer taken from a fixed position of the
+ *            image -- A's and B's sample at (min(x0 + 64, W - 1), (H - 1) / 2) for the 128 columns from x0 = 128 k on -- so the
+ *            subtraction is exact and the result does not depend on the batch.  The context's mode does not change this path.
+ *   Determinism  each image's sum runs over fixed 64-column cells in a fixed order: a pair gives the same bits (value and map)
+ *            alone or anywhere in a batch of any size, after any internal sub-batch split, through every entry point, on every
+ *            call, and as a view with negative step or stride compared with the same pixels uploaded contiguously.
+ *
+ * _enqueue_ssim16: device pointers; asynchronous on the context's stream; writes each pair's fp64 SUM of per-pixel values to
+ *            sumsDevice[i] (device memory), like rmgr_ssim_hip_enqueue_batch.  The mean is sum / (double(W) * double(H)).
+ * _compute_ssim16_device: device pointers; blocks; ssim: count floats in host memory.
+ * _compute_ssim16_host: host pointers (ctx NULL: a default context, as rmgr_ssim_hip_compute_ssim_host).  The images are staged to
+ *            the device and each map is copied back at its own step and stride; a batch runs in sub-batches that keep the device
+ *            scratch under about 1 GB -- results do not depend on the split.
+ * EINVAL: count == 0; a NULL params, ssim, image pointer or (enqueue) sumsDevice; a zero or differing width or height, or one above
+ *         0x7FFF0000; bitDepth
+ *         outside 8..16; an image pointer that is not 2-byte aligned; a NULL ctx for _device or _enqueue_ssim16 -- all checked
+ *         before any device is touched.  ENODEV: no device.
+ */
+typedef unsigned short rmgr_ssim_hip_uint16_t;
+typedef struct rmgr_ssim_hip_Img16 {
+    const rmgr_ssim_hip_uint16_t* topLeft;
+    ptrdiff_t step, stride;                     /* in samples */
+} rmgr_ssim_hip_Img16;
+typedef struct rmgr_ssim_hip_Params16 {
+    rmgr_uint32_t       width, height;
+    rmgr_ssim_hip_Img16 imgA, imgB;
+    float*              ssimMap;                /* NULL: no map */
+    ptrdiff_t           ssimStep, ssimStride;   /* in floats */
+} rmgr_ssim_hip_Params16;
+#define RMGR_SSIM_HIP_SSIM16_MIN_DEPTH 8
+#define RMGR_SSIM_HIP_SSIM16_MAX_DEPTH 16
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim16(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                          rmgr_uint32_t bitDepth, double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim16_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                 rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim16_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                               rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

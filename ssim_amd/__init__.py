@@ -9,4 +9,5 @@ from .api import (  # noqa: F401
     TuneResult, TunedEntry, compute_ssim, compute_ssim_batch, compute_ssim_batch_devices, compute_ssim_channels, compute_ssim_luminance, default_pool,
     MSSSIM_MAX_SCALES, MSSSIM_WANG_WEIGHTS, compute_msssim, compute_msssim_batch, default_pool_memory, device_count, finalize,
     get_plan, get_version, kernel_source_id, load_library, make_params, memory_info, trim_default_pool,
+    Img16, Params16, compute_ssim16, compute_ssim16_batch, make_params16,
 )

@@ -43,6 +43,18 @@ class Params(ctypes.Structure):
                 ("alloc", AllocFct), ("dealloc", DeallocFct)]
 
 
+class Img16(ctypes.Structure):
+    """rmgr_ssim_hip_Img16: step and stride count uint16 samples, not bytes."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
+
+
+class Params16(ctypes.Structure):
+    """rmgr_ssim_hip_Params16: ssimStep and ssimStride count floats; ssimMap None = no map."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("imgA", Img16), ("imgB", Img16),
+                ("ssimMap", ctypes.c_void_p), ("ssimStep", c_pd), ("ssimStride", c_pd)]
+
+
 class Plan(ctypes.Structure):
     _fields_ = [("structSize", ctypes.c_uint32), ("stripWidth", ctypes.c_uint32), ("stripRows", ctypes.c_uint32), ("stripsX", ctypes.c_uint32),
                 ("stripsY", ctypes.c_uint32), ("wavefronts", ctypes.c_uint32), ("waveSlots", ctypes.c_uint32), ("earlyRowSums", ctypes.c_uint32),
@@ -92,6 +104,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_trim", "rmgr_ssim_hip_trim_default_pool", "rmgr_ssim_hip_get_default_pool_memory", "rmgr_ssim_hip_get_memory_info",
     "rmgr_ssim_hip_tune", "rmgr_ssim_hip_clear_tuned", "rmgr_ssim_hip_get_tuned", "rmgr_ssim_hip_set_tuned", "rmgr_ssim_hip_get_profile_clock",
     "rmgr_ssim_hip_compute_msssim_device", "rmgr_ssim_hip_compute_msssim_host",
+    "rmgr_ssim_hip_enqueue_ssim16", "rmgr_ssim_hip_compute_ssim16_device", "rmgr_ssim_hip_compute_ssim16_host",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -165,6 +178,9 @@ def load_library(path=None):
         "rmgr_ssim_hip_get_memory_info": [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
         "rmgr_ssim_hip_compute_msssim_device": [vp, u32, PP, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssim_host": [vp, u32, PP, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_ssim16": [vp, u32, ctypes.POINTER(Params16), u32, vp],
+        "rmgr_ssim_hip_compute_ssim16_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssim16_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.POINTER(ctypes.c_float)],
     }
     for name, args in sig.items():
         if path is None and os.environ.get("RMGR_SSIM_LIB") and not hasattr(lib, name):
@@ -390,6 +406,62 @@ def compute_msssim_batch(pairs, scales=5, weights=None, per_scale=False, ctx=Non
     return _msssim_call("rmgr_ssim_hip_compute_msssim_host", ctx.handle if ctx is not None else None, params, n, scales, weights, per_scale)
 
 
+def make_params16(width, height, a_ptr, a_step, a_stride, b_ptr, b_step, b_stride, map_ptr=None, map_step=1, map_stride=None):
+    """rmgr_ssim_hip_Params16; steps and strides in samples (images) and floats (map)."""
+    p = Params16()
+    p.width, p.height = width, height
+    p.imgA = Img16(a_ptr, a_step, a_stride)
+    p.imgB = Img16(b_ptr, b_step, b_stride)
+    p.ssimMap = map_ptr
+    p.ssimStep = map_step
+    p.ssimStride = width if map_stride is None else map_stride
+    return p
+
+
+def _u16_view(x):
+    """A host-byte-order uint16 array whose strides are whole samples: x itself when it already is one (negative strides kept)."""
+    assert x.ndim == 2 and x.dtype.kind == "u" and x.dtype.itemsize == 2, "H x W uint16 expected"
+    if not x.dtype.isnative:
+        x = x.astype(np.uint16)
+    if x.strides[0] % 2 or x.strides[1] % 2 or x.ctypes.data % 2:
+        x = np.ascontiguousarray(x)
+    return x
+
+
+def _params16_of(a, b, map_ptr=None):
+    h, w = a.shape
+    return make_params16(w, h, a.ctypes.data, a.strides[1] // 2, a.strides[0] // 2, b.ctypes.data, b.strides[1] // 2, b.strides[0] // 2,
+                         map_ptr, 1, w)
+
+
+def compute_ssim16(a, b, bit_depth, want_map=False, ctx=None):
+    """SSIM of two H x W uint16 host arrays of `bit_depth` (8..16) bits (any strides numpy can express, negative ones included)
+    through rmgr_ssim_hip_compute_ssim16_host.  Returns (float32 value, H x W float32 map or None)."""
+    a, b = _u16_view(a), _u16_view(b)
+    assert a.shape == b.shape
+    h, w = a.shape
+    m = np.empty((h, w), np.float32) if want_map else None
+    params = (Params16 * 1)()
+    params[0] = _params16_of(a, b, m.ctypes.data if want_map else None)
+    out = (ctypes.c_float * 1)()
+    _check("rmgr_ssim_hip_compute_ssim16_host", load_library().rmgr_ssim_hip_compute_ssim16_host(
+        ctx.handle if ctx is not None else None, 1, params, bit_depth, out))
+    return np.float32(out[0]), m
+
+
+def compute_ssim16_batch(pairs, bit_depth, ctx=None):
+    """compute_ssim16() of many host pairs of one size in one call (no maps): a float32 array."""
+    pairs = [(_u16_view(a), _u16_view(b)) for a, b in pairs]
+    n = len(pairs)
+    params = (Params16 * max(n, 1))()
+    for i, (a, b) in enumerate(pairs):
+        params[i] = _params16_of(a, b)
+    out = (ctypes.c_float * max(n, 1))()
+    _check("rmgr_ssim_hip_compute_ssim16_host", load_library().rmgr_ssim_hip_compute_ssim16_host(
+        ctx.handle if ctx is not None else None, n, params, bit_depth, out))
+    return np.array(out[:n], np.float32)
+
+
 class DeviceBuffer(object):
     def __init__(self, ctx, nbytes):
         self.ctx, self.nbytes = ctx, nbytes
@@ -508,6 +580,16 @@ class Context(object):
         """MS-SSIM of `count` device-resident pairs (a Params array) through rmgr_ssim_hip_compute_msssim_device: a float32 array,
         and with per_scale=True also a (count, scales, 2) float64 array of [image][scale]{mcs, mssim}."""
         return _msssim_call("rmgr_ssim_hip_compute_msssim_device", self.handle, params_array, count, scales, weights, per_scale)
+
+    def ssim16_device(self, params_array, count, bit_depth):
+        """SSIM of `count` device-resident uint16 pairs (a Params16 array) through rmgr_ssim_hip_compute_ssim16_device: a float32 array."""
+        out = (ctypes.c_float * max(count, 1))()
+        _check("rmgr_ssim_hip_compute_ssim16_device", self.lib.rmgr_ssim_hip_compute_ssim16_device(self.handle, count, params_array, bit_depth, out))
+        return np.array(out[:count], np.float32)
+
+    def enqueue_ssim16(self, params_array, count, bit_depth, sums_dev_ptr):
+        """rmgr_ssim_hip_enqueue_ssim16: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        _check("rmgr_ssim_hip_enqueue_ssim16", self.lib.rmgr_ssim_hip_enqueue_ssim16(self.handle, count, params_array, bit_depth, sums_dev_ptr))
 
     def enqueue_batch(self, params_array, count, sums_dev_ptr):
         _check("rmgr_ssim_hip_enqueue_batch", self.lib.rmgr_ssim_hip_enqueue_batch(self.handle, count, params_array, sums_dev_ptr))

@@ -29,7 +29,12 @@ typedef std::vector<unsigned char> Bytes;
 struct Image {
     int width, height, channels;
     Bytes px;   // interleaved, top-down
-    Image() : width(0), height(0), channels(0) {}
+    // -d (full sample depth): a 16-bit PNG or a PNM with maxval > 255 is decoded into px16 at `depth` bits instead (px stays empty);
+    // widen() gives every other image its 8-bit samples there, at depth 8
+    bool deep;
+    int depth;
+    std::vector<unsigned short> px16;
+    Image() : width(0), height(0), channels(0), deep(false), depth(8) {}
 };
 
 // Decoders refuse absurd headers before allocating for them (stb_image, which the reference uses, caps
@@ -215,7 +220,9 @@ bool decode_png(const Bytes& f, Image& img, std::string& err)
     if (raw.size() < (rowBytes + 1) * h) { err = "short PNG data stream"; return false; }
     Bytes prev(rowBytes, 0), cur(rowBytes);
     img.width = int(w); img.height = int(h); img.channels = (ctype == 3) ? 3 : samples;
-    img.px.resize(size_t(w) * h * img.channels);
+    const bool full = img.deep && depth == 16;       // -d: all 16 bits of every sample
+    if (full) img.depth = 16, img.px16.resize(size_t(w) * h * img.channels);
+    else img.px.resize(size_t(w) * h * img.channels);
     for (unsigned y = 0; y < h; ++y) {
         const unsigned char* src = &raw[y * (rowBytes + 1)];
         const int ft = src[0];
@@ -226,6 +233,12 @@ bool decode_png(const Bytes& f, Image& img, std::string& err)
             else if (ft == 4) { const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c); pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c); }
             else if (ft != 0) { err = "bad PNG filter"; return false; }
             cur[i] = (unsigned char)(src[1 + i] + pred);
+        }
+        if (full) {
+            unsigned short* dst16 = &img.px16[size_t(y) * w * img.channels];
+            for (size_t i = 0; i < size_t(w) * samples; ++i) dst16[i] = (unsigned short)((cur[2 * i] << 8) | cur[2 * i + 1]);
+            prev.swap(cur);
+            continue;
         }
         unsigned char* dst = &img.px[size_t(y) * w * img.channels];
         for (unsigned x = 0; x < w; ++x) {
@@ -268,10 +281,23 @@ bool decode_pnm(const Bytes& f, Image& img, std::string& err)
     if (kind != 2 && kind != 3 && kind != 5 && kind != 6) { err = "unsupported PNM type"; return false; }
     size_t pos = 2;
     int w, h, maxv;
-    if (!pnm_token(f, pos, w) || !pnm_token(f, pos, h) || !pnm_token(f, pos, maxv) || maxv <= 0 || maxv > 255) { err = "bad PNM header (only maxval <= 255)"; return false; }
+    if (!pnm_token(f, pos, w) || !pnm_token(f, pos, h) || !pnm_token(f, pos, maxv) || maxv <= 0 || maxv > (img.deep ? 65535 : 255)) { err = "bad PNM header (only maxval <= 255)"; return false; }
     img.width = w; img.height = h; img.channels = (kind == 3 || kind == 6) ? 3 : 1;
-    if (!sane_size(size_t(w), size_t(h), size_t(img.channels))) { err = "bad PNM dimensions"; return false; }
+    if (!sane_size(size_t(w), size_t(h), size_t(img.channels) * (maxv > 255 ? 2 : 1))) { err = "bad PNM dimensions"; return false; }
     const size_t n = size_t(w) * h * img.channels;
+    if (maxv > 255) {           // -d only: samples as stored, big-endian in the binary forms; depth ceil(log2(maxval + 1))
+        img.depth = 9;
+        while ((1 << img.depth) - 1 < maxv) ++img.depth;
+        img.px16.resize(n);
+        if (kind >= 5) {
+            ++pos;
+            if (pos + 2 * n > f.size()) { err = "truncated PNM"; return false; }
+            for (size_t i = 0; i < n; ++i) img.px16[i] = (unsigned short)((f[pos + 2 * i] << 8) | f[pos + 2 * i + 1]);
+        } else {
+            for (size_t i = 0; i < n; ++i) { int v; if (!pnm_token(f, pos, v) || v > 65535) { err = "truncated PNM"; return false; } img.px16[i] = (unsigned short)v; }
+        }
+        return true;
+    }
     img.px.resize(n);
     if (kind >= 5) {
         ++pos;   // single whitespace after maxval
@@ -802,8 +828,10 @@ bool decode_jpeg(const Bytes& f, Image& img, std::string& err)
     return d.run(img);
 }
 
-bool load_image(const char* path, Image& img)
+// deep: -d, see Image
+bool load_image(const char* path, Image& img, bool deep = false)
 {
+    img.deep = deep;
     Bytes f;
     if (!read_file(path, f)) { fprintf(stderr, "Failed to open file \"%s\"\n", path); return false; }
     std::string err = "unknown image format (supported: PNG, JPEG, PNM, BMP, TGA)";
@@ -817,6 +845,14 @@ bool load_image(const char* path, Image& img)
     else if (ext && !strcasecmp(ext, ".tga")) ok = decode_tga(f, img, err);
     if (!ok) fprintf(stderr, "Failed to load image \"%s\":\n%s\n", path, err.c_str());
     return ok;
+}
+
+// An image decoded at depth 8 under -d: its samples as 16-bit ones.
+void widen(Image& img)
+{
+    if (!img.px16.empty()) return;
+    img.px16.assign(img.px.begin(), img.px.end());
+    img.depth = 8;
 }
 
 // ------------------------------------------------------------------------------ map output
@@ -920,7 +956,9 @@ void print_help(FILE* file)
                   "  -y  Compute SSIM on luminance\n"
                   "      For images with <= 2 channels, only channel 0's SSIM will be computed\n"
                   "      For images with >= 3 channels, first three channels are converted from RGB to Y\n"
-                  "  -m  Compute multi-scale SSIM (5 scales, Wang's weights) of every channel; no map\n\n");
+                  "  -m  Compute multi-scale SSIM (5 scales, Wang's weights) of every channel; no map\n"
+                  "  -d  Use every bit of the samples: a 16-bit PNG has depth 16, a PGM / PPM with maxval > 255 depth ceil(log2(maxval + 1));\n"
+                  "      other images have depth 8.  Both images must have the same depth.  May be combined with -0 .. -3, not with -y or -m\n\n");
 }
 
 int report(rmgr_int32_t rc)
@@ -941,6 +979,7 @@ struct Selection {
 
 struct Command {
     Selection   what;
+    bool        deep;        // -d
     const char* file[2];
     const char* mapFile;     // NULL: no map requested
 };
@@ -953,6 +992,13 @@ const struct { const char* flag; Selection sel; } kFlags[] = {
 // argv -> Command.  false: usage error (the message has been printed).
 bool parse_command(int argc, char* argv[], Command& cmd)
 {
+    // -d may come before or after the other option; it is taken out of the argument list first
+    std::vector<char*> args(argv, argv + argc);
+    cmd.deep = false;
+    for (size_t i = 1; i <= 2 && i < args.size() && args.size() >= 4; ++i)
+        if (!strcmp(args[i], "-d")) { cmd.deep = true; args.erase(args.begin() + ptrdiff_t(i)); break; }
+    argc = int(args.size());
+    argv = &args[0];
     if (argc < 3 || argc > 5) { print_help(stderr); return false; }
     cmd.what.kind = Selection::EVERY_CHANNEL;
     cmd.what.channel = 0;
@@ -971,6 +1017,10 @@ bool parse_command(int argc, char* argv[], Command& cmd)
         fprintf(stderr, "MS-SSIM has no per-pixel map: -m takes no map argument\n");
         return false;
     }
+    if (cmd.deep && (cmd.what.kind == Selection::LUMA || cmd.what.kind == Selection::MSSSIM)) {
+        fprintf(stderr, "-d (full sample depth) cannot be combined with %s\n", cmd.what.kind == Selection::LUMA ? "-y" : "-m");
+        return false;
+    }
     return true;
 }
 
@@ -980,6 +1030,8 @@ const struct { const char* ext; MapFormat fmt; bool anyChannels; const char* lab
     {".bmp", MAP_BMP, true, "BMP"}, {".png", MAP_PNG, true, "PNG"}, {".tga", MAP_TGA, true, "TGA"},
     {".pgm", MAP_PNM, false, "PNM"}, {".ppm", MAP_PNM, false, "PNM"}, {".pnm", MAP_PNM, false, "PNM"}, {".pfm", MAP_PFM, false, "PFM"},
 };
+
+int print_values(const std::vector<float>& value, bool single);
 
 // Runs the selected comparison and prints it in the reference's formats ("% 7.4f", "Channel %u: ...", "Average  : ...").
 int compare(const Image& a, const Image& b, Selection what, float* map, int mapChannels)
@@ -1022,10 +1074,39 @@ int compare(const Image& a, const Image& b, Selection what, float* map, int mapC
         break;
     }
     if (rc != 0) return report(rc);
-    if (!perChannel || (what.kind == Selection::MSSSIM && ch == 1)) {
+    return print_values(value, !perChannel || (what.kind == Selection::MSSSIM && ch == 1));
+}
+
+// -d: every channel, or the one chosen, through the 16-bit path (include/rmgr/ssim-hip.h rmgr_ssim_hip_compute_ssim16_host) at the
+// images' depth; the map as compare() stores it.
+int compare16(const Image& a, const Image& b, Selection what, float* map, int mapChannels)
+{
+    const rmgr_uint32_t w = rmgr_uint32_t(a.width), h = rmgr_uint32_t(a.height), ch = rmgr_uint32_t(a.channels);
+    const bool one = what.kind == Selection::ONE_CHANNEL;
+    const rmgr_uint32_t n = one ? 1u : ch;
+    std::vector<rmgr_ssim_hip_Params16> p(n);
+    for (rmgr_uint32_t i = 0; i < n; ++i) {
+        const rmgr_uint32_t c = one ? rmgr_uint32_t(what.channel) : i;
+        memset(&p[i], 0, sizeof(p[i]));
+        p[i].width = w; p[i].height = h;
+        p[i].imgA.topLeft = &a.px16[c]; p[i].imgA.step = ptrdiff_t(ch); p[i].imgA.stride = ptrdiff_t(w) * ch;
+        p[i].imgB.topLeft = &b.px16[c]; p[i].imgB.step = ptrdiff_t(ch); p[i].imgB.stride = ptrdiff_t(w) * ch;
+        if (map) { p[i].ssimMap = map + (one ? 0 : i); p[i].ssimStep = mapChannels; p[i].ssimStride = ptrdiff_t(w) * mapChannels; }
+    }
+    std::vector<float> value(n);
+    const rmgr_int32_t rc = rmgr_ssim_hip_compute_ssim16_host(NULL, n, &p[0], rmgr_uint32_t(a.depth), &value[0]);
+    if (rc != 0) return report(rc);
+    return print_values(value, one);
+}
+
+// "% 7.4f" for one value; otherwise "Channel %u: % 7.4f" per channel and their "Average  : % 7.4f" (the reference's formats).
+int print_values(const std::vector<float>& value, bool single)
+{
+    if (single) {
         printf("% 7.4f\n", value[0]);
         return EXIT_SUCCESS;
     }
+    const rmgr_uint32_t ch = rmgr_uint32_t(value.size());
     float total = 0.0f;
     for (rmgr_uint32_t c = 0; c < ch; ++c) {
         printf("Channel %u: % 7.4f\n", unsigned(c), value[c]);
@@ -1077,6 +1158,23 @@ int save_map(const char* path, const std::vector<float>& map, int w, int h, int 
     return EXIT_SUCCESS;
 }
 
+// test hook (not in the reference): decode an image at full depth (-d), dump its samples as little-endian uint16
+int decode16_to_file(const char* in, const char* out)
+{
+    Image img;
+    if (!load_image(in, img, true)) return EXIT_FAILURE;
+    widen(img);
+    Bytes le(img.px16.size() * 2);
+    for (size_t i = 0; i < img.px16.size(); ++i) { le[2 * i] = (unsigned char)(img.px16[i] & 0xFF); le[2 * i + 1] = (unsigned char)(img.px16[i] >> 8); }
+    FILE* f = fopen(out, "wb");
+    if (!f) return EXIT_FAILURE;
+    const bool ok = fwrite(&le[0], 1, le.size(), f) == le.size();
+    fclose(f);
+    if (!ok) return EXIT_FAILURE;
+    printf("%d %d %d %d\n", img.width, img.height, img.channels, img.depth);
+    return EXIT_SUCCESS;
+}
+
 // test hook (not in the reference): decode an image with the built-in codecs, dump the raw pixels
 int decode_to_file(const char* in, const char* out)
 {
@@ -1095,12 +1193,13 @@ static int run(int argc, char* argv[])
 {
     if (argc == 2 && (!strcmp(argv[1], "-h") || !strcmp(argv[1], "--help"))) { print_help(stdout); return EXIT_SUCCESS; }
     if (argc == 4 && !strcmp(argv[1], "--decode")) return decode_to_file(argv[2], argv[3]);
+    if (argc == 4 && !strcmp(argv[1], "--decode16")) return decode16_to_file(argv[2], argv[3]);
     Command cmd;
     if (!parse_command(argc, argv, cmd)) return EXIT_FAILURE;
 
     Image img[2];
     for (int i = 0; i < 2; ++i)
-        if (!load_image(cmd.file[i], img[i])) return EXIT_FAILURE;
+        if (!load_image(cmd.file[i], img[i], cmd.deep)) return EXIT_FAILURE;
     if (img[0].width != img[1].width || img[0].height != img[1].height) {
         fprintf(stderr, "Images do not have the same dimensions: %ux%u vs %ux%u\n", img[0].width, img[0].height, img[1].width, img[1].height);
         return EXIT_FAILURE;
@@ -1114,10 +1213,18 @@ static int run(int argc, char* argv[])
         return EXIT_FAILURE;
     }
 
+    if (cmd.deep) {
+        widen(img[0]); widen(img[1]);
+        if (img[0].depth != img[1].depth) {
+            fprintf(stderr, "Images do not have the same sample depth: %d vs %d bits\n", img[0].depth, img[1].depth);
+            return EXIT_FAILURE;
+        }
+    }
     std::vector<float> map;
     const int mapChannels = !cmd.mapFile ? 0 : (cmd.what.kind == Selection::EVERY_CHANNEL ? img[0].channels : 1);
     if (cmd.mapFile) map.resize(size_t(img[0].width) * img[0].height * mapChannels);
-    const int rc = compare(img[0], img[1], cmd.what, cmd.mapFile ? &map[0] : NULL, mapChannels);
+    const int rc = cmd.deep ? compare16(img[0], img[1], cmd.what, cmd.mapFile ? &map[0] : NULL, mapChannels)
+                            : compare(img[0], img[1], cmd.what, cmd.mapFile ? &map[0] : NULL, mapChannels);
     if (rc != EXIT_SUCCESS || !cmd.mapFile) return rc;
     return save_map(cmd.mapFile, map, img[0].width, img[0].height, mapChannels);
 }

@@ -6,6 +6,7 @@
 
 #include <rmgr/ssim-hip.h>
 #include "ssim_kernels.h"
+#include "ssim16_kernels.h"
 #include <rccl/rccl.h>      // types only: the library is dlopen()ed on first use, never linked
 
 #include <algorithm>
@@ -176,6 +177,14 @@ struct rmgr_ssim_hip_Context_ {
     PinnedBuffer<ssim_hip::PairDesc> ms_desc_pin;
     DeviceBuffer<double>   ms_sums;
     PinnedBuffer<double>   ms_sums_pin;
+    // SSIM of 16-bit samples (rmgr_ssim_hip_*_ssim16): descriptor table (its pinned mirror is rewritten only once the launch that
+    // read it has run: s16_desc_used), cell partials, per-pair sums written by the GPU
+    DeviceBuffer<ssim_hip::Pair16Desc> s16_desc;
+    PinnedBuffer<ssim_hip::Pair16Desc> s16_desc_pin;
+    LazyEvent              s16_desc_used;
+    bool                   s16_desc_pending = false;
+    DeviceBuffer<double>   s16_partials;
+    PinnedBuffer<double>   s16_sums_pin;
 
     // Every grow-only staging buffer above, once: what context_held counts and context_trim gives back.
     template <typename F> void for_each_staging(F f)
@@ -186,6 +195,7 @@ struct rmgr_ssim_hip_Context_ {
         for (int i = 0; i < 2; ++i) { f(slot_dev[i]); f(slot_pin[i]); f(h_map[i]); }
         f(batch_sums);
         f(ms_scratch); f(ms_desc); f(ms_desc_pin); f(ms_sums); f(ms_sums_pin);
+        f(s16_desc); f(s16_desc_pin); f(s16_partials); f(s16_sums_pin);
     }
 
     bool profiling = false;

@@ -916,6 +916,221 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssim_host(rmgr_ssim_hip_Context* c, rmgr_ui
     return msssim_batches(c, count, params, scales, weights ? weights : kWangWeights, msssim, scaleMeans, true);
 }
 
+// ---- SSIM of 9- to 16-bit samples (rmgr_ssim_hip_enqueue_ssim16, rmgr_ssim_hip_compute_ssim16_*) ----------------------------------------------
+// The definition is in include/rmgr/ssim-hip.h, the kernels in ssim16_kernels.hip.  Each pair's sum runs over fixed cells in a fixed order, so
+// neither the sub-batches (kS16ScratchCap of partials, staged images and maps per sub-batch) nor the launch a pair lands in change a bit.
+namespace {
+
+using ssim_hip::Pair16Desc;
+const uint64_t kS16ScratchCap = uint64_t(1) << 30;
+
+// Every check of the three entry points, before any device is touched.
+int ssim16_validate(rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params, rmgr_uint32_t bitDepth, const void* out)
+{
+    if (count == 0 || params == NULL || out == NULL) return EINVAL;
+    if (bitDepth < RMGR_SSIM_HIP_SSIM16_MIN_DEPTH || bitDepth > RMGR_SSIM_HIP_SSIM16_MAX_DEPTH) return EINVAL;
+    const uint32_t W = params[0].width, H = params[0].height;
+    if (W == 0 || H == 0 || W > ssim_hip::kS16MaxDim || H > ssim_hip::kS16MaxDim) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i) {
+        const rmgr_ssim_hip_Params16& p = params[i];
+        if (p.width != W || p.height != H) return EINVAL;
+        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
+        if (((uintptr_t)p.imgA.topLeft & 1u) || ((uintptr_t)p.imgB.topLeft & 1u)) return EINVAL;
+    }
+    if (ssim_hip::ssim16_max_count(W, H) == 0) return EINVAL;
+    return 0;
+}
+
+Pair16Desc make_desc16(const rmgr_ssim_hip_Params16& p)
+{
+    Pair16Desc d;
+    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride;
+    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride;
+    d.map = p.ssimMap;
+    d.map_step = p.ssimMap ? p.ssimStep : 0;
+    d.map_stride = p.ssimMap ? p.ssimStride : 0;
+    return d;
+}
+
+// Sample extent [lo, hi] (inclusive, relative to topLeft, in samples) of a width x height image.
+void extent16(const rmgr_ssim_hip_Img16& im, uint32_t w, uint32_t h, int64_t& lo, int64_t& hi)
+{
+    const int64_t dx = (int64_t)(w - 1) * (int64_t)im.step, dy = (int64_t)(h - 1) * (int64_t)im.stride;
+    lo = (dx < 0 ? dx : 0) + (dy < 0 ? dy : 0);
+    hi = (dx > 0 ? dx : 0) + (dy > 0 ? dy : 0);
+}
+
+uint64_t ssim16_partials_per_pair(uint32_t W, uint32_t H)
+{
+    const ssim_hip::Geometry16 g = ssim_hip::plan16(W, H, 1, 0);
+    return g.cells_per_image() * sizeof(double);
+}
+
+// Enqueues n pairs (descriptors in host memory, images on the device) on the context's stream: descriptor upload, strip kernel,
+// reduction into sums[0 .. n-1] (device or pinned host memory).  n <= ssim16_max_count and its partials within the cap.
+int ssim16_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const Pair16Desc* d, uint32_t W, uint32_t H, uint32_t depth, double* sums)
+{
+    int rc;
+    if (c->s16_desc_pending) {               // the pinned mirror is the source of the last queued upload
+        HIP_TRY(hipEventSynchronize(c->s16_desc_used));
+        c->s16_desc_pending = false;
+    }
+    HIP_TRY(c->s16_desc_used.ensure());
+    const ssim_hip::Geometry16 geo = ssim_hip::plan16(W, H, n, c->cu_count);
+    if ((rc = c->s16_desc_pin.grow(n))) return rc;
+    if ((rc = c->s16_desc.grow(n))) return rc;
+    if ((rc = c->s16_partials.grow((size_t)(geo.cells_per_image() * n)))) return rc;
+    bool map = false, unit = (W % 2) == 0, wide = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        map = map || d[i].map != NULL;
+        unit = unit && (d[i].map == NULL || d[i].map_step == 1);
+        wide = wide || !ssim_hip::fits16_narrow(d[i]);
+    }
+    memcpy(c->s16_desc_pin.get(), d, n * sizeof(Pair16Desc));
+    HIP_TRY(hipMemcpyAsync(c->s16_desc, c->s16_desc_pin, n * sizeof(Pair16Desc), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ssim_hip::launch_ssim16(geo, c->s16_desc, map, unit, wide, depth, c->xcd_count, c->s16_partials, sums, c->stream));
+    HIP_TRY(hipEventRecord(c->s16_desc_used, c->stream));
+    c->s16_desc_pending = true;
+    return 0;
+}
+
+// Pairs of params[i0 ..] that one sub-batch takes: at least one; within the launch limit and, with `stage_bytes` per pair of staged
+// images and maps (host pointers), kS16ScratchCap of device scratch.
+uint32_t ssim16_take(const rmgr_ssim_hip_Params16* params, uint32_t i0, uint32_t count, bool stage, uint64_t& staged)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const uint64_t part = ssim16_partials_per_pair(W, H);
+    const uint32_t nmax = ssim_hip::ssim16_max_count(W, H);
+    uint32_t n = 0;
+    staged = 0;
+    while (i0 + n < count && n < nmax) {
+        uint64_t bytes = 0;
+        if (stage) {
+            const rmgr_ssim_hip_Params16& p = params[i0 + n];
+            int64_t lo, hi;
+            extent16(p.imgA, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 2 + 63) & ~uint64_t(63);
+            extent16(p.imgB, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 2 + 63) & ~uint64_t(63);
+            if (p.ssimMap) bytes += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
+        }
+        if (n > 0 && part * (n + 1) + staged + bytes > kS16ScratchCap) break;
+        staged += bytes;
+        ++n;
+    }
+    return n;
+}
+
+// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the images are copied
+// (each image's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own step and stride.
+int ssim16_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t depth, float* ssim, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const double px = (double)W * (double)H;
+    int rc;
+    if ((rc = c->s16_sums_pin.grow(count))) return rc;
+    try {
+        std::vector<Pair16Desc> d;
+        std::vector<float> back;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = ssim16_take(params, i0, count, stage, staged);
+            d.resize(n);
+            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
+            uint64_t off = 0;
+            std::vector<uint64_t> map_off(n, 0);
+            for (uint32_t i = 0; i < n; ++i) {
+                const rmgr_ssim_hip_Params16& p = params[i0 + i];
+                d[i] = make_desc16(p);
+                if (!stage) continue;
+                for (int k = 0; k < 2; ++k) {
+                    const rmgr_ssim_hip_Img16& im = k ? p.imgB : p.imgA;
+                    int64_t lo, hi;
+                    extent16(im, W, H, lo, hi);
+                    const size_t bytes = (size_t)(hi - lo + 1) * 2;
+                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
+                    (k ? d[i].b : d[i].a) = reinterpret_cast<const uint16_t*>(c->stage_a + off) - lo;
+                    off += (bytes + 63) & ~uint64_t(63);
+                }
+                if (p.ssimMap) {
+                    map_off[i] = off;
+                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
+                    d[i].map_step = 1; d[i].map_stride = W;
+                    off += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
+                }
+            }
+            if ((rc = ssim16_enqueue(c, n, &d[0], W, H, depth, c->s16_sums_pin + i0))) return rc;
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (uint32_t i = 0; i < n && stage; ++i) {
+                const rmgr_ssim_hip_Params16& p = params[i0 + i];
+                if (!p.ssimMap) continue;
+                const float* src = reinterpret_cast<const float*>(c->stage_a + map_off[i]);
+                if (p.ssimStep == 1 && p.ssimStride == (ptrdiff_t)W) {
+                    HIP_TRY(hipMemcpy(p.ssimMap, src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+                    continue;
+                }
+                back.resize((size_t)W * H);
+                HIP_TRY(hipMemcpy(&back[0], src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+                for (uint32_t y = 0; y < H; ++y) {
+                    float* row = p.ssimMap + (ptrdiff_t)y * p.ssimStride;
+                    const float* s = &back[(size_t)y * W];
+                    for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = s[x];
+                }
+            }
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->s16_sums_pin[i] / px);
+    return 0;
+}
+
+} // namespace
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim16(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                          rmgr_uint32_t bitDepth, double* sumsDevice) RMGR_NOEXCEPT
+{
+    int rc = ssim16_validate(count, params, bitDepth, sumsDevice);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    try {
+        std::vector<Pair16Desc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = ssim16_take(params, i0, count, false, staged);
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) d[i] = make_desc16(params[i0 + i]);
+            if ((rc = ssim16_enqueue(c, n, &d[0], params[0].width, params[0].height, bitDepth, sumsDevice + i0))) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim16_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                 rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT
+{
+    int rc = ssim16_validate(count, params, bitDepth, ssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return ssim16_blocking(c, count, params, bitDepth, ssim, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim16_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                               rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT
+{
+    int rc = ssim16_validate(count, params, bitDepth, ssim);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    c = lease.c;
+    USE_DEVICE(c);
+    return ssim16_blocking(c, count, params, bitDepth, ssim, true);
+}
+
 // ---- one process, several devices ------------------------------------------------------------------------------------
 // The reference parallelises one call over a caller-supplied thread pool (tile jobs, src/ssim.cpp:1048-1088; the OpenMP
 // adapter src/ssim-openmp.c:26-47).  The batch-level counterpart here: a contiguous block of the pairs per device, one
