@@ -21,8 +21,8 @@ lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr
 
 # The objects both flavours share: kernels, the C ABI's host layer apart from ssim_context (the only one that reads
 # RMGR_SSIM_USE_DOUBLE: $(OBJ)/ssim_context.o / ssim_context_double.o), the drop-in layer.
-ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
-HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
+HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
 
 # Static flavour under the reference's archive name (CMakeLists.txt:205): the same objects, linked into ONE relocatable
 # object whose only global symbols are the API (the shared libraries' export list has no counterpart for archives: the
@@ -69,6 +69,11 @@ $(OBJ)/msssim_kernels.o: $(SRC)/msssim_kernels.hip $(SRC)/msssim_kernels.h $(SRC
 
 # SSIM of 9- to 16-bit samples (rmgr_ssim_hip_*_ssim16): its own file for the same reason.
 $(OBJ)/ssim16_kernels.o: $(SRC)/ssim16_kernels.hip $(SRC)/ssim16_kernels.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_ssimf*): its own file for the same reason.
+$(OBJ)/ssimf_kernels.o: $(SRC)/ssimf_kernels.hip $(SRC)/ssimf_kernels.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -22,6 +22,8 @@
  *   rmgr_ssim_hip_compute_msssim_device / _host   multi-scale SSIM: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim16, rmgr_ssim_hip_compute_ssim16_device / _host   SSIM of 9- to 16-bit samples: no reference
  *                                      counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssimf, rmgr_ssim_hip_compute_ssimf_device / _host, rmgr_ssim_hip_enqueue_ssimf_grad   SSIM of float32
+ *                                      samples and its gradient: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -399,6 +401,81 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssim16_device(rmgr_ssim_hip_Context* ctx, rmg
                                                  rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT;
 rmgr_int32_t rmgr_ssim_hip_compute_ssim16_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
                                                rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT;
+
+/*
+ * SSIM of `count` pairs of float32 images of one size, and its gradient (HDR and linear-light frames, normalised tensors, the
+ * output of a model; SSIM as a training loss).  No reference counterpart: the definition is pinned down here, and
+ * tests/ssimf_model.py restates it in float64, the gradient included.
+ *
+ *   Samples  float32 planes, used as stored.  Negative values and values above dataRange are not rejected; NaN and Inf propagate.
+ *   Data range  dataRange, one float per call, finite and > 0 (R): C1 = float((0.01 R) * (0.01 R)), C2 = float((0.03 R) * (0.03 R)),
+ *            products in double.
+ *   Inputs   params[0 .. count-1]: width, height (the same for every pair), imgA / imgB with any step / stride in FLOATS (not bytes),
+ *            negative ones included; ssimMap NULL (no map) or a float map with ssimStep / ssimStride in floats -- per pair.
+ *   Window   the engine's 11-tap Gaussian (sigma 1.5, normalised over the 11 taps, fp32 taps), separable, with CLAMPED edges, same-size
+ *            output: the linear operator G.
+ *   Per pixel  mu_a = G a, mu_b = G b, s_aa = G(a^2) - mu_a^2, s_bb = G(b^2) - mu_b^2, s_ab = G(a b) - mu_a mu_b;
+ *              A1 = 2 mu_a mu_b + C1, A2 = 2 s_ab + C2, B1 = mu_a^2 + mu_b^2 + C1, B2 = s_aa + s_bb + C2;  ssim = A1 A2 / (B1 B2).
+ *   Global   S_i: the fp64 sum of the per-pixel values divided by double(W) * double(H), a 64-bit product as for ssim16.
+ *   Gradient  given gOut[i] = dLoss/dS_i, the exact derivative of the above, clamped edges included.  With k = gOut[i] / (double(W) *
+ *            double(H)), d_ab = 2 A1 / (B1 B2), d_aa = -ssim / B2 and
+ *              d_mu = 2 mu_b A2 / (B1 B2) - 2 mu_a ssim / B1 - 2 mu_a d_aa - mu_b d_ab:
+ *              dLoss/da = Gt(k d_mu) + 2 a Gt(k d_aa) + b Gt(k d_ab),    dLoss/db: the same with a and b exchanged.
+ *            Gt is the ADJOINT of the clamped window, not the window: (Gt v)(q) is the sum of w_t v(p) over every (p, t) with
+ *            clamp(p + t) = q.  It is separable; in the interior it equals G; the first and last row and column also collect the
+ *            taps the forward pass clamped onto them: on each axis the plain blur of v zero-extended by 5, with the 5 results
+ *            beyond each end added onto the end pixel.  The rule covers axes of 5 pixels and fewer, down to 1 x 1.
+ *   Arithmetic  fp32 with centred samples as for ssim16: the centre of the 128 columns from x0 = 128 k on is A's and B's sample at
+ *            (min(x0 + 64, W - 1), (H - 1) / 2) when its magnitude is at most dataRange, else 0.  Unlike an integer centre the
+ *            subtraction rounds (to half an ulp of the difference).  The gradient kernel differentiates in the centred variables,
+ *            which is the formula above with its cancelling terms removed before rounding.  The position is fixed by the image, so
+ *            results do not depend on the batch.  The context's mode does not change this path.
+ *   Determinism  each image's sum runs over fixed 64-column cells in a fixed order, and every gradient pixel is written by exactly one
+ *            work-item in a fixed summation order (32 x 32 tiles at absolute positions, no floating-point atomics): a pair gives the
+ *            same bits -- value, map, gradient -- alone or anywhere in a batch of any size, after any internal sub-batch split,
+ *            through every entry point, on every call, with both gradients or one, and as a view with negative step or stride
+ *            compared with the same pixels stored contiguously.
+ *
+ * _enqueue_ssimf: device pointers; asynchronous on the context's stream; writes each pair's fp64 SUM of per-pixel values to
+ *            sumsDevice[i] (device memory).  The mean is sum / (double(W) * double(H)).
+ * _compute_ssimf_device: device pointers; blocks; ssim: count floats in host memory.
+ * _compute_ssimf_host: host pointers (ctx NULL: a default context, as rmgr_ssim_hip_compute_ssim_host).  The images are staged to
+ *            the device and each map is copied back at its own step and stride; a batch runs in sub-batches that keep the device
+ *            scratch under about 1 GB -- results do not depend on the split.
+ * _enqueue_ssimf_grad: everything device-resident, asynchronous on the context's stream, no host synchronisation.  gradOutDevice:
+ *            count floats in DEVICE memory (dLoss/dS_i).  gradA / gradB: arrays of count rmgr_ssim_hip_GradF (host memory) that
+ *            describe where dLoss/dA and dLoss/dB of each pair go (device planes, step / stride in floats, negatives included); either
+ *            array may be NULL (that gradient is not computed), not both.  Gradients are WRITTEN, not accumulated.  A gradient
+ *            plane must not overlap an input plane or another gradient plane: this is not checked.  params[i].ssimMap is ignored.
+ *            One fused launch recomputes the statistics: no scratch memory beyond the descriptors.
+ * EINVAL: count == 0; a NULL params, ssim, image pointer, sumsDevice, gradOutDevice or gradient plane; both gradient arrays NULL; a
+ *         zero or differing width or height, or one above 0x7FFF0000; a dataRange that is not finite or not > 0; an image or gradient
+ *         pointer that is not 4-byte aligned; a NULL ctx for anything but _host -- all checked before any device is touched.
+ *         ENODEV: no device.
+ */
+typedef struct rmgr_ssim_hip_ImgF {
+    const float* topLeft;
+    ptrdiff_t step, stride;                     /* in floats */
+} rmgr_ssim_hip_ImgF;
+typedef struct rmgr_ssim_hip_ParamsF {
+    rmgr_uint32_t      width, height;
+    rmgr_ssim_hip_ImgF imgA, imgB;
+    float*             ssimMap;                 /* NULL: no map */
+    ptrdiff_t          ssimStep, ssimStride;    /* in floats */
+} rmgr_ssim_hip_ParamsF;
+typedef struct rmgr_ssim_hip_GradF {
+    float*    topLeft;
+    ptrdiff_t step, stride;                     /* in floats */
+} rmgr_ssim_hip_GradF;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                         float dataRange, double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                float dataRange, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                              float dataRange, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                              float dataRange, const float* gradOutDevice,
+                                              const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

@@ -10,4 +10,5 @@ from .api import (  # noqa: F401
     MSSSIM_MAX_SCALES, MSSSIM_WANG_WEIGHTS, compute_msssim, compute_msssim_batch, default_pool_memory, device_count, finalize,
     get_plan, get_version, kernel_source_id, load_library, make_params, memory_info, trim_default_pool,
     Img16, Params16, compute_ssim16, compute_ssim16_batch, make_params16,
+    ImgF, ParamsF, GradF, compute_ssimf, compute_ssimf_batch, make_params_f,
 )

@@ -55,6 +55,23 @@ class Params16(ctypes.Structure):
                 ("ssimMap", ctypes.c_void_p), ("ssimStep", c_pd), ("ssimStride", c_pd)]
 
 
+class ImgF(ctypes.Structure):
+    """rmgr_ssim_hip_ImgF: step and stride count floats, not bytes."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
+
+
+class ParamsF(ctypes.Structure):
+    """rmgr_ssim_hip_ParamsF: ssimStep and ssimStride count floats; ssimMap None = no map."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("imgA", ImgF), ("imgB", ImgF),
+                ("ssimMap", ctypes.c_void_p), ("ssimStep", c_pd), ("ssimStride", c_pd)]
+
+
+class GradF(ctypes.Structure):
+    """rmgr_ssim_hip_GradF: one gradient plane in device memory; step and stride count floats."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
+
+
 class Plan(ctypes.Structure):
     _fields_ = [("structSize", ctypes.c_uint32), ("stripWidth", ctypes.c_uint32), ("stripRows", ctypes.c_uint32), ("stripsX", ctypes.c_uint32),
                 ("stripsY", ctypes.c_uint32), ("wavefronts", ctypes.c_uint32), ("waveSlots", ctypes.c_uint32), ("earlyRowSums", ctypes.c_uint32),
@@ -105,6 +122,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_tune", "rmgr_ssim_hip_clear_tuned", "rmgr_ssim_hip_get_tuned", "rmgr_ssim_hip_set_tuned", "rmgr_ssim_hip_get_profile_clock",
     "rmgr_ssim_hip_compute_msssim_device", "rmgr_ssim_hip_compute_msssim_host",
     "rmgr_ssim_hip_enqueue_ssim16", "rmgr_ssim_hip_compute_ssim16_device", "rmgr_ssim_hip_compute_ssim16_host",
+    "rmgr_ssim_hip_enqueue_ssimf", "rmgr_ssim_hip_compute_ssimf_device", "rmgr_ssim_hip_compute_ssimf_host", "rmgr_ssim_hip_enqueue_ssimf_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -181,6 +199,10 @@ def load_library(path=None):
         "rmgr_ssim_hip_enqueue_ssim16": [vp, u32, ctypes.POINTER(Params16), u32, vp],
         "rmgr_ssim_hip_compute_ssim16_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_compute_ssim16_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssimf": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, vp],
+        "rmgr_ssim_hip_compute_ssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssimf_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
     }
     for name, args in sig.items():
         if path is None and os.environ.get("RMGR_SSIM_LIB") and not hasattr(lib, name):
@@ -462,6 +484,62 @@ def compute_ssim16_batch(pairs, bit_depth, ctx=None):
     return np.array(out[:n], np.float32)
 
 
+def make_params_f(width, height, a_ptr, a_step, a_stride, b_ptr, b_step, b_stride, map_ptr=None, map_step=1, map_stride=None):
+    """rmgr_ssim_hip_ParamsF; steps and strides in floats (images and map)."""
+    p = ParamsF()
+    p.width, p.height = width, height
+    p.imgA = ImgF(a_ptr, a_step, a_stride)
+    p.imgB = ImgF(b_ptr, b_step, b_stride)
+    p.ssimMap = map_ptr
+    p.ssimStep = map_step
+    p.ssimStride = width if map_stride is None else map_stride
+    return p
+
+
+def _f32_view(x):
+    """A native float32 array whose strides are whole floats: x itself when it already is one (negative strides kept)."""
+    assert x.ndim == 2 and x.dtype.kind == "f" and x.dtype.itemsize == 4, "H x W float32 expected"
+    if not x.dtype.isnative:
+        x = x.astype(np.float32)
+    if x.strides[0] % 4 or x.strides[1] % 4 or x.ctypes.data % 4:
+        x = np.ascontiguousarray(x)
+    return x
+
+
+def _params_f_of(a, b, map_ptr=None):
+    h, w = a.shape
+    return make_params_f(w, h, a.ctypes.data, a.strides[1] // 4, a.strides[0] // 4, b.ctypes.data, b.strides[1] // 4, b.strides[0] // 4,
+                         map_ptr, 1, w)
+
+
+def compute_ssimf(a, b, data_range, want_map=False, ctx=None):
+    """SSIM of two H x W float32 host arrays at `data_range` (any strides numpy can express, negative ones included) through
+    rmgr_ssim_hip_compute_ssimf_host.  Returns (float32 value, H x W float32 map or None)."""
+    a, b = _f32_view(a), _f32_view(b)
+    assert a.shape == b.shape
+    h, w = a.shape
+    m = np.empty((h, w), np.float32) if want_map else None
+    params = (ParamsF * 1)()
+    params[0] = _params_f_of(a, b, m.ctypes.data if want_map else None)
+    out = (ctypes.c_float * 1)()
+    _check("rmgr_ssim_hip_compute_ssimf_host", load_library().rmgr_ssim_hip_compute_ssimf_host(
+        ctx.handle if ctx is not None else None, 1, params, data_range, out))
+    return np.float32(out[0]), m
+
+
+def compute_ssimf_batch(pairs, data_range, ctx=None):
+    """compute_ssimf() of many host pairs of one size in one call (no maps): a float32 array."""
+    pairs = [(_f32_view(a), _f32_view(b)) for a, b in pairs]
+    n = len(pairs)
+    params = (ParamsF * max(n, 1))()
+    for i, (a, b) in enumerate(pairs):
+        params[i] = _params_f_of(a, b)
+    out = (ctypes.c_float * max(n, 1))()
+    _check("rmgr_ssim_hip_compute_ssimf_host", load_library().rmgr_ssim_hip_compute_ssimf_host(
+        ctx.handle if ctx is not None else None, n, params, data_range, out))
+    return np.array(out[:n], np.float32)
+
+
 class DeviceBuffer(object):
     def __init__(self, ctx, nbytes):
         self.ctx, self.nbytes = ctx, nbytes
@@ -590,6 +668,21 @@ class Context(object):
     def enqueue_ssim16(self, params_array, count, bit_depth, sums_dev_ptr):
         """rmgr_ssim_hip_enqueue_ssim16: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
         _check("rmgr_ssim_hip_enqueue_ssim16", self.lib.rmgr_ssim_hip_enqueue_ssim16(self.handle, count, params_array, bit_depth, sums_dev_ptr))
+
+    def ssimf_device(self, params_array, count, data_range):
+        """SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_ssimf_device: a float32 array."""
+        out = (ctypes.c_float * max(count, 1))()
+        _check("rmgr_ssim_hip_compute_ssimf_device", self.lib.rmgr_ssim_hip_compute_ssimf_device(self.handle, count, params_array, data_range, out))
+        return np.array(out[:count], np.float32)
+
+    def enqueue_ssimf(self, params_array, count, data_range, sums_dev_ptr):
+        """rmgr_ssim_hip_enqueue_ssimf: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        _check("rmgr_ssim_hip_enqueue_ssimf", self.lib.rmgr_ssim_hip_enqueue_ssimf(self.handle, count, params_array, data_range, sums_dev_ptr))
+
+    def enqueue_ssimf_grad(self, params_array, count, data_range, grad_out_dev_ptr, grad_a=None, grad_b=None):
+        """rmgr_ssim_hip_enqueue_ssimf_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs into the planes the GradF arrays
+        grad_a / grad_b describe (None: not wanted), from `count` floats dLoss/dS_i in device memory; asynchronous, written not accumulated."""
+        _check("rmgr_ssim_hip_enqueue_ssimf_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_grad(self.handle, count, params_array, data_range, grad_out_dev_ptr, grad_a, grad_b))
 
     def enqueue_batch(self, params_array, count, sums_dev_ptr):
         _check("rmgr_ssim_hip_enqueue_batch", self.lib.rmgr_ssim_hip_enqueue_batch(self.handle, count, params_array, sums_dev_ptr))

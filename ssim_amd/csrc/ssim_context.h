@@ -7,6 +7,7 @@
 #include <rmgr/ssim-hip.h>
 #include "ssim_kernels.h"
 #include "ssim16_kernels.h"
+#include "ssimf_kernels.h"
 #include <rccl/rccl.h>      // types only: the library is dlopen()ed on first use, never linked
 
 #include <algorithm>
@@ -185,6 +186,19 @@ struct rmgr_ssim_hip_Context_ {
     bool                   s16_desc_pending = false;
     DeviceBuffer<double>   s16_partials;
     PinnedBuffer<double>   s16_sums_pin;
+    // SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_ssimf*): a ring of descriptor tables (pair descriptors, then the
+    // gradient descriptors of a gradient launch), so that an enqueue waits at most for the launch kSfSlots enqueues ago -- a training
+    // step's forward and backward never wait for each other --, cell partials, per-pair sums written by the GPU
+    enum { kSfSlots = 8 };
+    struct SfSlot {
+        DeviceBuffer<uint8_t> dev;
+        PinnedBuffer<uint8_t> pin;          // rewritten only once the launch that read its upload has run: `used`
+        LazyEvent used;
+        bool      pending = false;
+    } sf_slots[kSfSlots];
+    int                    sf_next = 0;
+    DeviceBuffer<double>   sf_partials;
+    PinnedBuffer<double>   sf_sums_pin;
 
     // Every grow-only staging buffer above, once: what context_held counts and context_trim gives back.
     template <typename F> void for_each_staging(F f)
@@ -196,6 +210,8 @@ struct rmgr_ssim_hip_Context_ {
         f(batch_sums);
         f(ms_scratch); f(ms_desc); f(ms_desc_pin); f(ms_sums); f(ms_sums_pin);
         f(s16_desc); f(s16_desc_pin); f(s16_partials); f(s16_sums_pin);
+        for (SfSlot& s : sf_slots) { f(s.dev); f(s.pin); }
+        f(sf_partials); f(sf_sums_pin);
     }
 
     bool profiling = false;

@@ -1131,6 +1131,277 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssim16_host(rmgr_ssim_hip_Context* c, rmgr_ui
     return ssim16_blocking(c, count, params, bitDepth, ssim, true);
 }
 
+// ---- SSIM of float32 samples and its gradient (rmgr_ssim_hip_enqueue_ssimf, _compute_ssimf_*, _enqueue_ssimf_grad) ---------------------------
+// The definition is in include/rmgr/ssim-hip.h, the kernels in ssimf_kernels.hip.  The forward path is the ssim16 one with float samples; the
+// gradient is one fused launch without scratch.  Sums run over fixed cells and gradient pixels over fixed tiles, so neither the sub-batches
+// nor the launch a pair lands in change a bit.
+namespace {
+
+using ssim_hip::PairFDesc;
+using ssim_hip::GradFDesc;
+const uint64_t kSFScratchCap = uint64_t(1) << 30;
+
+// Every check the entry points share, before any device is touched.
+int ssimf_validate(rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const void* out)
+{
+    if (count == 0 || params == NULL || out == NULL) return EINVAL;
+    if (!(dataRange > 0.0f) || !std::isfinite(dataRange)) return EINVAL;
+    const uint32_t W = params[0].width, H = params[0].height;
+    if (W == 0 || H == 0 || W > ssim_hip::kSFMaxDim || H > ssim_hip::kSFMaxDim) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i) {
+        const rmgr_ssim_hip_ParamsF& p = params[i];
+        if (p.width != W || p.height != H) return EINVAL;
+        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
+        if (((uintptr_t)p.imgA.topLeft & 3u) || ((uintptr_t)p.imgB.topLeft & 3u)) return EINVAL;
+    }
+    if (ssim_hip::ssimf_max_count(W, H) == 0) return EINVAL;
+    return 0;
+}
+
+PairFDesc make_descf(const rmgr_ssim_hip_ParamsF& p, bool with_map)
+{
+    PairFDesc d;
+    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride;
+    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride;
+    const bool m = with_map && p.ssimMap;
+    d.map = m ? p.ssimMap : NULL;
+    d.map_step = m ? p.ssimStep : 0;
+    d.map_stride = m ? p.ssimStride : 0;
+    return d;
+}
+
+// Sample extent [lo, hi] (inclusive, relative to topLeft, in floats) of a width x height image.
+void extentf(const rmgr_ssim_hip_ImgF& im, uint32_t w, uint32_t h, int64_t& lo, int64_t& hi)
+{
+    const int64_t dx = (int64_t)(w - 1) * (int64_t)im.step, dy = (int64_t)(h - 1) * (int64_t)im.stride;
+    lo = (dx < 0 ? dx : 0) + (dy < 0 ? dy : 0);
+    hi = (dx > 0 ? dx : 0) + (dy > 0 ? dy : 0);
+}
+
+uint64_t ssimf_partials_per_pair(uint32_t W, uint32_t H)
+{
+    const ssim_hip::GeometryF g = ssim_hip::planf(W, H, 1, 0);
+    return g.cells_per_image() * sizeof(double);
+}
+
+// The next descriptor table of the ring with room for `bytes`: waits, at most, for the launch that read it kSfSlots enqueues ago.
+int ssimf_slot(rmgr_ssim_hip_Context* c, size_t bytes, rmgr_ssim_hip_Context_::SfSlot*& out)
+{
+    rmgr_ssim_hip_Context_::SfSlot& s = c->sf_slots[c->sf_next];
+    c->sf_next = (c->sf_next + 1) % rmgr_ssim_hip_Context_::kSfSlots;
+    if (s.pending) {
+        HIP_TRY(hipEventSynchronize(s.used));
+        s.pending = false;
+    }
+    HIP_TRY(s.used.ensure());
+    int rc;
+    if ((rc = s.pin.grow(bytes))) return rc;
+    if ((rc = s.dev.grow(bytes))) return rc;
+    out = &s;
+    return 0;
+}
+
+// Enqueues n pairs (descriptors in host memory, images on the device) on the context's stream: descriptor upload, strip kernel,
+// reduction into sums[0 .. n-1] (device or pinned host memory).  n <= ssimf_max_count and its partials within the cap.
+int ssimf_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const PairFDesc* d, uint32_t W, uint32_t H, float range, double* sums)
+{
+    int rc;
+    rmgr_ssim_hip_Context_::SfSlot* s;
+    if ((rc = ssimf_slot(c, n * sizeof(PairFDesc), s))) return rc;
+    const ssim_hip::GeometryF geo = ssim_hip::planf(W, H, n, c->cu_count);
+    if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_image() * n)))) return rc;
+    bool map = false, unit = (W % 2) == 0, wide = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        map = map || d[i].map != NULL;
+        unit = unit && (d[i].map == NULL || d[i].map_step == 1);
+        wide = wide || !ssim_hip::fitsf_narrow(d[i]);
+    }
+    memcpy(s->pin.get(), d, n * sizeof(PairFDesc));
+    HIP_TRY(hipMemcpyAsync(s->dev, s->pin, n * sizeof(PairFDesc), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ssim_hip::launch_ssimf(geo, reinterpret_cast<const PairFDesc*>(s->dev.get()), map, unit, wide, range, c->xcd_count, c->sf_partials, sums, c->stream));
+    HIP_TRY(hipEventRecord(s->used, c->stream));
+    s->pending = true;
+    return 0;
+}
+
+// Pairs of params[i0 ..] that one sub-batch takes: at least one; within the launch limit and, with the staged images and maps of host
+// pointers, kSFScratchCap of device scratch.
+uint32_t ssimf_take(const rmgr_ssim_hip_ParamsF* params, uint32_t i0, uint32_t count, bool stage, uint64_t& staged)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const uint64_t part = ssimf_partials_per_pair(W, H);
+    const uint32_t nmax = ssim_hip::ssimf_max_count(W, H);
+    uint32_t n = 0;
+    staged = 0;
+    while (i0 + n < count && n < nmax) {
+        uint64_t bytes = 0;
+        if (stage) {
+            const rmgr_ssim_hip_ParamsF& p = params[i0 + n];
+            int64_t lo, hi;
+            extentf(p.imgA, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 4 + 63) & ~uint64_t(63);
+            extentf(p.imgB, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 4 + 63) & ~uint64_t(63);
+            if (p.ssimMap) bytes += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
+        }
+        if (n > 0 && part * (n + 1) + staged + bytes > kSFScratchCap) break;
+        staged += bytes;
+        ++n;
+    }
+    return n;
+}
+
+// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the images are copied
+// (each image's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own step and stride.
+int ssimf_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float range, float* ssim, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const double px = (double)W * (double)H;
+    int rc;
+    if ((rc = c->sf_sums_pin.grow(count))) return rc;
+    try {
+        std::vector<PairFDesc> d;
+        std::vector<float> back;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = ssimf_take(params, i0, count, stage, staged);
+            d.resize(n);
+            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
+            uint64_t off = 0;
+            std::vector<uint64_t> map_off(n, 0);
+            for (uint32_t i = 0; i < n; ++i) {
+                const rmgr_ssim_hip_ParamsF& p = params[i0 + i];
+                d[i] = make_descf(p, true);
+                if (!stage) continue;
+                for (int k = 0; k < 2; ++k) {
+                    const rmgr_ssim_hip_ImgF& im = k ? p.imgB : p.imgA;
+                    int64_t lo, hi;
+                    extentf(im, W, H, lo, hi);
+                    const size_t bytes = (size_t)(hi - lo + 1) * 4;
+                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
+                    (k ? d[i].b : d[i].a) = reinterpret_cast<const float*>(c->stage_a + off) - lo;
+                    off += (bytes + 63) & ~uint64_t(63);
+                }
+                if (p.ssimMap) {
+                    map_off[i] = off;
+                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
+                    d[i].map_step = 1; d[i].map_stride = W;
+                    off += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
+                }
+            }
+            if ((rc = ssimf_enqueue(c, n, &d[0], W, H, range, c->sf_sums_pin + i0))) return rc;
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (uint32_t i = 0; i < n && stage; ++i) {
+                const rmgr_ssim_hip_ParamsF& p = params[i0 + i];
+                if (!p.ssimMap) continue;
+                const float* src = reinterpret_cast<const float*>(c->stage_a + map_off[i]);
+                if (p.ssimStep == 1 && p.ssimStride == (ptrdiff_t)W) {
+                    HIP_TRY(hipMemcpy(p.ssimMap, src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+                    continue;
+                }
+                back.resize((size_t)W * H);
+                HIP_TRY(hipMemcpy(&back[0], src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+                for (uint32_t y = 0; y < H; ++y) {
+                    float* row = p.ssimMap + (ptrdiff_t)y * p.ssimStride;
+                    const float* s = &back[(size_t)y * W];
+                    for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = s[x];
+                }
+            }
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->sf_sums_pin[i] / px);
+    return 0;
+}
+
+} // namespace
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                         float dataRange, double* sumsDevice) RMGR_NOEXCEPT
+{
+    int rc = ssimf_validate(count, params, dataRange, sumsDevice);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    try {
+        std::vector<PairFDesc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = ssimf_take(params, i0, count, false, staged);
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) d[i] = make_descf(params[i0 + i], true);
+            if ((rc = ssimf_enqueue(c, n, &d[0], params[0].width, params[0].height, dataRange, sumsDevice + i0))) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    int rc = ssimf_validate(count, params, dataRange, ssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return ssimf_blocking(c, count, params, dataRange, ssim, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                              float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    int rc = ssimf_validate(count, params, dataRange, ssim);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    c = lease.c;
+    USE_DEVICE(c);
+    return ssimf_blocking(c, count, params, dataRange, ssim, true);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                              float dataRange, const float* gradOutDevice,
+                                              const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    int rc = ssimf_validate(count, params, dataRange, gradOutDevice);
+    if (rc) return rc;
+    if (gradA == NULL && gradB == NULL) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const rmgr_ssim_hip_GradF* g = k ? gradB : gradA;
+            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 3u))) return EINVAL;
+        }
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
+    const uint32_t nmax = ssim_hip::ssimf_max_count(W, H);
+    for (uint32_t i0 = 0; i0 < count;) {
+        const uint32_t n = std::min(count - i0, nmax);
+        rmgr_ssim_hip_Context_::SfSlot* s;
+        const size_t pair_bytes = n * sizeof(PairFDesc), bytes = pair_bytes + n * sizeof(GradFDesc);
+        if ((rc = ssimf_slot(c, bytes, s))) return rc;
+        PairFDesc* pd = reinterpret_cast<PairFDesc*>(s->pin.get());
+        GradFDesc* gd = reinterpret_cast<GradFDesc*>(s->pin.get() + pair_bytes);
+        for (uint32_t i = 0; i < n; ++i) {
+            pd[i] = make_descf(params[i0 + i], false);
+            GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
+            if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
+            if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
+            gd[i] = g;
+        }
+        HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(ssim_hip::launch_ssimf_grad(W, H, n, reinterpret_cast<const PairFDesc*>(s->dev.get()),
+                                            reinterpret_cast<const GradFDesc*>(s->dev.get() + pair_bytes), gradOutDevice + i0, dataRange, which, c->stream));
+        HIP_TRY(hipEventRecord(s->used, c->stream));
+        s->pending = true;
+        i0 += n;
+    }
+    return 0;
+}
+
 // ---- one process, several devices ------------------------------------------------------------------------------------
 // The reference parallelises one call over a caller-supplied thread pool (tile jobs, src/ssim.cpp:1048-1088; the OpenMP
 // adapter src/ssim-openmp.c:26-47).  The batch-level counterpart here: a contiguous block of the pairs per device, one

@@ -1,0 +1,163 @@
+"""SSIM of float32 tensors as a differentiable PyTorch operation, on the library's fused gfx950 kernels.
+
+    from ssim_amd.torch_ops import ssim, SSIMLoss
+    loss = 0.8 * (x - y).abs().mean() + 0.2 * SSIMLoss()(x, y)      # x, y: (N, C, H, W) float32 on the GPU
+    loss.backward()
+
+ssim(x, y, data_range) is the per-plane mean of the definition in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssimf); its backward is
+rmgr_ssim_hip_enqueue_ssimf_grad.  Everything is enqueued on torch.cuda.current_stream() of the tensors' device through a Context cached
+per (device, stream); neither forward nor backward waits for the host.  There is no eager fall-back: without the library this raises.
+
+torch is imported on first use, so `import ssim_amd` stays torch-free.
+"""
+import ctypes
+import math
+
+from . import api
+
+_contexts = {}      # (device index, stream handle) -> (Context, the torch stream it is bound to)
+_side = {}          # device index -> torch stream that stands in for the legacy default stream
+_function = None
+
+
+def _working_stream(torch, device):
+    """(current stream, stream the library's context is bound to).  The legacy default stream has no handle a context could adopt
+    (NULL means `create one`), so its work runs on a side stream that waits for it and that it waits for: device-side ordering only."""
+    cur = torch.cuda.current_stream(device)
+    if cur.cuda_stream != 0:
+        return cur, cur
+    side = _side.get(device.index)
+    if side is None:
+        side = _side[device.index] = torch.cuda.Stream(device)
+    return cur, side
+
+
+def _context(device, stream):
+    key = (device.index, stream.cuda_stream)
+    ent = _contexts.get(key)
+    if ent is None:
+        ent = _contexts[key] = (api.Context(device.index, ctypes.c_void_p(stream.cuda_stream)), stream)
+    return ent[0]
+
+
+def _check(x, y, data_range):
+    """The documented errors, before any GPU call.  Returns data_range as a float."""
+    import torch
+    if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
+        raise TypeError("ssim: x and y must be torch tensors")
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise TypeError("ssim: float32 tensors expected, got %s and %s" % (x.dtype, y.dtype))
+    if x.dim() < 2:
+        raise ValueError("ssim: tensors of shape (..., H, W) expected, got %d dimension(s)" % x.dim())
+    if x.shape != y.shape:
+        raise ValueError("ssim: shapes differ: %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    if not x.is_cuda or not y.is_cuda:
+        raise ValueError("ssim: the tensors must be on a GPU (there is no CPU path)")
+    if x.device != y.device:
+        raise ValueError("ssim: the tensors are on different devices: %s and %s" % (x.device, y.device))
+    if x.shape[-1] == 0 or x.shape[-2] == 0:
+        raise ValueError("ssim: empty planes: %s" % (tuple(x.shape),))
+    r = float(data_range)
+    if not (r > 0.0) or math.isinf(r):
+        raise ValueError("ssim: data_range must be finite and > 0, got %r" % (data_range,))
+    return r
+
+
+def _plane_offsets(t):
+    """Element offset of every (H, W) plane of t from t.data_ptr(), in the order of t.reshape(-1, H, W)."""
+    offs = [0]
+    for size, stride in zip(t.shape[:-2], t.stride()[:-2]):
+        offs = [o + i * stride for o in offs for i in range(size)]
+    return offs
+
+
+def _params(x, y):
+    h, w = x.shape[-2], x.shape[-1]
+    ox, oy = _plane_offsets(x), _plane_offsets(y)
+    n = len(ox)
+    params = (api.ParamsF * max(n, 1))()
+    px, py = x.data_ptr(), y.data_ptr()
+    xs, xr, ys, yr = x.stride(-1), x.stride(-2), y.stride(-1), y.stride(-2)
+    for i in range(n):
+        params[i] = api.make_params_f(w, h, px + 4 * ox[i], xs, xr, py + 4 * oy[i], ys, yr)
+    return params, n
+
+
+def _grad_planes(g, n, h, w):
+    """GradF array over the n contiguous planes of g."""
+    arr = (api.GradF * max(n, 1))()
+    base = g.data_ptr()
+    for i in range(n):
+        arr[i] = api.GradF(base + 4 * i * h * w, 1, w)
+    return arr
+
+
+def _make_function():
+    import torch
+
+    class _SSIM(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, data_range):
+            lead, h, w = x.shape[:-2], x.shape[-2], x.shape[-1]
+            params, n = _params(x, y)
+            sums = torch.empty(n, dtype=torch.float64, device=x.device)
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr())
+                if work is not cur:
+                    cur.wait_stream(work)
+            ctx.save_for_backward(x, y)
+            ctx.data_range = data_range
+            return (sums / (float(w) * float(h))).to(torch.float32).reshape(lead)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            x, y = ctx.saved_tensors
+            h, w = x.shape[-2], x.shape[-1]
+            want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_x or want_y):
+                return None, None, None
+            params, n = _params(x, y)
+            g = grad_out.to(torch.float32).reshape(-1).contiguous()
+            gx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_x else None
+            gy = torch.empty(y.shape, dtype=torch.float32, device=y.device) if want_y else None
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                _context(x.device, work).enqueue_ssimf_grad(params, n, ctx.data_range, g.data_ptr(),
+                                                            _grad_planes(gx, n, h, w) if want_x else None,
+                                                            _grad_planes(gy, n, h, w) if want_y else None)
+                if work is not cur:
+                    cur.wait_stream(work)
+            return gx, gy, None
+
+    return _SSIM
+
+
+def ssim(x, y, data_range=1.0):
+    """Per-plane SSIM of two float32 GPU tensors of identical shape (..., H, W), any strides (each plane is addressed in place, no copy):
+    a float32 tensor of shape x.shape[:-2].  Differentiable with respect to x, y or both; the gradient is computed only for the inputs
+    that need it.  TypeError: not float32 tensors.  ValueError: CPU tensors, differing shapes or devices, fewer than 2 dimensions,
+    empty planes, a data_range that is not finite and > 0."""
+    global _function
+    r = _check(x, y, data_range)
+    if _function is None:
+        _function = _make_function()
+    return _function.apply(x, y, r)
+
+
+class SSIMLoss(object):
+    """1 - ssim(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per plane).  A plain callable: it has no parameters."""
+
+    def __init__(self, data_range=1.0, reduction="mean"):
+        if reduction not in ("mean", "none"):
+            raise ValueError("SSIMLoss: reduction must be 'mean' or 'none', got %r" % (reduction,))
+        self.data_range, self.reduction = data_range, reduction
+
+    def __call__(self, x, y):
+        loss = 1.0 - ssim(x, y, self.data_range)
+        return loss.mean() if self.reduction == "mean" else loss
