@@ -22,6 +22,8 @@
  *   rmgr_ssim_hip_compute_msssim_device / _host   multi-scale SSIM: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim16, rmgr_ssim_hip_compute_ssim16_device / _host   SSIM of 9- to 16-bit samples: no reference
  *                                      counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_msssimf, rmgr_ssim_hip_compute_msssimf_device / _host, rmgr_ssim_hip_enqueue_msssimf_grad   multi-scale SSIM
+ *       of float32 images and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssimf, rmgr_ssim_hip_compute_ssimf_device / _host, rmgr_ssim_hip_enqueue_ssimf_grad   SSIM of float32
  *                                      samples and its gradient: no reference counterpart (definition below)
  *
@@ -476,6 +478,75 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssimf_host(rmgr_ssim_hip_Context* ctx, rmgr_u
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                               float dataRange, const float* gradOutDevice,
                                               const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
+
+/*
+ * Multi-scale SSIM of `count` pairs of float32 images of one size, and its gradient (1 - MS-SSIM as a training loss; MS-SSIM of HDR,
+ * linear-light and 9- to 16-bit material: uint16 converts to float32 exactly, dataRange = 2^depth - 1).  No reference counterpart:
+ * the definition is pinned down here, and tests/msssimf_model.py restates it in float64, the gradient included.  Additions only:
+ * RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ *   Samples, data range, inputs, window, alignment and size limit: as rmgr_ssim_hip_enqueue_ssimf (steps and strides in FLOATS;
+ *            C1 = float((0.01 R)^2), C2 = float((0.03 R)^2)); params[i].ssimMap must be NULL.
+ *   Scales and weights: as rmgr_ssim_hip_compute_msssim_device.  1 <= scales <= RMGR_SSIM_HIP_MSSSIM_MAX_SCALES; weights NULL: Wang's
+ *            five {0.0448, 0.2856, 0.3001, 0.2363, 0.1333} and scales must be 5; else `scales` finite weights >= 0 (host memory).
+ *   Pyramid  scale 0 is the input; scale s+1 is ceil(W_s/2) x ceil(H_s/2):
+ *              P'(x, y) = ((P(2x, 2y) + P(2x+1, 2y)) + (P(2x, 2y+1) + P(2x+1, 2y+1))) * 0.25f,
+ *            coordinates clamped to scale s, every operation rounded to fp32 in that order.  For floats the pyramid is not exact; the
+ *            order is part of the definition, so the bits are reproducible.
+ *   Per scale  with mu, s_aa, s_bb, s_ab, A1, A2, B1, B2 of the scale's planes as for ssimf:  cs = A2 / B2,  ssim = A1 A2 / (B1 B2);
+ *            mcs_s, mssim_s: the fp64 sums of the per-pixel values divided by double(W_s) * double(H_s).
+ *   Value    MS = prod_{s < M-1} max(mcs_s, 0)^w_s * max(mssim_{M-1}, 0)^w_{M-1} in double, with x^0 = 1 for every x (a zero
+ *            weight switches a scale off).  A NaN mean gives a NaN value.
+ *   Gradient  given gOut[i] = dLoss/dMS_i.  Let m_s be the mean scale s contributes (mcs_s, or mssim_s for the last scale).  If MS = 0
+ *            (some m_s <= 0 with w_s > 0) the whole gradient is 0 (the ReLU's subgradient).  Otherwise
+ *              k_s = gOut * w_s * MS / m_s / (double(W_s) * double(H_s))      (0 where w_s = 0),
+ *            and the local gradient of scale s is the ssimf formula Gt(k d_mu) + 2 a Gt(k d_aa) + b Gt(k d_ab) on the scale's planes with
+ *              last scale:    d_ab, d_aa, d_mu exactly as for ssimf;
+ *              other scales:  d_ab = 2 / B2,  d_aa = -cs / B2,  d_mu = -2 mu_a d_aa - mu_b d_ab      (cs only).
+ *            The total runs from the coarsest scale down through the ADJOINT of the clamped box filter:
+ *              g_s(x, y) = local_s(x, y) + 0.25 * c(x, y) * g_{s+1}(x >> 1, y >> 1),    c = cx * cy,
+ *            cx = 2 on the last column of an odd W_s (the column the clamp read twice; W_s = 1 included), else 1; likewise cy.
+ *            A gather: one writer per pixel, no atomics.  g_0 is dLoss/da (dLoss/db: a and b exchanged).
+ *   Arithmetic  fp32, centred at EVERY scale by the ssimf rule applied to that scale's planes: the centre of the 128 columns from
+ *            x0 = 128 k on is A's and B's sample of scale s at (min(x0 + 64, W_s - 1), (H_s - 1) / 2) when its magnitude is at most
+ *            dataRange, else 0.  The position is fixed by the image, so results do not depend on the batch.  k_s is rounded to float
+ *            once; 0.25 c is a power of two, so g_s = fp32(local_s + fp32(0.25 c g_{s+1})) adds one rounding per scale.  A scale
+ *            whose k_s is 0 contributes +0 whatever its samples are.  The product, the ReLU and k_s are computed on the device (pow
+ *            in double).  The context's mode does not change this path.
+ *   Determinism  as for ssimf: value, per-scale means and gradients have the same bits alone or anywhere in a batch, after any
+ *            sub-batch split, through every entry point, on every call, with one gradient or both, and for views with negative steps
+ *            or interleaved samples against the same pixels stored contiguously.  No floating-point atomics.
+ *
+ * _enqueue_msssimf: device pointers; asynchronous on the context's stream, never waits for the host.  valuesDevice: count doubles
+ *            (MS_i); scaleMeansDevice: count x scales x 2 doubles, [pair][scale]{mcs, mssim} -- both in DEVICE memory, both required.
+ * _compute_msssimf_device: device pointers; blocks.  msssim: count floats (host memory); scaleMeans: NULL, or count x scales x 2
+ *            doubles (host memory).
+ * _compute_msssimf_host: host pointers (ctx NULL: a default context); the images are staged to the device.
+ * _enqueue_msssimf_grad: everything device-resident, asynchronous on the context's stream, no host synchronisation.
+ *            scaleMeansDevice: what the forward wrote for the same pairs, scales and weights (16 x scales bytes per pair is all a
+ *            training step has to keep besides its inputs); gradOutDevice: count floats (device); gradA / gradB as for
+ *            _enqueue_ssimf_grad (either may be NULL, not both; written, not accumulated, each pixel once).  The pyramid is recomputed,
+ *            the forward statistics are not redone.
+ * Scratch  belongs to the context and is reused in stream order: the pyramid planes of scales >= 1 (about 2.7 bytes per scale-0 pixel of
+ *            a pair) and, in the backward, the gradient planes of scales >= 1 (up to 2.7 bytes more).  A batch runs in sub-batches
+ *            that keep it under about 1 GB; results do not depend on the split.
+ * EINVAL: every EINVAL of rmgr_ssim_hip_enqueue_ssimf / _enqueue_ssimf_grad and of rmgr_ssim_hip_compute_msssim_device (scales out of
+ *         range, NULL weights with scales != 5, a negative or non-finite weight, a non-NULL ssimMap), a NULL valuesDevice,
+ *         scaleMeansDevice or msssim -- all checked before any device is touched.  ENODEV: no device.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                           float dataRange, rmgr_uint32_t scales, const double* weights,
+                                           double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                  float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                  float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                const double* scaleMeansDevice, const float* gradOutDevice,
+                                                const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

@@ -123,6 +123,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_compute_msssim_device", "rmgr_ssim_hip_compute_msssim_host",
     "rmgr_ssim_hip_enqueue_ssim16", "rmgr_ssim_hip_compute_ssim16_device", "rmgr_ssim_hip_compute_ssim16_host",
     "rmgr_ssim_hip_enqueue_ssimf", "rmgr_ssim_hip_compute_ssimf_device", "rmgr_ssim_hip_compute_ssimf_host", "rmgr_ssim_hip_enqueue_ssimf_grad",
+    "rmgr_ssim_hip_enqueue_msssimf", "rmgr_ssim_hip_compute_msssimf_device", "rmgr_ssim_hip_compute_msssimf_host", "rmgr_ssim_hip_enqueue_msssimf_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -203,6 +204,10 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_compute_ssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssimf_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
+        "rmgr_ssim_hip_enqueue_msssimf": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
+        "rmgr_ssim_hip_compute_msssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_msssimf_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
     }
     for name, args in sig.items():
         if path is None and os.environ.get("RMGR_SSIM_LIB") and not hasattr(lib, name):
@@ -540,6 +545,45 @@ def compute_ssimf_batch(pairs, data_range, ctx=None):
     return np.array(out[:n], np.float32)
 
 
+def _weights_array(weights):
+    """The `weights` argument of the multi-scale entry points: NULL (Wang's five) or a double array."""
+    if weights is None:
+        return None
+    return (ctypes.c_double * max(len(weights), 1))(*[float(x) for x in weights])
+
+
+def _msssimf_call(fn_name, handle, params, count, data_range, scales, weights, per_scale):
+    out = (ctypes.c_float * max(count, 1))()
+    means = (ctypes.c_double * max(count * scales * 2, 1))() if per_scale else None
+    _check(fn_name, getattr(load_library(), fn_name)(handle, count, params, data_range, scales, _weights_array(weights), out, means))
+    vals = np.array(out[:count], np.float32)
+    if not per_scale:
+        return vals
+    return vals, np.array(means[:count * scales * 2], np.float64).reshape(count, scales, 2)
+
+
+def compute_msssimf(a, b, data_range, scales=5, weights=None, per_scale=False, ctx=None):
+    """Multi-scale SSIM of two H x W float32 host arrays at `data_range` (any strides numpy can express, negative ones included)
+    through rmgr_ssim_hip_compute_msssimf_host.  weights None: Wang's five (scales must be 5).  Returns a float32, and with
+    per_scale=True also a (scales, 2) float64 array of [scale]{mcs, mssim}."""
+    a, b = _f32_view(a), _f32_view(b)
+    assert a.shape == b.shape
+    params = (ParamsF * 1)()
+    params[0] = _params_f_of(a, b)
+    r = _msssimf_call("rmgr_ssim_hip_compute_msssimf_host", ctx.handle if ctx is not None else None, params, 1, data_range, scales, weights, per_scale)
+    return (r[0][0], r[1][0]) if per_scale else r[0]
+
+
+def compute_msssimf_batch(pairs, data_range, scales=5, weights=None, per_scale=False, ctx=None):
+    """compute_msssimf() of many host pairs of one size in one call: a float32 array (and a (count, scales, 2) array with per_scale)."""
+    pairs = [(_f32_view(a), _f32_view(b)) for a, b in pairs]
+    n = len(pairs)
+    params = (ParamsF * max(n, 1))()
+    for i, (a, b) in enumerate(pairs):
+        params[i] = _params_f_of(a, b)
+    return _msssimf_call("rmgr_ssim_hip_compute_msssimf_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale)
+
+
 class DeviceBuffer(object):
     def __init__(self, ctx, nbytes):
         self.ctx, self.nbytes = ctx, nbytes
@@ -683,6 +727,23 @@ class Context(object):
         """rmgr_ssim_hip_enqueue_ssimf_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs into the planes the GradF arrays
         grad_a / grad_b describe (None: not wanted), from `count` floats dLoss/dS_i in device memory; asynchronous, written not accumulated."""
         _check("rmgr_ssim_hip_enqueue_ssimf_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_grad(self.handle, count, params_array, data_range, grad_out_dev_ptr, grad_a, grad_b))
+
+    def msssimf_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False):
+        """MS-SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_msssimf_device: a float32
+        array, and with per_scale=True also a (count, scales, 2) float64 array of [pair][scale]{mcs, mssim}."""
+        return _msssimf_call("rmgr_ssim_hip_compute_msssimf_device", self.handle, params_array, count, data_range, scales, weights, per_scale)
+
+    def enqueue_msssimf(self, params_array, count, data_range, values_dev_ptr, means_dev_ptr, scales=5, weights=None):
+        """rmgr_ssim_hip_enqueue_msssimf: per-pair fp64 values and count x scales x 2 fp64 means into device memory, asynchronously on the
+        context's stream."""
+        _check("rmgr_ssim_hip_enqueue_msssimf", self.lib.rmgr_ssim_hip_enqueue_msssimf(
+            self.handle, count, params_array, data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+
+    def enqueue_msssimf_grad(self, params_array, count, data_range, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5, weights=None):
+        """rmgr_ssim_hip_enqueue_msssimf_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs, from the forward's means
+        (device memory), into the planes the GradF arrays describe; asynchronous on the context's stream, no host synchronisation."""
+        _check("rmgr_ssim_hip_enqueue_msssimf_grad", self.lib.rmgr_ssim_hip_enqueue_msssimf_grad(
+            self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
 
     def enqueue_batch(self, params_array, count, sums_dev_ptr):
         _check("rmgr_ssim_hip_enqueue_batch", self.lib.rmgr_ssim_hip_enqueue_batch(self.handle, count, params_array, sums_dev_ptr))

@@ -8,6 +8,7 @@
 #include "ssim_kernels.h"
 #include "ssim16_kernels.h"
 #include "ssimf_kernels.h"
+#include "msssimf_kernels.h"
 #include <rccl/rccl.h>      // types only: the library is dlopen()ed on first use, never linked
 
 #include <algorithm>
@@ -199,6 +200,12 @@ struct rmgr_ssim_hip_Context_ {
     int                    sf_next = 0;
     DeviceBuffer<double>   sf_partials;
     PinnedBuffer<double>   sf_sums_pin;
+    // multi-scale SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_msssimf*), reused in stream order: the pyramid planes
+    // of scales >= 1, the backward's gradient planes of scales >= 1, cell partials, the backward's coefficients k_s, and the
+    // blocking entry points' values and means (device, and pinned for the copy back).  Descriptor tables come from sf_slots.
+    DeviceBuffer<float>    msf_pyramid, msf_grads, msf_coef;
+    DeviceBuffer<double>   msf_partials, msf_out;
+    PinnedBuffer<double>   msf_out_pin;
 
     // Every grow-only staging buffer above, once: what context_held counts and context_trim gives back.
     template <typename F> void for_each_staging(F f)
@@ -212,6 +219,7 @@ struct rmgr_ssim_hip_Context_ {
         f(s16_desc); f(s16_desc_pin); f(s16_partials); f(s16_sums_pin);
         for (SfSlot& s : sf_slots) { f(s.dev); f(s.pin); }
         f(sf_partials); f(sf_sums_pin);
+        f(msf_pyramid); f(msf_grads); f(msf_coef); f(msf_partials); f(msf_out); f(msf_out_pin);
     }
 
     bool profiling = false;

@@ -1402,6 +1402,260 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uin
     return 0;
 }
 
+// ---- multi-scale SSIM of float32 samples and its gradient (rmgr_ssim_hip_enqueue_msssimf, _compute_msssimf_*, _enqueue_msssimf_grad) --------
+// The definition is in include/rmgr/ssim-hip.h, the kernels in msssimf_kernels.hip.  Scale 0 is read where the caller has it; the planes
+// of scales >= 1 (and, in the backward, their gradient planes) are dense planes of the context's scratch, one set per pair, rewritten by
+// every sub-batch in stream order.  Every plane, cell and tile belongs to one pair, so neither the sub-batches nor the launch a pair lands
+// in change a bit.
+namespace {
+
+const uint64_t kMsfScratchCap = uint64_t(1) << 30;
+
+// Every check the entry points share, before any device is touched.
+int msssimf_validate(rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, rmgr_uint32_t scales, const double* weights,
+                     const void* out)
+{
+    int rc = ssimf_validate(count, params, dataRange, out);
+    if (rc) return rc;
+    if (scales < 1 || scales > RMGR_SSIM_HIP_MSSSIM_MAX_SCALES) return EINVAL;
+    if (weights == NULL) {
+        if (scales != 5) return EINVAL;
+    } else {
+        for (uint32_t s = 0; s < scales; ++s)
+            if (!std::isfinite(weights[s]) || weights[s] < 0.0) return EINVAL;
+    }
+    for (uint32_t i = 0; i < count; ++i)
+        if (params[i].ssimMap != NULL) return EINVAL;
+    if (ssim_hip::msssimf_max_count(params[0].width, params[0].height) == 0) return EINVAL;
+    return 0;
+}
+
+// Device scratch one pair needs: the pyramid of both images, grad_planes (0 forward, 1 or 2 backward) coarse gradient pyramids, its
+// cell partials (forward) or coefficients (backward).
+uint64_t msf_pair_bytes(uint32_t W, uint32_t H, uint32_t scales, int grad_planes)
+{
+    const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
+    return (2 + (uint64_t)grad_planes) * pyr * sizeof(float) +
+           (grad_planes ? scales * sizeof(float) : ssim_hip::msf_partials(W, H, 1, scales) * sizeof(double));
+}
+
+// Pairs one sub-batch takes when none of them is staged: at least one.
+uint32_t msf_take(uint32_t W, uint32_t H, uint32_t scales, int grad_planes, uint32_t left)
+{
+    const uint64_t fit = std::max<uint64_t>(1, kMsfScratchCap / msf_pair_bytes(W, H, scales, grad_planes));
+    return (uint32_t)std::min<uint64_t>(std::min<uint64_t>(left, ssim_hip::msssimf_max_count(W, H)), fit);
+}
+
+// Fills table[scale][pair] (scales x n): scale 0 from d, scales >= 1 dense planes of `pyramid`, scale by scale, A then B of each pair.
+void msf_fill_descs(PairFDesc* table, const PairFDesc* d, uint32_t n, uint32_t W, uint32_t H, uint32_t scales, float* pyramid)
+{
+    for (uint32_t i = 0; i < n; ++i) { table[i] = d[i]; table[i].map = NULL; table[i].map_step = table[i].map_stride = 0; }
+    float* at = pyramid;
+    for (uint32_t s = 1; s < scales; ++s) {
+        const uint64_t plane = ssim_hip::msf_plane(W, H, s);
+        const int64_t stride = ssim_hip::msf_dim(W, s);
+        for (uint32_t i = 0; i < n; ++i) {
+            PairFDesc& t = table[(size_t)s * n + i];
+            t.a = at; t.a_step = 1; t.a_stride = stride; at += plane;
+            t.b = at; t.b_step = 1; t.b_stride = stride; at += plane;
+            t.map = NULL; t.map_step = t.map_stride = 0;
+        }
+    }
+}
+
+// Enqueues the forward of n pairs (scale-0 descriptors in host memory, images on the device) on the context's stream: n x scales x 2
+// means and n values into device memory.
+int msssimf_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const PairFDesc* d, uint32_t W, uint32_t H, float range, uint32_t scales,
+                    const double* w, double* means, double* values)
+{
+    int rc;
+    if ((rc = c->msf_pyramid.grow((size_t)(2 * ssim_hip::msf_pyramid_floats(W, H, scales) * n)))) return rc;
+    if ((rc = c->msf_partials.grow((size_t)ssim_hip::msf_partials(W, H, n, scales)))) return rc;
+    rmgr_ssim_hip_Context_::SfSlot* s;
+    const size_t bytes = (size_t)scales * n * sizeof(PairFDesc);
+    if ((rc = ssimf_slot(c, bytes, s))) return rc;
+    msf_fill_descs(reinterpret_cast<PairFDesc*>(s->pin.get()), d, n, W, H, scales, c->msf_pyramid);
+    bool wide = false;
+    for (uint32_t i = 0; i < n; ++i) wide = wide || !ssim_hip::fitsf_narrow(d[i]);
+    HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ssim_hip::launch_msssimf(reinterpret_cast<const PairFDesc*>(s->dev.get()), n, W, H, scales, wide, range, w, c->cu_count, c->xcd_count,
+                                     c->msf_partials, means, values, c->stream));
+    HIP_TRY(hipEventRecord(s->used, c->stream));
+    s->pending = true;
+    return 0;
+}
+
+// The blocking entry points: every sub-batch into c->msf_out (count values, then count x scales x 2 means), one copy back, one wait.
+// stage: host pointers -- each sub-batch's images are copied (each image's sample range) into c->stage_a first.
+int msssimf_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float range, uint32_t scales, const double* w,
+                     float* msssim, double* scaleMeans, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const size_t per = 1 + 2 * (size_t)scales, total = per * count;
+    const uint64_t pair_bytes = msf_pair_bytes(W, H, scales, 0);
+    int rc;
+    if ((rc = c->msf_out.grow(total))) return rc;
+    if ((rc = c->msf_out_pin.grow(total))) return rc;
+    double* values = c->msf_out;
+    double* means = c->msf_out + count;
+    try {
+        std::vector<PairFDesc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint32_t n = msf_take(W, H, scales, 0, count - i0);
+            uint64_t staged = 0;
+            if (stage) {                    // the staged images count against the same cap
+                uint32_t m = 0;
+                while (m < n) {
+                    uint64_t bytes = 0;
+                    int64_t lo, hi;
+                    extentf(params[i0 + m].imgA, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 4 + 63) & ~uint64_t(63);
+                    extentf(params[i0 + m].imgB, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 4 + 63) & ~uint64_t(63);
+                    if (m > 0 && pair_bytes * (m + 1) + staged + bytes > kMsfScratchCap) break;
+                    staged += bytes;
+                    ++m;
+                }
+                n = m;
+                if ((rc = c->stage_a.grow((size_t)staged))) return rc;
+            }
+            d.resize(n);
+            uint64_t off = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                const rmgr_ssim_hip_ParamsF& p = params[i0 + i];
+                d[i] = make_descf(p, false);
+                for (int k = 0; k < 2 && stage; ++k) {
+                    const rmgr_ssim_hip_ImgF& im = k ? p.imgB : p.imgA;
+                    int64_t lo, hi;
+                    extentf(im, W, H, lo, hi);
+                    const size_t bytes = (size_t)(hi - lo + 1) * 4;
+                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
+                    (k ? d[i].b : d[i].a) = reinterpret_cast<const float*>(c->stage_a + off) - lo;
+                    off += (bytes + 63) & ~uint64_t(63);
+                }
+            }
+            if ((rc = msssimf_enqueue(c, n, &d[0], W, H, range, scales, w, means + (size_t)i0 * scales * 2, values + i0))) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    HIP_TRY(hipMemcpyAsync(c->msf_out_pin, c->msf_out, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < count; ++i) msssim[i] = (float)c->msf_out_pin[i];
+    if (scaleMeans) memcpy(scaleMeans, c->msf_out_pin + count, (size_t)count * scales * 2 * sizeof(double));
+    return 0;
+}
+
+} // namespace
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
+                                           rmgr_uint32_t scales, const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
+{
+    int rc = msssimf_validate(count, params, dataRange, scales, weights, valuesDevice);
+    if (rc) return rc;
+    if (scaleMeansDevice == NULL || !c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    try {
+        std::vector<PairFDesc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            const uint32_t n = msf_take(W, H, scales, 0, count - i0);
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) d[i] = make_descf(params[i0 + i], false);
+            if ((rc = msssimf_enqueue(c, n, &d[0], W, H, dataRange, scales, weights ? weights : kWangWeights,
+                                      scaleMeansDevice + (size_t)i0 * scales * 2, valuesDevice + i0))) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
+                                                  rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    int rc = msssimf_validate(count, params, dataRange, scales, weights, msssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return msssimf_blocking(c, count, params, dataRange, scales, weights ? weights : kWangWeights, msssim, scaleMeans, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
+                                                rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    int rc = msssimf_validate(count, params, dataRange, scales, weights, msssim);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    c = lease.c;
+    USE_DEVICE(c);
+    return msssimf_blocking(c, count, params, dataRange, scales, weights ? weights : kWangWeights, msssim, scaleMeans, true);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
+                                                rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
+                                                const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    int rc = msssimf_validate(count, params, dataRange, scales, weights, gradOutDevice);
+    if (rc) return rc;
+    if (scaleMeansDevice == NULL || (gradA == NULL && gradB == NULL)) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const rmgr_ssim_hip_GradF* g = k ? gradB : gradA;
+            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 3u))) return EINVAL;
+        }
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0), planes = (gradA ? 1 : 0) + (gradB ? 1 : 0);
+    const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
+    const double* w = weights ? weights : kWangWeights;
+    try {
+        std::vector<PairFDesc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            const uint32_t n = msf_take(W, H, scales, planes, count - i0);
+            if ((rc = c->msf_pyramid.grow((size_t)(2 * pyr * n)))) return rc;
+            if ((rc = c->msf_grads.grow((size_t)((uint64_t)planes * pyr * n)))) return rc;
+            if ((rc = c->msf_coef.grow((size_t)n * scales))) return rc;
+            rmgr_ssim_hip_Context_::SfSlot* s;
+            const size_t pair_bytes = (size_t)scales * n * sizeof(PairFDesc), bytes = pair_bytes + (size_t)scales * n * sizeof(GradFDesc);
+            if ((rc = ssimf_slot(c, bytes, s))) return rc;
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) d[i] = make_descf(params[i0 + i], false);
+            msf_fill_descs(reinterpret_cast<PairFDesc*>(s->pin.get()), &d[0], n, W, H, scales, c->msf_pyramid);
+            // gradient planes: scale 0 the caller's, scales >= 1 dense scratch, scale by scale, dA then dB of each pair
+            GradFDesc* gd = reinterpret_cast<GradFDesc*>(s->pin.get() + pair_bytes);
+            float* at = c->msf_grads;
+            for (uint32_t sc = 0; sc < scales; ++sc) {
+                const uint64_t plane = ssim_hip::msf_plane(W, H, sc);
+                const int64_t stride = ssim_hip::msf_dim(W, sc);
+                for (uint32_t i = 0; i < n; ++i) {
+                    GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
+                    if (sc == 0) {
+                        if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
+                        if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
+                    } else {
+                        if (gradA) { g.ga = at; g.ga_step = 1; g.ga_stride = stride; at += plane; }
+                        if (gradB) { g.gb = at; g.gb_step = 1; g.gb_stride = stride; at += plane; }
+                    }
+                    gd[(size_t)sc * n + i] = g;
+                }
+            }
+            HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(ssim_hip::launch_msssimf_grad(reinterpret_cast<const PairFDesc*>(s->dev.get()), reinterpret_cast<const GradFDesc*>(s->dev.get() + pair_bytes),
+                                                  n, W, H, scales, dataRange, w, scaleMeansDevice + (size_t)i0 * scales * 2, gradOutDevice + i0,
+                                                  c->msf_coef, which, c->stream));
+            HIP_TRY(hipEventRecord(s->used, c->stream));
+            s->pending = true;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
 // ---- one process, several devices ------------------------------------------------------------------------------------
 // The reference parallelises one call over a caller-supplied thread pool (tile jobs, src/ssim.cpp:1048-1088; the OpenMP
 // adapter src/ssim-openmp.c:26-47).  The batch-level counterpart here: a contiguous block of the pairs per device, one

@@ -1,11 +1,13 @@
-"""SSIM of float32 tensors as a differentiable PyTorch operation, on the library's fused gfx950 kernels.
+"""SSIM and multi-scale SSIM of float32 tensors as differentiable PyTorch operations, on the library's fused gfx950 kernels.
 
-    from ssim_amd.torch_ops import ssim, SSIMLoss
+    from ssim_amd.torch_ops import ssim, SSIMLoss, ms_ssim, MSSSIMLoss
     loss = 0.8 * (x - y).abs().mean() + 0.2 * SSIMLoss()(x, y)      # x, y: (N, C, H, W) float32 on the GPU
+    loss = 0.16 * (x - y).abs().mean() + 0.84 * MSSSIMLoss()(x, y)
     loss.backward()
 
 ssim(x, y, data_range) is the per-plane mean of the definition in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssimf); its backward is
-rmgr_ssim_hip_enqueue_ssimf_grad.  Everything is enqueued on torch.cuda.current_stream() of the tensors' device through a Context cached
+rmgr_ssim_hip_enqueue_ssimf_grad; ms_ssim(x, y, data_range, scales, weights) is rmgr_ssim_hip_enqueue_msssimf and its backward
+rmgr_ssim_hip_enqueue_msssimf_grad.  Everything is enqueued on torch.cuda.current_stream() of the tensors' device through a Context cached
 per (device, stream); neither forward nor backward waits for the host.  There is no eager fall-back: without the library this raises.
 
 torch is imported on first use, so `import ssim_amd` stays torch-free.
@@ -18,6 +20,7 @@ from . import api
 _contexts = {}      # (device index, stream handle) -> (Context, the torch stream it is bound to)
 _side = {}          # device index -> torch stream that stands in for the legacy default stream
 _function = None
+_ms_function = None
 
 
 def _working_stream(torch, device):
@@ -160,4 +163,99 @@ class SSIMLoss(object):
 
     def __call__(self, x, y):
         loss = 1.0 - ssim(x, y, self.data_range)
+        return loss.mean() if self.reduction == "mean" else loss
+
+
+def _check_scales(scales, weights):
+    """The documented errors of ms_ssim's scales and weights, before any GPU call.  Returns (scales, weights as a tuple of floats or None)."""
+    if isinstance(scales, bool) or not isinstance(scales, int):
+        raise TypeError("ms_ssim: scales must be an int, got %r" % (scales,))
+    if not 1 <= scales <= api.MSSSIM_MAX_SCALES:
+        raise ValueError("ms_ssim: scales must be 1 .. %d, got %d" % (api.MSSSIM_MAX_SCALES, scales))
+    if weights is None:
+        if scales != 5:
+            raise ValueError("ms_ssim: the default weights are Wang's five: pass %d weights for scales=%d" % (scales, scales))
+        return scales, None
+    w = tuple(float(v) for v in weights)
+    if len(w) != scales:
+        raise ValueError("ms_ssim: %d weights for %d scales" % (len(w), scales))
+    for v in w:
+        if not (v >= 0.0) or math.isinf(v):
+            raise ValueError("ms_ssim: weights must be finite and >= 0, got %r" % (weights,))
+    return scales, w
+
+
+def _make_ms_function():
+    import torch
+
+    class _MSSSIM(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, data_range, scales, weights):
+            lead = x.shape[:-2]
+            params, n = _params(x, y)
+            values = torch.empty(n, dtype=torch.float64, device=x.device)
+            means = torch.empty((n, scales, 2), dtype=torch.float64, device=x.device)
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                _context(x.device, work).enqueue_msssimf(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights)
+                if work is not cur:
+                    cur.wait_stream(work)
+            ctx.save_for_backward(x, y, means)
+            ctx.data_range, ctx.scales, ctx.weights = data_range, scales, weights
+            return values.to(torch.float32).reshape(lead)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            x, y, means = ctx.saved_tensors
+            h, w = x.shape[-2], x.shape[-1]
+            want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_x or want_y):
+                return None, None, None, None, None
+            params, n = _params(x, y)
+            g = grad_out.to(torch.float32).reshape(-1).contiguous()
+            gx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_x else None
+            gy = torch.empty(y.shape, dtype=torch.float32, device=y.device) if want_y else None
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                _context(x.device, work).enqueue_msssimf_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(),
+                                                              _grad_planes(gx, n, h, w) if want_x else None,
+                                                              _grad_planes(gy, n, h, w) if want_y else None, ctx.scales, ctx.weights)
+                if work is not cur:
+                    cur.wait_stream(work)
+            return gx, gy, None, None, None
+
+    return _MSSSIM
+
+
+def ms_ssim(x, y, data_range=1.0, scales=5, weights=None):
+    """Per-plane multi-scale SSIM of two float32 GPU tensors of identical shape (..., H, W), any strides (each plane is addressed in
+    place, no copy): a float32 tensor of shape x.shape[:-2].  weights None: Wang's five (scales must be 5); else `scales` finite weights
+    >= 0.  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that need it, from x, y and the
+    (planes, scales, 2) float64 per-scale means the forward keeps.  TypeError / ValueError as ssim(), plus ValueError for scales outside
+    1 .. 8, a wrong number of weights, a negative or non-finite weight (TypeError: scales is not an int)."""
+    global _ms_function
+    r = _check(x, y, data_range)
+    scales, w = _check_scales(scales, weights)
+    if _ms_function is None:
+        _ms_function = _make_ms_function()
+    return _ms_function.apply(x, y, r, scales, w)
+
+
+class MSSSIMLoss(object):
+    """1 - ms_ssim(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per plane).  A plain callable: it
+    has no parameters."""
+
+    def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean"):
+        if reduction not in ("mean", "none"):
+            raise ValueError("MSSSIMLoss: reduction must be 'mean' or 'none', got %r" % (reduction,))
+        _check_scales(scales, weights)
+        self.data_range, self.scales, self.weights, self.reduction = data_range, scales, weights, reduction
+
+    def __call__(self, x, y):
+        loss = 1.0 - ms_ssim(x, y, self.data_range, self.scales, self.weights)
         return loss.mean() if self.reduction == "mean" else loss

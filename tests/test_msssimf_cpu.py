@@ -1,0 +1,384 @@
+"""CPU: multi-scale SSIM of float32 samples and its gradient -- the definition and its boundaries (include/rmgr/ssim-hip.h,
+rmgr_ssim_hip_*_msssimf*).
+
+  * the float64 model (tests/msssimf_model.py) on integer-valued planes at range 255 IS the uint8 model (tests/msssim_model.py) given
+    the same taps; with one scale of weight 1 it IS the ssimf model, value and gradient; it is scale invariant;
+  * downsample_t is the adjoint of downsample, and the model's gradient is the derivative of the model's MS (central differences at
+    two steps: corners, edges, odd sizes, a crop narrower than 5, 1 x 1, a zero weight in the middle of the list);
+  * the ReLU: an anti-correlated pair has value 0 and gradient exactly 0, and no golden fixture sits near the kink;
+  * the fp32 emulation of the kernels stays inside the bounds tests/test_gpu_msssimf.py asserts;
+  * the entry points are exported, every EINVAL comes before the device, a valid call without a device is ENODEV, ssim_amd.torch_ops
+    refuses what it documents before any GPU call, and the new kernels keep their budgets.
+"""
+import ctypes
+import errno
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import msssim_model as MS8
+import msssimf_model as M
+import ssimf_model as SF
+import ssim_amd
+from conftest import ROOT, image_entries, load_pair
+
+ENTRY_POINTS = ("rmgr_ssim_hip_enqueue_msssimf", "rmgr_ssim_hip_compute_msssimf_device", "rmgr_ssim_hip_compute_msssimf_host",
+                "rmgr_ssim_hip_enqueue_msssimf_grad")
+CONFIGS = [(5, None)] + [(m, (1.0 / m,) * m) for m in range(1, 9)]      # Wang's five; uniform weights at 1 .. 8 scales
+
+
+def test_model_is_the_uint8_model_on_integer_planes_and_scale_invariant(manifest):
+    """msssim_model uses the true (float64) taps and the float-rounded constants of range 255: given those the two models are one
+    (with each model's own taps they differ by 4.5e-8 on einstein_jpg, f32-rounded against true taps)."""
+    g64 = MS8.gaussian_taps()
+    c64 = M.constants(255.0, f32=False)
+    for n in image_entries(manifest):
+        a, b = load_pair(manifest[n])
+        mod = M.Model(a, b, 255.0, g=g64)
+        assert (mod.c1, mod.c2) == (MS8.C1_F32, MS8.C2_F32)
+        for scales, w in ((5, None), (1, (1.0,)), (3, (0.2, 0.3, 0.5)), (8, (0.125,) * 8)):
+            got, gm = mod.msssim(scales, w)
+            want, wm = MS8.msssim(a, b, scales, w)
+            assert abs(got - want) <= 1e-12 and np.abs(gm - wm).max() <= 1e-12, (n, scales, got, want)
+        # a / 255 at range 1 against the samples as stored at range 255, the double constants on both sides
+        raw, _ = M.msssim(a, b, 255.0, 5, None, *c64)
+        unit, _ = M.msssim(a / 255.0, b / 255.0, 1.0, 5, None, *M.constants(1.0, f32=False))
+        assert abs(raw - unit) <= 1e-12, (n, raw, unit)
+
+
+def test_one_scale_of_weight_one_is_the_ssimf_model(manifest):
+    for n in ("einstein_jpg", "bbb257x65_q50_ch1", "einstein_blur"):
+        a, b = load_pair(manifest[n])
+        a, b = a[:60, :70] / 255.0, b[:60, :70] / 255.0
+        v, means = M.msssim(a, b, 1.0, 1, (1.0,))
+        want, _ = SF.ssim(a, b, 1.0)
+        assert abs(v - want) <= 1e-12 * abs(want) and abs(means[0][1] - want) <= 1e-12 * abs(want)
+        ga, gb = M.grad(a, b, 1.0, -0.75, 1, (1.0,))
+        wa, wb = SF.grad(a, b, 1.0, -0.75)
+        assert np.abs(ga - wa).max() <= 1e-12 * np.abs(wa).max() and np.abs(gb - wb).max() <= 1e-12 * np.abs(wb).max()
+
+
+def test_downsample_t_is_the_adjoint_of_downsample():
+    rng = np.random.default_rng(17)
+    for shape in [(40, 48), (41, 48), (40, 47), (33, 17), (5, 3), (1, 1), (1, 9), (1, 8), (7, 1), (2, 2), (3, 3)]:
+        u = rng.standard_normal(shape)
+        d = M.downsample(u)
+        assert d.shape == ((shape[0] + 1) // 2, (shape[1] + 1) // 2)
+        v = rng.standard_normal(d.shape)
+        lhs, rhs = float(np.sum(d * v)), float(np.sum(u * M.downsample_t(v, *shape)))
+        assert abs(lhs - rhs) <= 1e-12 * max(abs(lhs), abs(rhs), 1e-3), (shape, lhs, rhs)
+        # the gather form of the definition: 0.25 c(x, y) v(x >> 1, y >> 1)
+        c = 0.25 * np.outer(M.box_adjoint_weight(shape[0]), M.box_adjoint_weight(shape[1]))
+        gather = c * v[np.ix_(np.arange(shape[0]) >> 1, np.arange(shape[1]) >> 1)]
+        assert np.abs(gather - M.downsample_t(v, *shape)).max() <= 1e-15
+    assert np.array_equal(M.downsample(np.array([[1.0, 3.0, 5.0]])), np.array([[2.0, 5.0]]))          # the clamp reads the last column twice
+    assert M.downsample(np.arange(12, dtype=np.float32).reshape(3, 4)).dtype == np.float32
+
+
+def _fd_points(h, w, rng):
+    pts = {(0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1), (0, w // 2), (h - 1, w // 3), (h // 2, 0), (h // 3, w - 1)}
+    while len(pts) < min(12, h * w):
+        pts.add((int(rng.integers(0, h)), int(rng.integers(0, w))))
+    return sorted(pts)
+
+
+def test_gradient_is_the_derivative_of_the_value(manifest):
+    """Central differences of the model's own MS at steps 1e-5 and 5e-6 (range 1) against grad().  The bound is the method's: the
+    truncation error of a central difference is eps^2 f''' / 6, about 1e-10 f''' here, and the round-off of the fp64 value about
+    1e-16 / eps = 1e-11 against gradients of 1e-4 .. 1e-2; measured at most 1.2e-8 of the plane's largest gradient magnitude at 1e-5
+    and 5.7e-7 on the 1 x 1 image, whose value bends most.  1e-6 holds at both steps and is four orders below what a wrong term
+    would leave."""
+    rng = np.random.default_rng(5)
+    W5 = M.WANG_WEIGHTS
+    cases = (("einstein_jpg", (0, 0, 41, 51), W5), ("bbb257x65_q50_ch1", (10, 100, 37, 48), W5), ("einstein_blur", (7, 9, 3, 5), (0.5, 0.3, 0.2)),
+             ("einstein_jpg", (30, 30, 20, 4), (0.25, 0.25, 0.5)), ("einstein_jpg", (50, 50, 1, 1), W5), ("einstein_blur", (100, 60, 33, 64), (1.0,)),
+             ("einstein_contrast", (216, 208, 40, 47), (0.3, 0.0, 0.3, 0.4)))
+    for n, (y0, x0, h, w), wts in cases:
+        a, b = load_pair(manifest[n])
+        a, b = a[y0:y0 + h, x0:x0 + w] / 255.0, b[y0:y0 + h, x0:x0 + w] / 255.0
+        assert a.shape == (h, w)
+        g_out, scales = -0.75, len(wts)
+        ga, gb = M.grad(a, b, 1.0, g_out, scales, wts)
+        worst = 0.0
+        for which, gr in ((0, ga), (1, gb)):
+            scale = np.abs(gr).max()
+            for eps in (1e-5, 5e-6):
+                for (y, x) in _fd_points(h, w, rng):
+                    p, m = [a.copy(), b.copy()], [a.copy(), b.copy()]
+                    p[which][y, x] += eps
+                    m[which][y, x] -= eps
+                    fd = g_out * (M.msssim(p[0], p[1], 1.0, scales, wts)[0] - M.msssim(m[0], m[1], 1.0, scales, wts)[0]) / (2 * eps)
+                    worst = max(worst, abs(fd - gr[y, x]) / scale)
+                    assert abs(fd - gr[y, x]) <= 1e-6 * scale, (n, (h, w), which, y, x, eps, fd, gr[y, x])
+        print("%s %dx%d, %d scales: worst mismatch %.2g of max|grad|" % (n, w, h, scales, worst))
+
+
+def test_relu_switches_the_gradient_off_and_no_fixture_sits_near_it(manifest):
+    a, _ = load_pair(manifest["einstein_jpg"])
+    a = a.astype(np.float64)
+    v, means = M.msssim(a, 255.0 - a, 255.0)
+    assert v == 0.0 and np.all(means[:, 0] < -0.3) and np.all(means[:, 0] > -0.9), means
+    ga, gb = M.grad(a, 255.0 - a, 255.0, 1.0)
+    assert not ga.any() and not gb.any()
+    # a zero weight switches a scale off, even one whose mean is negative
+    v, _ = M.msssim(a, 255.0 - a, 255.0, 2, (0.0, 0.0))
+    assert v == 1.0
+    lowest = (9.0, None)
+    for n in image_entries(manifest):
+        fa, fb = load_pair(manifest[n])
+        means = M.Model(fa, fb, 255.0).means(8)
+        lowest = min(lowest, (float(means.min()), n))
+        assert means.min() > 0.25, (n, means)
+    print("lowest per-scale mean over scales 1 .. 8: %.3f (%s)" % lowest)
+
+
+def test_fp32_emulation_is_inside_the_gpu_bounds(manifest):
+    """Emulation against the float64 model on every golden pair in the three forms x {Wang's 5 scales, uniform weights at 1 .. 8
+    scales}: value, every per-scale mean, both gradients.  Measured: 1.172e-6 on the value, 1.602e-6 on a per-scale mean, 2.648e-4 of
+    the plane's largest float64 gradient magnitude (einstein_meanshift), and max|grad| * W * H * R = 3.648e-4 on the pair of identical
+    images (exact gradient 0).  tests/test_gpu_msssimf.py asserts 1.9 to 2.2 x these: the margin covers the order of the fp64 sums, the
+    1-ulp reciprocal, fma contraction and the device's pow, which the emulation does not restate."""
+    worst_v = worst_m = worst_grad = worst_ident = 0.0
+    identical = 0
+    for n in image_entries(manifest):
+        a, b = load_pair(manifest[n])
+        for form, fa, fb, r in M.forms(a, b):
+            mod, emu = M.Model(fa, fb, r), M.Emulation(fa, fb, r)
+            for scales, w in CONFIGS:
+                gv, gm = mod.msssim(scales, w)
+                ev, em = emu.msssim(scales, w)
+                worst_v, worst_m = max(worst_v, abs(ev - gv)), max(worst_m, float(np.abs(em - gm).max()))
+                ga, gb = mod.grad(1.0, scales, w)
+                ea, eb = emu.grad(1.0, scales, w)
+                for e, g in ((ea, ga), (eb, gb)):
+                    assert e.dtype == np.float32 and np.all(np.isfinite(e))
+                    if np.array_equal(a, b):
+                        assert np.abs(g).max() < 1e-13 / r
+                        identical += 1
+                        worst_ident = max(worst_ident, float(np.abs(e).max()) * fa.size * r)
+                    else:
+                        worst_grad = max(worst_grad, float(np.abs(e - g).max() / np.abs(g).max()))
+    assert identical == 2 * 3 * len(CONFIGS)       # einstein_einstein, both gradients, three forms, every configuration
+    print("emulation: value %.4g mean %.4g grad %.4g identical %.4g" % (worst_v, worst_m, worst_grad, worst_ident))
+    assert worst_v <= M.EMU_VALUE and worst_m <= M.EMU_MEAN and worst_grad <= M.EMU_GRAD and worst_ident <= M.EMU_IDENT, (worst_v, worst_m, worst_grad, worst_ident)
+    # pinned from below as well: a figure that moved far away means the emulation no longer restates these kernels
+    assert worst_v >= M.EMU_VALUE / 2 and worst_m >= M.EMU_MEAN / 2 and worst_grad >= M.EMU_GRAD / 2 and worst_ident >= M.EMU_IDENT / 2
+    for tol, emu in ((M.VALUE_TOL, M.EMU_VALUE), (M.MEAN_TOL, M.EMU_MEAN), (M.GRAD_TOL, M.EMU_GRAD), (M.IDENT_TOL, M.EMU_IDENT)):
+        assert 1.9 <= tol / emu <= 2.2
+
+
+def test_emulation_restates_the_pyramid_order_the_centres_and_the_accumulation():
+    rng = np.random.default_rng(3)
+    a = (rng.random((37, 300)) * 1000).astype(np.float32)
+    b = (rng.random((37, 300)) * 1000).astype(np.float32)
+    emu = M.Emulation(a, b, 1000.0)
+    s1 = emu.scale(1)
+    # fp32 in the defined order: (top pair) + (bottom pair), then * 0.25f; the last row of an odd height is read twice
+    want = ((a[36, 0] + a[36, 1]) + (a[36, 0] + a[36, 1])) * np.float32(0.25)
+    assert s1.a.dtype == np.float32 and s1.a.shape == (19, 150) and s1.a[18, 0] == want
+    # the centres of scale 1 come from scale 1's own plane
+    assert list(SF.centres(s1.a, 1000.0)) == [s1.a[9, 64], s1.a[9, 149]]
+    # a scale whose coefficient is 0 contributes +0, and the coarser gradient arrives through 0.25 c g(x >> 1, y >> 1)
+    ga, _ = emu.grad(1.0, 2, (0.0, 1.0))
+    up, _ = s1.local(np.float32(M.coefficients(emu.means(2), (0.0, 1.0), 1.0, [(300, 37), (150, 19)])[1]), True)
+    assert ga[10, 20] == np.float32(0.25) * up[5, 10] and ga[36, 299] == np.float32(0.5) * up[18, 149]
+
+
+# ---- the C ABI's validation (no device needed) ----
+
+def _params(a, b, n=1, **over):
+    ps = (ssim_amd.ParamsF * n)()
+    h, w = a.shape
+    for i in range(n):
+        ps[i] = ssim_amd.make_params_f(w, h, a.ctypes.data, 1, w, b.ctypes.data, 1, w)
+    for k, v in over.items():
+        setattr(ps[0], k, v)
+    return ps
+
+
+def _grads(a, n=1):
+    gs = (ssim_amd.GradF * n)()
+    for i in range(n):
+        gs[i] = ssim_amd.GradF(a.ctypes.data, 1, a.shape[1])
+    return gs
+
+
+def _weights(w):
+    return None if w is None else (ctypes.c_double * len(w))(*w)
+
+
+def test_entry_points_are_exported(lib):
+    for name in ENTRY_POINTS:
+        assert hasattr(lib, name) and name in ssim_amd.C_SYMBOLS
+    for name in ("compute_msssimf", "compute_msssimf_batch"):
+        assert hasattr(ssim_amd, name)
+    for name in ("msssimf_device", "enqueue_msssimf", "enqueue_msssimf_grad"):
+        assert hasattr(ssim_amd.Context, name)
+    from ssim_amd import torch_ops
+    assert hasattr(torch_ops, "ms_ssim") and hasattr(torch_ops, "MSSSIMLoss")
+    assert lib.rmgr_ssim_hip_get_abi_version() == 6
+    with open(os.path.join(ROOT, "ssim_amd", "csrc", "exports.map")) as f:
+        assert "rmgr_ssim_*;" in f.read()
+
+
+@pytest.mark.parametrize("fn", ENTRY_POINTS)
+def test_every_einval_comes_before_the_device(lib, fn):
+    a = np.zeros((20, 30), np.float32)
+    b = np.zeros((20, 30), np.float32)
+    ga = np.zeros((20, 30), np.float32)
+    grad, enq = fn.endswith("_grad"), fn.endswith("enqueue_msssimf")
+    fake = ctypes.c_void_p(16)                                                                          # never dereferenced
+    fake_ctx = None if fn.endswith("_host") else ctypes.c_void_p(1)                                     # never dereferenced
+    out = fake if (grad or enq) else (ctypes.c_float * 4)()
+    E = errno.EINVAL
+    f = getattr(lib, fn)
+
+    def rc(count=1, params=None, r=1.0, scales=5, w=None, o=out, ctx=fake_ctx, grads=None, means=fake):
+        ps = _params(a, b, max(count, 1)) if params is None else params
+        if grad:
+            ga_, gb_ = (_grads(ga, max(count, 1)), None) if grads is None else grads
+            return f(ctx, count, ps, r, scales, _weights(w), means, o, ga_, gb_)
+        if enq:
+            return f(ctx, count, ps, r, scales, _weights(w), o, means)
+        return f(ctx, count, ps, r, scales, _weights(w), o, None)
+    assert rc(count=0) == E
+    if grad:
+        assert f(fake_ctx, 1, None, 1.0, 5, None, fake, out, _grads(ga), None) == E                      # params NULL
+    else:
+        assert f(fake_ctx, 1, None, 1.0, 5, None, out, fake if enq else None) == E
+    assert rc(o=None) == E                                                     # msssim / valuesDevice / gradOutDevice NULL
+    if grad or enq:
+        assert rc(means=None) == E                                             # scaleMeansDevice NULL
+    assert rc(params=_params(a, b, width=0)) == E
+    assert rc(params=_params(a, b, height=0)) == E
+    assert rc(params=_params(a, b, width=0x7FFF0001)) == E                     # above the kernels' limit
+    two = _params(a, b, 2)
+    two[1].width = 29
+    assert rc(count=2, params=two) == E                                        # sizes differ
+    two = _params(a, b, 2)
+    two[1].height = 19
+    assert rc(count=2, params=two) == E
+    bad = _params(a, b)
+    bad[0].imgA.topLeft = None
+    assert rc(params=bad) == E
+    bad = _params(a, b, 2)
+    bad[1].imgB.topLeft = None
+    assert rc(count=2, params=bad) == E
+    for off in (1, 2, 3):
+        bad = _params(a, b)
+        bad[0].imgA.topLeft = a.ctypes.data + off                              # not 4-byte aligned
+        assert rc(params=bad) == E
+        bad = _params(a, b, 2)
+        bad[1].imgB.topLeft = b.ctypes.data + off
+        assert rc(count=2, params=bad) == E
+    for r in (0.0, -1.0, float("inf"), float("-inf"), float("nan")):
+        assert rc(r=r) == E
+    # the multi-scale rules: scales, weights, no map
+    for scales in (0, 9, 100):
+        assert rc(scales=scales, w=[0.1] * max(scales, 1)) == E
+    for scales in (1, 4, 6, 8):
+        assert rc(scales=scales, w=None) == E                                  # NULL weights are Wang's five
+    for w in ([0.2, -0.1, 0.9], [0.2, float("nan"), 0.8], [float("inf"), 0.5, 0.5], [0.2, 0.3, float("-inf")]):
+        assert rc(scales=3, w=w) == E
+    m = np.zeros((20, 30), np.float32)
+    bad = _params(a, b, 2)
+    bad[1].ssimMap = m.ctypes.data
+    assert rc(count=2, params=bad) == E                                        # a map
+    if not fn.endswith("_host"):
+        assert rc(ctx=None) == E                                               # these entries need a context
+        assert rc(ctx=None, scales=3, w=[0.2, 0.3, 0.5], r=255.0) == E
+    if grad:
+        assert rc(grads=(None, None)) == E                                     # both gradient arrays NULL
+        g = _grads(ga, 2)
+        g[1].topLeft = None
+        assert rc(count=2, grads=(g, None)) == E and rc(count=2, grads=(None, g)) == E
+        g = _grads(ga)
+        g[0].topLeft = ga.ctypes.data + 2
+        assert rc(grads=(g, None)) == E and rc(grads=(_grads(ga), g)) == E
+
+
+def test_valid_call_without_a_device_fails_loudly(lib):
+    if ssim_amd.device_count() > 0:
+        v = ssim_amd.compute_msssimf(np.full((8, 8), 0.25, np.float32), np.full((8, 8), 0.25, np.float32), 1.0)
+        assert abs(float(v) - 1.0) < 1e-6
+        return
+    a = np.zeros((20, 30), np.float32)
+    out = (ctypes.c_float * 1)()
+    for r, scales, w in ((1.0, 5, None), (255.0, 1, [1.0]), (1000.0, 8, [0.125] * 8), (1.0, 3, [0.0, 0.0, 1.0])):
+        assert lib.rmgr_ssim_hip_compute_msssimf_host(None, 1, _params(a, a), r, scales, _weights(w), out, None) == errno.ENODEV
+    with pytest.raises(ssim_amd.SsimError):
+        ssim_amd.compute_msssimf(a, a, 1.0)
+    with pytest.raises(ssim_amd.SsimError):
+        ssim_amd.compute_msssimf_batch([(a, a), (a, a)], 1.0, per_scale=True)
+
+
+def test_torch_ops_refuses_what_it_documents_before_any_gpu_call():
+    import torch
+    from ssim_amd import torch_ops
+    x = torch.zeros(2, 3, 16, 16)
+    with pytest.raises(ValueError):
+        torch_ops.ms_ssim(x, x)                                                # CPU tensors
+    with pytest.raises(ValueError):
+        torch_ops.MSSSIMLoss()(x, x)
+    with pytest.raises(TypeError):
+        torch_ops.ms_ssim(x.double(), x.double())
+    with pytest.raises(TypeError):
+        torch_ops.ms_ssim(x, x.half())
+    with pytest.raises(TypeError):
+        torch_ops.ms_ssim(x.numpy(), x.numpy())
+    with pytest.raises(ValueError):
+        torch_ops.ms_ssim(x, torch.zeros(2, 3, 16, 15))
+    with pytest.raises(ValueError):
+        torch_ops.ms_ssim(torch.zeros(16), torch.zeros(16))
+    with pytest.raises(ValueError):
+        torch_ops.ms_ssim(x, x, data_range=0.0)
+    with pytest.raises(ValueError):
+        torch_ops.MSSSIMLoss(reduction="sum")
+    # scales and weights
+    for kw in (dict(scales=0), dict(scales=9, weights=[0.1] * 9), dict(scales=4), dict(scales=3, weights=[0.5, 0.5]),
+               dict(scales=2, weights=[0.5, -0.5]), dict(scales=2, weights=[0.5, float("nan")]), dict(scales=2, weights=[float("inf"), 0.5])):
+        with pytest.raises(ValueError):
+            torch_ops.MSSSIMLoss(**kw)
+    with pytest.raises(TypeError):
+        torch_ops.MSSSIMLoss(scales=2.0, weights=[0.5, 0.5])
+
+
+def test_import_stays_torch_free():
+    r = subprocess.run(["python3", "-c", "import sys; sys.path.insert(0, %r); import ssim_amd, ssim_amd.torch_ops; "
+                        "assert hasattr(ssim_amd.torch_ops, 'ms_ssim') and 'torch' not in sys.modules" % ROOT], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_multi_scale_float_kernels_keep_their_budgets():
+    """Build-time guard from the compiler's remarks, as tests/test_ssimf_cpu.py has for ssimf_kernels.hip: nothing spills; the strip
+    kernels keep three waves per SIMD (at most 168 VGPRs, LDS for 12 waves per CU); the gradient kernels two workgroups of 256 lanes per
+    CU (at most 128 VGPRs, at most 64 KiB of LDS per workgroup).  12 kernels: 2 strip, 6 gradient (cs / ssim form x A, B, both), the
+    pyramid step, the reduction, the product, the coefficients."""
+    src = os.path.join(ROOT, "ssim_amd", "csrc", "msssimf_kernels.hip")
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(src), "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    kernels = {}
+    name = None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            kernels[name] = {}
+        for key in ("VGPRs", "ScratchSize \\[bytes/lane\\]", "Occupancy \\[waves/SIMD\\]", "LDS Size \\[bytes/block\\]"):
+            m = re.search(r"remark:\s+" + key + r": (\d+)", line)
+            if m and name:
+                kernels[name][key.split(" ")[0]] = int(m.group(1))
+    strip = {k: v for k, v in kernels.items() if "msssimf_strip" in k}
+    grad = {k: v for k, v in kernels.items() if "msssimf_grad" in k}
+    assert len(strip) == 2 and len(grad) == 6 and len(kernels) == 12, sorted(kernels)
+    for k, v in kernels.items():
+        assert v["ScratchSize"] == 0, (k, v)
+    for k, v in strip.items():
+        assert v["VGPRs"] <= 168 and v["Occupancy"] >= 3 and v["LDS"] <= 13312, (k, v)
+    for k, v in grad.items():
+        assert v["VGPRs"] <= 128 and v["Occupancy"] >= 2 and v["LDS"] <= 65536, (k, v)
