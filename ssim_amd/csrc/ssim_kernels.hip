@@ -881,14 +881,26 @@ void ssim_strip2_kernel(const KArgs args)
             separable_rows_pair<ORDER_CENTRE_FIRST>(hab[0], hab[1], s0, s1, gf);
         }
         if constexpr (EARLY && !FAST && !HYB) {
+            // The twelve row sums (2 columns x S0..S5), TERM-major: the twelve products s0*K(0,j) first, then for i = 1..5
+            // the twelve multiply-adds of term i -- the order the reference's source has (src/ssim_fma.cpp:203-243).  Every
+            // sum keeps its own operation order (row_sum), so the bits are the same; what changes is that a link of one
+            // chain is followed by eleven independent instructions.  Listed chain by chain the compiler kept that order and
+            // ran all 72 packed instructions through one register pair, each link behind a hazard wait state (90 s_nop per
+            // two rows of the bit-exact loop; 16 now).  The fences keep the scheduler from serialising the terms again.
+            const f2 s[2][6] = {{ca[0], fa[0][0], fa[0][1], fa[0][2], fa[0][3], fa[0][4]}, {ca[1], fa[1][0], fa[1][1], fa[1][2], fa[1][3], fa[1][4]}};
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                sab[c][0] = row_sum<0, FUSED>(ca[c], fa[c][0], fa[c][1], fa[c][2], fa[c][3], fa[c][4]);
-                sab[c][1] = row_sum<1, FUSED>(ca[c], fa[c][0], fa[c][1], fa[c][2], fa[c][3], fa[c][4]);
-                sab[c][2] = row_sum<2, FUSED>(ca[c], fa[c][0], fa[c][1], fa[c][2], fa[c][3], fa[c][4]);
-                sab[c][3] = row_sum<3, FUSED>(ca[c], fa[c][0], fa[c][1], fa[c][2], fa[c][3], fa[c][4]);
-                sab[c][4] = row_sum<4, FUSED>(ca[c], fa[c][0], fa[c][1], fa[c][2], fa[c][3], fa[c][4]);
-                sab[c][5] = row_sum<5, FUSED>(ca[c], fa[c][0], fa[c][1], fa[c][2], fa[c][3], fa[c][4]);
+#pragma unroll
+                for (int j = 0; j < 6; ++j) sab[c][j] = s[c][0] * VT<f2>::splat(kc(0, j));
+            }
+#pragma unroll
+            for (int i = 1; i <= 5; ++i) {
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) sab[c][j] = mad<FUSED>(s[c][i], VT<f2>::splat(kc(i, j)), sab[c][j]);
+                }
             }
         }
     };
