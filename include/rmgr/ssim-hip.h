@@ -26,6 +26,8 @@
  *       of float32 images and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssimf, rmgr_ssim_hip_compute_ssimf_device / _host, rmgr_ssim_hip_enqueue_ssimf_grad   SSIM of float32
  *                                      samples and its gradient: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssimh, rmgr_ssim_hip_compute_ssimh_device / _host, rmgr_ssim_hip_enqueue_ssimh_grad   SSIM of float16 /
+ *                                      bfloat16 samples and its gradient: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -547,6 +549,70 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_grad(rmgr_ssim_hip_Context* ctx, rmgr
                                                 float dataRange, rmgr_uint32_t scales, const double* weights,
                                                 const double* scaleMeansDevice, const float* gradOutDevice,
                                                 const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
+
+/*
+ * SSIM of `count` pairs of float16 or bfloat16 images of one size, and its gradient (what a model produces under mixed precision; SSIM
+ * as a training loss without a float32 copy of the images or of the gradient).  No reference counterpart: the definition is
+ * rmgr_ssim_hip_enqueue_ssimf's on the samples widened to float32, so tests/ssimf_model.py restates it as well; tests/halfmodel.py
+ * restates the two encodings.  Additions only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ *   Samples  16-bit, host byte order (rmgr_ssim_hip_uint16_t), in ONE encoding per call: sampleType RMGR_SSIM_HIP_SAMPLE_F16 (IEEE
+ *            binary16) or RMGR_SSIM_HIP_SAMPLE_BF16 (bfloat16: the upper half of a float32).  Each sample is widened to float32
+ *            EXACTLY: float16 subnormals become the float32 normals they equal (they are not flushed), a bfloat16 sample is the
+ *            float32 whose upper 16 bits it is, NaN and Inf stay NaN and Inf.  The widened samples are used as stored, as for ssimf.
+ *   Data range, window, per pixel, global, constants  as rmgr_ssim_hip_enqueue_ssimf, word for word, on the widened planes: dataRange
+ *            finite and > 0, C1 = float((0.01 R) * (0.01 R)), C2 = float((0.03 R) * (0.03 R)), the clamped 11-tap window G, the
+ *            per-pixel formula, S_i = the fp64 sum of the per-pixel values divided by double(W) * double(H).
+ *   Inputs   params[0 .. count-1] (rmgr_ssim_hip_Params16): width, height (the same for every pair), imgA / imgB with any step / stride
+ *            in SAMPLES (not bytes), negative ones included; ssimMap NULL (no map) or a FLOAT32 map with ssimStep / ssimStride in
+ *            floats -- per pair.
+ *   Arithmetic  ssimf's: fp32 with centred samples, the centre of the 128 columns from x0 = 128 k on being A's and B's WIDENED sample
+ *            at (min(x0 + 64, W - 1), (H - 1) / 2) when its magnitude is at most dataRange, else 0 (a NaN counts as `else`); the same
+ *            64-column cells and the same 32 x 32 gradient tiles at absolute positions.  Value, map and every per-image sum have the
+ *            BITS rmgr_ssim_hip_enqueue_ssimf / _compute_ssimf_* give on the widened planes.  The context's mode does not change this
+ *            path.
+ *   Gradient  the float32 value rmgr_ssim_hip_enqueue_ssimf_grad would store for the widened planes, rounded ONCE, to nearest-even, into
+ *            the sample encoding of the inputs.  float16 results below the normal range are kept as subnormals (not flushed), overflow
+ *            gives +-Inf; NaN stays NaN, its payload is not specified.  gOut stays float32, so a loss scale that arrives in gOut is
+ *            applied before the single rounding.  The gradient of a mean is of order gOut / (W H): in float16 it underflows for all
+ *            but small images unless gOut carries a loss scale.  float32 gradient planes for 16-bit inputs are not offered.
+ *   Determinism  everything ssimf promises: the same bits -- value, map, gradient -- alone or anywhere in a batch of any size, after any
+ *            internal sub-batch split, through every entry point, on every call, with both gradients or one, and as a view with
+ *            negative step or stride, or interleaved samples, compared with the same pixels stored contiguously.  One writer per
+ *            gradient pixel, no atomics.
+ *
+ * _enqueue_ssimh: device pointers; asynchronous on the context's stream, never waits for the host; writes each pair's fp64 SUM of
+ *            per-pixel values to sumsDevice[i] (device memory).  The mean is sum / (double(W) * double(H)).
+ * _compute_ssimh_device: device pointers; blocks; ssim: count floats in host memory.
+ * _compute_ssimh_host: host pointers (ctx NULL: a default context, as rmgr_ssim_hip_compute_ssim_host).  The images are staged to
+ *            the device and each map is copied back at its own step and stride; a batch runs in sub-batches that keep the device
+ *            scratch under about 1 GB -- results do not depend on the split.
+ * _enqueue_ssimh_grad: everything device-resident, asynchronous on the context's stream, no host synchronisation.  gradOutDevice:
+ *            count FLOAT32 values in DEVICE memory (dLoss/dS_i).  gradA / gradB: arrays of count rmgr_ssim_hip_GradH (host memory) that
+ *            describe where dLoss/dA and dLoss/dB of each pair go (16-bit device planes in the inputs' encoding, step / stride in
+ *            samples, negatives included); either array may be NULL (that gradient is not computed), not both.  Gradients are WRITTEN,
+ *            not accumulated.  A gradient plane must not overlap an input plane or another gradient plane: this is not checked.
+ *            params[i].ssimMap is ignored.  One fused launch recomputes the statistics: no scratch memory beyond the descriptors.
+ * EINVAL: count == 0; a NULL params, ssim, image pointer, sumsDevice, gradOutDevice or gradient plane; both gradient arrays NULL; a
+ *         zero or differing width or height, or one above 0x7FFF0000; a dataRange that is not finite or not > 0; a sampleType that is
+ *         neither of the two constants; an image or gradient pointer that is not 2-byte aligned; a NULL ctx for anything but _host --
+ *         all checked before any device is touched.  ENODEV: no device.
+ */
+#define RMGR_SSIM_HIP_SAMPLE_F16  0   /* IEEE 754 binary16 */
+#define RMGR_SSIM_HIP_SAMPLE_BF16 1   /* bfloat16 */
+typedef struct rmgr_ssim_hip_GradH {
+    rmgr_ssim_hip_uint16_t* topLeft;
+    ptrdiff_t step, stride;                     /* in samples */
+} rmgr_ssim_hip_GradH;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                         rmgr_uint32_t sampleType, float dataRange, double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                              rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                              rmgr_uint32_t sampleType, float dataRange, const float* gradOutDevice,
+                                              const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

@@ -72,6 +72,15 @@ class GradF(ctypes.Structure):
     _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
 
 
+class GradH(ctypes.Structure):
+    """rmgr_ssim_hip_GradH: one float16 / bfloat16 gradient plane in device memory; step and stride count 16-bit samples."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
+
+
+SAMPLE_F16, SAMPLE_BF16 = 0, 1      # RMGR_SSIM_HIP_SAMPLE_F16 / _BF16
+_SAMPLE_TYPES = {"float16": SAMPLE_F16, "bfloat16": SAMPLE_BF16}
+
+
 class Plan(ctypes.Structure):
     _fields_ = [("structSize", ctypes.c_uint32), ("stripWidth", ctypes.c_uint32), ("stripRows", ctypes.c_uint32), ("stripsX", ctypes.c_uint32),
                 ("stripsY", ctypes.c_uint32), ("wavefronts", ctypes.c_uint32), ("waveSlots", ctypes.c_uint32), ("earlyRowSums", ctypes.c_uint32),
@@ -124,6 +133,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssim16", "rmgr_ssim_hip_compute_ssim16_device", "rmgr_ssim_hip_compute_ssim16_host",
     "rmgr_ssim_hip_enqueue_ssimf", "rmgr_ssim_hip_compute_ssimf_device", "rmgr_ssim_hip_compute_ssimf_host", "rmgr_ssim_hip_enqueue_ssimf_grad",
     "rmgr_ssim_hip_enqueue_msssimf", "rmgr_ssim_hip_compute_msssimf_device", "rmgr_ssim_hip_compute_msssimf_host", "rmgr_ssim_hip_enqueue_msssimf_grad",
+    "rmgr_ssim_hip_enqueue_ssimh", "rmgr_ssim_hip_compute_ssimh_device", "rmgr_ssim_hip_compute_ssimh_host", "rmgr_ssim_hip_enqueue_ssimh_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -204,6 +214,10 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_compute_ssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssimf_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
+        "rmgr_ssim_hip_enqueue_ssimh": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, vp],
+        "rmgr_ssim_hip_compute_ssimh_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssimh_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssimh_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
         "rmgr_ssim_hip_enqueue_msssimf": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
         "rmgr_ssim_hip_compute_msssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
@@ -545,6 +559,76 @@ def compute_ssimf_batch(pairs, data_range, ctx=None):
     return np.array(out[:n], np.float32)
 
 
+def sample_type_code(sample_type):
+    """RMGR_SSIM_HIP_SAMPLE_F16 / _BF16 of "float16" / "bfloat16" (or of the code itself).  ValueError: anything else."""
+    if isinstance(sample_type, str) and sample_type in _SAMPLE_TYPES:
+        return _SAMPLE_TYPES[sample_type]
+    if not isinstance(sample_type, (str, bool)) and sample_type in (SAMPLE_F16, SAMPLE_BF16):
+        return int(sample_type)
+    raise ValueError("sample_type must be 'float16' or 'bfloat16', got %r" % (sample_type,))
+
+
+def _h_view(x, sample_type):
+    """(host-byte-order uint16 view of an H x W array of 16-bit float samples, sample type code).  np.float16 arrays are float16;
+    np.uint16 arrays hold the bit patterns of the encoding `sample_type` names (numpy has no bfloat16).  TypeError: another dtype, or a
+    float16 array declared bfloat16; ValueError: a uint16 array without a sample_type, or an unknown one."""
+    if not isinstance(x, np.ndarray) or x.ndim != 2:
+        raise TypeError("H x W numpy array of float16 or uint16 expected")
+    if x.dtype.kind == "f" and x.dtype.itemsize == 2:
+        code = SAMPLE_F16 if sample_type is None else sample_type_code(sample_type)
+        if code != SAMPLE_F16:
+            raise TypeError("a float16 array cannot be read as bfloat16: pass the bit patterns as uint16")
+        if not x.dtype.isnative:
+            x = x.astype(np.float16)
+        return _u16_view(x.view(np.uint16)), code
+    if x.dtype.kind == "u" and x.dtype.itemsize == 2:
+        if sample_type is None:
+            raise ValueError("uint16 arrays need sample_type='bfloat16' or 'float16'")
+        return _u16_view(x), sample_type_code(sample_type)
+    raise TypeError("float16 or uint16 arrays expected, got %s" % x.dtype)
+
+
+def _h_pair(a, b, sample_type):
+    (a, ta), (b, tb) = _h_view(a, sample_type), _h_view(b, sample_type)
+    if ta != tb:
+        raise TypeError("the two images differ in sample type")
+    if a.shape != b.shape:
+        raise ValueError("shapes differ: %s and %s" % (a.shape, b.shape))
+    return a, b, ta
+
+
+def compute_ssimh(a, b, data_range, sample_type=None, want_map=False, ctx=None):
+    """SSIM of two H x W host arrays of float16 or bfloat16 samples at `data_range` (any strides numpy can express, negative ones
+    included) through rmgr_ssim_hip_compute_ssimh_host.  np.float16 arrays select float16; np.uint16 arrays carry bit patterns and
+    need sample_type="bfloat16" or "float16".  Returns (float32 value, H x W float32 map or None)."""
+    a, b, code = _h_pair(a, b, sample_type)
+    h, w = a.shape
+    m = np.empty((h, w), np.float32) if want_map else None
+    params = (Params16 * 1)()
+    params[0] = _params16_of(a, b, m.ctypes.data if want_map else None)
+    out = (ctypes.c_float * 1)()
+    _check("rmgr_ssim_hip_compute_ssimh_host", load_library().rmgr_ssim_hip_compute_ssimh_host(
+        ctx.handle if ctx is not None else None, 1, params, code, data_range, out))
+    return np.float32(out[0]), m
+
+
+def compute_ssimh_batch(pairs, data_range, sample_type=None, ctx=None):
+    """compute_ssimh() of many host pairs of one size and one sample type in one call (no maps): a float32 array."""
+    pairs = [_h_pair(a, b, sample_type) for a, b in pairs]
+    n = len(pairs)
+    codes = set(t for _, _, t in pairs)
+    if len(codes) > 1:
+        raise TypeError("the pairs differ in sample type")
+    code = codes.pop() if codes else sample_type_code("float16" if sample_type is None else sample_type)
+    params = (Params16 * max(n, 1))()
+    for i, (a, b, _) in enumerate(pairs):
+        params[i] = _params16_of(a, b)
+    out = (ctypes.c_float * max(n, 1))()
+    _check("rmgr_ssim_hip_compute_ssimh_host", load_library().rmgr_ssim_hip_compute_ssimh_host(
+        ctx.handle if ctx is not None else None, n, params, code, data_range, out))
+    return np.array(out[:n], np.float32)
+
+
 def _weights_array(weights):
     """The `weights` argument of the multi-scale entry points: NULL (Wang's five) or a double array."""
     if weights is None:
@@ -727,6 +811,25 @@ class Context(object):
         """rmgr_ssim_hip_enqueue_ssimf_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs into the planes the GradF arrays
         grad_a / grad_b describe (None: not wanted), from `count` floats dLoss/dS_i in device memory; asynchronous, written not accumulated."""
         _check("rmgr_ssim_hip_enqueue_ssimf_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_grad(self.handle, count, params_array, data_range, grad_out_dev_ptr, grad_a, grad_b))
+
+    def ssimh_device(self, params_array, count, data_range, sample_type):
+        """SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_ssimh_device: a
+        float32 array."""
+        out = (ctypes.c_float * max(count, 1))()
+        _check("rmgr_ssim_hip_compute_ssimh_device", self.lib.rmgr_ssim_hip_compute_ssimh_device(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, out))
+        return np.array(out[:count], np.float32)
+
+    def enqueue_ssimh(self, params_array, count, data_range, sample_type, sums_dev_ptr):
+        """rmgr_ssim_hip_enqueue_ssimh: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        _check("rmgr_ssim_hip_enqueue_ssimh", self.lib.rmgr_ssim_hip_enqueue_ssimh(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, sums_dev_ptr))
+
+    def enqueue_ssimh_grad(self, params_array, count, data_range, sample_type, grad_out_dev_ptr, grad_a=None, grad_b=None):
+        """rmgr_ssim_hip_enqueue_ssimh_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs into the 16-bit planes the GradH
+        arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values; asynchronous, no host synchronisation."""
+        _check("rmgr_ssim_hip_enqueue_ssimh_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_grad(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_dev_ptr, grad_a, grad_b))
 
     def msssimf_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False):
         """MS-SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_msssimf_device: a float32

@@ -6,6 +6,7 @@
 // no gfx950 device is usable every entry point fails loudly with ENODEV.
 #include "ssim_context.h"
 #include "msssim_kernels.h"
+#include "ssimh_kernels.h"
 
 #include <cmath>
 #include <condition_variable>
@@ -1395,6 +1396,256 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uin
         HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(ssim_hip::launch_ssimf_grad(W, H, n, reinterpret_cast<const PairFDesc*>(s->dev.get()),
                                             reinterpret_cast<const GradFDesc*>(s->dev.get() + pair_bytes), gradOutDevice + i0, dataRange, which, c->stream));
+        HIP_TRY(hipEventRecord(s->used, c->stream));
+        s->pending = true;
+        i0 += n;
+    }
+    return 0;
+}
+
+// ---- SSIM of float16 / bfloat16 samples and its gradient (rmgr_ssim_hip_enqueue_ssimh, _compute_ssimh_*, _enqueue_ssimh_grad) -------------------
+// The definition is in include/rmgr/ssim-hip.h, the kernels in ssimh_kernels.hip.  The host flow is the ssimf one with 2-byte samples; it
+// runs on the float path's descriptor ring, partials and pinned sums (one stream, stream order), so the enqueue forms never wait for the
+// host either.  Sums run over fixed cells and gradient pixels over fixed tiles: neither the sub-batches nor the launch a pair lands in
+// change a bit.
+namespace {
+
+using ssim_hip::PairHDesc;
+using ssim_hip::GradHDesc;
+
+// Every check the entry points share, before any device is touched.
+int ssimh_validate(rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params, rmgr_uint32_t sampleType, float dataRange, const void* out)
+{
+    if (count == 0 || params == NULL || out == NULL) return EINVAL;
+    if (sampleType != RMGR_SSIM_HIP_SAMPLE_F16 && sampleType != RMGR_SSIM_HIP_SAMPLE_BF16) return EINVAL;
+    if (!(dataRange > 0.0f) || !std::isfinite(dataRange)) return EINVAL;
+    const uint32_t W = params[0].width, H = params[0].height;
+    if (W == 0 || H == 0 || W > ssim_hip::kSHMaxDim || H > ssim_hip::kSHMaxDim) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i) {
+        const rmgr_ssim_hip_Params16& p = params[i];
+        if (p.width != W || p.height != H) return EINVAL;
+        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
+        if (((uintptr_t)p.imgA.topLeft & 1u) || ((uintptr_t)p.imgB.topLeft & 1u)) return EINVAL;
+    }
+    if (ssim_hip::ssimh_max_count(W, H) == 0) return EINVAL;
+    return 0;
+}
+
+int ssimh_type(rmgr_uint32_t sampleType) { return sampleType == RMGR_SSIM_HIP_SAMPLE_BF16 ? ssim_hip::kSHTypeBF16 : ssim_hip::kSHTypeF16; }
+
+PairHDesc make_desch(const rmgr_ssim_hip_Params16& p, bool with_map)
+{
+    PairHDesc d;
+    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride;
+    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride;
+    const bool m = with_map && p.ssimMap;
+    d.map = m ? p.ssimMap : NULL;
+    d.map_step = m ? p.ssimStep : 0;
+    d.map_stride = m ? p.ssimStride : 0;
+    return d;
+}
+
+uint64_t ssimh_partials_per_pair(uint32_t W, uint32_t H)
+{
+    const ssim_hip::GeometryH g = ssim_hip::planh(W, H, 1, 0);
+    return g.cells_per_image() * sizeof(double);
+}
+
+// Enqueues n pairs (descriptors in host memory, images on the device) on the context's stream: descriptor upload, strip kernel,
+// reduction into sums[0 .. n-1] (device or pinned host memory).  n <= ssimh_max_count and its partials within the cap.
+int ssimh_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const PairHDesc* d, uint32_t W, uint32_t H, int type, float range, double* sums)
+{
+    int rc;
+    rmgr_ssim_hip_Context_::SfSlot* s;
+    if ((rc = ssimf_slot(c, n * sizeof(PairHDesc), s))) return rc;
+    const ssim_hip::GeometryH geo = ssim_hip::planh(W, H, n, c->cu_count);
+    if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_image() * n)))) return rc;
+    bool map = false, unit = (W % 2) == 0, wide = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        map = map || d[i].map != NULL;
+        unit = unit && (d[i].map == NULL || d[i].map_step == 1);
+        wide = wide || !ssim_hip::fitsh_narrow(d[i]);
+    }
+    memcpy(s->pin.get(), d, n * sizeof(PairHDesc));
+    HIP_TRY(hipMemcpyAsync(s->dev, s->pin, n * sizeof(PairHDesc), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ssim_hip::launch_ssimh(geo, reinterpret_cast<const PairHDesc*>(s->dev.get()), type, map, unit, wide, range, c->xcd_count, c->sf_partials, sums, c->stream));
+    HIP_TRY(hipEventRecord(s->used, c->stream));
+    s->pending = true;
+    return 0;
+}
+
+// Pairs of params[i0 ..] that one sub-batch takes: at least one; within the launch limit and, with the staged images and maps of host
+// pointers, kSFScratchCap of device scratch.
+uint32_t ssimh_take(const rmgr_ssim_hip_Params16* params, uint32_t i0, uint32_t count, bool stage, uint64_t& staged)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const uint64_t part = ssimh_partials_per_pair(W, H);
+    const uint32_t nmax = ssim_hip::ssimh_max_count(W, H);
+    uint32_t n = 0;
+    staged = 0;
+    while (i0 + n < count && n < nmax) {
+        uint64_t bytes = 0;
+        if (stage) {
+            const rmgr_ssim_hip_Params16& p = params[i0 + n];
+            int64_t lo, hi;
+            extent16(p.imgA, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 2 + 63) & ~uint64_t(63);
+            extent16(p.imgB, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 2 + 63) & ~uint64_t(63);
+            if (p.ssimMap) bytes += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
+        }
+        if (n > 0 && part * (n + 1) + staged + bytes > kSFScratchCap) break;
+        staged += bytes;
+        ++n;
+    }
+    return n;
+}
+
+// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the images are copied
+// (each image's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own step and stride.
+int ssimh_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params16* params, int type, float range, float* ssim, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const double px = (double)W * (double)H;
+    int rc;
+    if ((rc = c->sf_sums_pin.grow(count))) return rc;
+    try {
+        std::vector<PairHDesc> d;
+        std::vector<float> back;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = ssimh_take(params, i0, count, stage, staged);
+            d.resize(n);
+            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
+            uint64_t off = 0;
+            std::vector<uint64_t> map_off(n, 0);
+            for (uint32_t i = 0; i < n; ++i) {
+                const rmgr_ssim_hip_Params16& p = params[i0 + i];
+                d[i] = make_desch(p, true);
+                if (!stage) continue;
+                for (int k = 0; k < 2; ++k) {
+                    const rmgr_ssim_hip_Img16& im = k ? p.imgB : p.imgA;
+                    int64_t lo, hi;
+                    extent16(im, W, H, lo, hi);
+                    const size_t bytes = (size_t)(hi - lo + 1) * 2;
+                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
+                    (k ? d[i].b : d[i].a) = reinterpret_cast<const uint16_t*>(c->stage_a + off) - lo;
+                    off += (bytes + 63) & ~uint64_t(63);
+                }
+                if (p.ssimMap) {
+                    map_off[i] = off;
+                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
+                    d[i].map_step = 1; d[i].map_stride = W;
+                    off += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
+                }
+            }
+            if ((rc = ssimh_enqueue(c, n, &d[0], W, H, type, range, c->sf_sums_pin + i0))) return rc;
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (uint32_t i = 0; i < n && stage; ++i) {
+                const rmgr_ssim_hip_Params16& p = params[i0 + i];
+                if (!p.ssimMap) continue;
+                const float* src = reinterpret_cast<const float*>(c->stage_a + map_off[i]);
+                if (p.ssimStep == 1 && p.ssimStride == (ptrdiff_t)W) {
+                    HIP_TRY(hipMemcpy(p.ssimMap, src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+                    continue;
+                }
+                back.resize((size_t)W * H);
+                HIP_TRY(hipMemcpy(&back[0], src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+                for (uint32_t y = 0; y < H; ++y) {
+                    float* row = p.ssimMap + (ptrdiff_t)y * p.ssimStride;
+                    const float* sr = &back[(size_t)y * W];
+                    for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = sr[x];
+                }
+            }
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->sf_sums_pin[i] / px);
+    return 0;
+}
+
+} // namespace
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                         rmgr_uint32_t sampleType, float dataRange, double* sumsDevice) RMGR_NOEXCEPT
+{
+    int rc = ssimh_validate(count, params, sampleType, dataRange, sumsDevice);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    try {
+        std::vector<PairHDesc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = ssimh_take(params, i0, count, false, staged);
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) d[i] = make_desch(params[i0 + i], true);
+            if ((rc = ssimh_enqueue(c, n, &d[0], params[0].width, params[0].height, ssimh_type(sampleType), dataRange, sumsDevice + i0))) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return ssimh_blocking(c, count, params, ssimh_type(sampleType), dataRange, ssim, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                              rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    c = lease.c;
+    USE_DEVICE(c);
+    return ssimh_blocking(c, count, params, ssimh_type(sampleType), dataRange, ssim, true);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                              rmgr_uint32_t sampleType, float dataRange, const float* gradOutDevice,
+                                              const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
+{
+    int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutDevice);
+    if (rc) return rc;
+    if (gradA == NULL && gradB == NULL) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const rmgr_ssim_hip_GradH* g = k ? gradB : gradA;
+            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 1u))) return EINVAL;
+        }
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
+    const uint32_t nmax = ssim_hip::ssimh_max_count(W, H);
+    for (uint32_t i0 = 0; i0 < count;) {
+        const uint32_t n = std::min(count - i0, nmax);
+        rmgr_ssim_hip_Context_::SfSlot* s;
+        const size_t pair_bytes = n * sizeof(PairHDesc), bytes = pair_bytes + n * sizeof(GradHDesc);
+        if ((rc = ssimf_slot(c, bytes, s))) return rc;
+        PairHDesc* pd = reinterpret_cast<PairHDesc*>(s->pin.get());
+        GradHDesc* gd = reinterpret_cast<GradHDesc*>(s->pin.get() + pair_bytes);
+        for (uint32_t i = 0; i < n; ++i) {
+            pd[i] = make_desch(params[i0 + i], false);
+            GradHDesc g = {NULL, 0, 0, NULL, 0, 0};
+            if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
+            if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
+            gd[i] = g;
+        }
+        HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(ssim_hip::launch_ssimh_grad(W, H, n, reinterpret_cast<const PairHDesc*>(s->dev.get()),
+                                            reinterpret_cast<const GradHDesc*>(s->dev.get() + pair_bytes), ssimh_type(sampleType),
+                                            gradOutDevice + i0, dataRange, which, c->stream));
         HIP_TRY(hipEventRecord(s->used, c->stream));
         s->pending = true;
         i0 += n;

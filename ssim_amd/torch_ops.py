@@ -1,4 +1,5 @@
-"""SSIM and multi-scale SSIM of float32 tensors as differentiable PyTorch operations, on the library's fused gfx950 kernels.
+"""SSIM of float32, float16 and bfloat16 tensors and multi-scale SSIM of float32 tensors as differentiable PyTorch operations, on the
+library's fused gfx950 kernels.
 
     from ssim_amd.torch_ops import ssim, SSIMLoss, ms_ssim, MSSSIMLoss
     loss = 0.8 * (x - y).abs().mean() + 0.2 * SSIMLoss()(x, y)      # x, y: (N, C, H, W) float32 on the GPU
@@ -9,6 +10,17 @@ ssim(x, y, data_range) is the per-plane mean of the definition in include/rmgr/s
 rmgr_ssim_hip_enqueue_ssimf_grad; ms_ssim(x, y, data_range, scales, weights) is rmgr_ssim_hip_enqueue_msssimf and its backward
 rmgr_ssim_hip_enqueue_msssimf_grad.  Everything is enqueued on torch.cuda.current_stream() of the tensors' device through a Context cached
 per (device, stream); neither forward nor backward waits for the host.  There is no eager fall-back: without the library this raises.
+
+float16 and bfloat16 (ssim and SSIMLoss only).  x and y both float16 or both bfloat16 run rmgr_ssim_hip_enqueue_ssimh and its backward
+rmgr_ssim_hip_enqueue_ssimh_grad: the samples are read as they are (2 B/px), the result is float32 per plane at every input dtype (a loss
+of 1 - 0.98 has no business in 8 significant bits), and the gradient comes back in the inputs' dtype, written by the kernel into a 2 B/px
+tensor with one rounding and no float32 intermediate.  Two things to know:
+  * inside torch.autocast the function takes its tensors as they come and is not itself autocast: a conv's bfloat16 output is read as
+    bfloat16, a float32 tensor as float32, and a mixed pair is a TypeError, not a silent cast;
+  * with float16 the gradient of a mean SSIM is of order 1 / (W H) and underflows without torch.amp.GradScaler.  With a scaled loss
+    the scale arrives in grad_out, which stays float32, and is applied before the single rounding: the result is round(scale * g), not
+    scale * round(g).
+ms_ssim and MSSSIMLoss keep refusing 16-bit tensors (TypeError): that is the follow-up, and needs only scale 0's loads and stores.
 
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
@@ -43,12 +55,20 @@ def _context(device, stream):
     return ent[0]
 
 
-def _check(x, y, data_range):
-    """The documented errors, before any GPU call.  Returns data_range as a float."""
+def _sample_type(torch, dtype):
+    """None for float32, the library's sample type code for float16 / bfloat16."""
+    return {torch.float16: api.SAMPLE_F16, torch.bfloat16: api.SAMPLE_BF16}.get(dtype)
+
+
+def _check(x, y, data_range, half=False):
+    """The documented errors, before any GPU call.  Returns data_range as a float.  half: float16 and bfloat16 pairs are taken too."""
     import torch
     if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
         raise TypeError("ssim: x and y must be torch tensors")
-    if x.dtype != torch.float32 or y.dtype != torch.float32:
+    if half:
+        if x.dtype != y.dtype or x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError("ssim: two float32, two float16 or two bfloat16 tensors expected, got %s and %s" % (x.dtype, y.dtype))
+    elif x.dtype != torch.float32 or y.dtype != torch.float32:
         raise TypeError("ssim: float32 tensors expected, got %s and %s" % (x.dtype, y.dtype))
     if x.dim() < 2:
         raise ValueError("ssim: tensors of shape (..., H, W) expected, got %d dimension(s)" % x.dim())
@@ -78,20 +98,23 @@ def _params(x, y):
     h, w = x.shape[-2], x.shape[-1]
     ox, oy = _plane_offsets(x), _plane_offsets(y)
     n = len(ox)
-    params = (api.ParamsF * max(n, 1))()
+    es = x.element_size()                      # 4: ParamsF; 2 (float16, bfloat16): Params16 -- steps and strides count samples in both
+    make, params = (api.make_params_f, (api.ParamsF * max(n, 1))()) if es == 4 else (api.make_params16, (api.Params16 * max(n, 1))())
     px, py = x.data_ptr(), y.data_ptr()
     xs, xr, ys, yr = x.stride(-1), x.stride(-2), y.stride(-1), y.stride(-2)
     for i in range(n):
-        params[i] = api.make_params_f(w, h, px + 4 * ox[i], xs, xr, py + 4 * oy[i], ys, yr)
+        params[i] = make(w, h, px + es * ox[i], xs, xr, py + es * oy[i], ys, yr)
     return params, n
 
 
 def _grad_planes(g, n, h, w):
-    """GradF array over the n contiguous planes of g."""
-    arr = (api.GradF * max(n, 1))()
+    """GradF (float32) or GradH (float16, bfloat16) array over the n contiguous planes of g."""
+    es = g.element_size()
+    cls = api.GradF if es == 4 else api.GradH
+    arr = (cls * max(n, 1))()
     base = g.data_ptr()
     for i in range(n):
-        arr[i] = api.GradF(base + 4 * i * h * w, 1, w)
+        arr[i] = cls(base + es * i * h * w, 1, w)
     return arr
 
 
@@ -108,7 +131,11 @@ def _make_function():
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
-                _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr())
+                st = _sample_type(torch, x.dtype)
+                if st is None:
+                    _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr())
+                else:
+                    _context(x.device, work).enqueue_ssimh(params, n, data_range, st, sums.data_ptr())
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
@@ -125,15 +152,19 @@ def _make_function():
                 return None, None, None
             params, n = _params(x, y)
             g = grad_out.to(torch.float32).reshape(-1).contiguous()
-            gx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_x else None
-            gy = torch.empty(y.shape, dtype=torch.float32, device=y.device) if want_y else None
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
+            gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
             if n:
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
-                _context(x.device, work).enqueue_ssimf_grad(params, n, ctx.data_range, g.data_ptr(),
-                                                            _grad_planes(gx, n, h, w) if want_x else None,
-                                                            _grad_planes(gy, n, h, w) if want_y else None)
+                st = _sample_type(torch, x.dtype)
+                ga = _grad_planes(gx, n, h, w) if want_x else None
+                gb = _grad_planes(gy, n, h, w) if want_y else None
+                if st is None:
+                    _context(x.device, work).enqueue_ssimf_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb)
+                else:
+                    _context(x.device, work).enqueue_ssimh_grad(params, n, ctx.data_range, st, g.data_ptr(), ga, gb)
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None
@@ -142,19 +173,22 @@ def _make_function():
 
 
 def ssim(x, y, data_range=1.0):
-    """Per-plane SSIM of two float32 GPU tensors of identical shape (..., H, W), any strides (each plane is addressed in place, no copy):
-    a float32 tensor of shape x.shape[:-2].  Differentiable with respect to x, y or both; the gradient is computed only for the inputs
-    that need it.  TypeError: not float32 tensors.  ValueError: CPU tensors, differing shapes or devices, fewer than 2 dimensions,
-    empty planes, a data_range that is not finite and > 0."""
+    """Per-plane SSIM of two GPU tensors of identical shape (..., H, W), both float32, both float16 or both bfloat16, any strides (each
+    plane is addressed in place, no copy): a float32 tensor of shape x.shape[:-2] at every input dtype.  Differentiable with respect to
+    x, y or both; the gradient is computed only for the inputs that need it and has the inputs' dtype (float16 and bfloat16: the
+    float32 value rounded once; see the top of this file for autocast and loss scaling).  TypeError: not tensors, mixed dtypes, any
+    other dtype.  ValueError: CPU tensors, differing shapes or devices, fewer than 2 dimensions, empty planes, a data_range that is not
+    finite and > 0."""
     global _function
-    r = _check(x, y, data_range)
+    r = _check(x, y, data_range, half=True)
     if _function is None:
         _function = _make_function()
     return _function.apply(x, y, r)
 
 
 class SSIMLoss(object):
-    """1 - ssim(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per plane).  A plain callable: it has no parameters."""
+    """1 - ssim(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per plane), float32 whatever the inputs' dtype (float32,
+    float16 or bfloat16, as ssim()).  A plain callable: it has no parameters."""
 
     def __init__(self, data_range=1.0, reduction="mean"):
         if reduction not in ("mean", "none"):
@@ -237,7 +271,8 @@ def ms_ssim(x, y, data_range=1.0, scales=5, weights=None):
     place, no copy): a float32 tensor of shape x.shape[:-2].  weights None: Wang's five (scales must be 5); else `scales` finite weights
     >= 0.  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that need it, from x, y and the
     (planes, scales, 2) float64 per-scale means the forward keeps.  TypeError / ValueError as ssim(), plus ValueError for scales outside
-    1 .. 8, a wrong number of weights, a negative or non-finite weight (TypeError: scales is not an int)."""
+    1 .. 8, a wrong number of weights, a negative or non-finite weight (TypeError: scales is not an int).  float16 and bfloat16 tensors
+    are refused (TypeError) -- unlike ssim(); taking them needs only scale 0's loads and stores and is the follow-up."""
     global _ms_function
     r = _check(x, y, data_range)
     scales, w = _check_scales(scales, weights)
@@ -248,7 +283,7 @@ def ms_ssim(x, y, data_range=1.0, scales=5, weights=None):
 
 class MSSSIMLoss(object):
     """1 - ms_ssim(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per plane).  A plain callable: it
-    has no parameters."""
+    has no parameters.  float32 tensors only, as ms_ssim()."""
 
     def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean"):
         if reduction not in ("mean", "none"):
