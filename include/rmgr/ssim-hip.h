@@ -28,6 +28,8 @@
  *                                      samples and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssimh, rmgr_ssim_hip_compute_ssimh_device / _host, rmgr_ssim_hip_enqueue_ssimh_grad   SSIM of float16 /
  *                                      bfloat16 samples and its gradient: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssimf_map_grad, rmgr_ssim_hip_enqueue_ssimh_map_grad   gradient of the SSIM MAP for a per-pixel upstream
+ *                                      gradient: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -613,6 +615,53 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssimh_host(rmgr_ssim_hip_Context* ctx, rmgr_u
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
                                               rmgr_uint32_t sampleType, float dataRange, const float* gradOutDevice,
                                               const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
+
+/*
+ * Gradient of the SSIM map: dLoss/da and dLoss/db of `count` pairs for an upstream gradient given PER PIXEL (a weighted or masked mean,
+ * a per-pixel combination with L1 and a minimum over views, sums over boxes -- any loss that is a function of the map
+ * rmgr_ssim_hip_enqueue_ssimf / _ssimh write through params[i].ssimMap, not of its plain mean).  No reference counterpart:
+ * tests/ssimw_model.py restates it in float64.  Additions only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ * It is the definition of rmgr_ssim_hip_enqueue_ssimf_grad with ONE change:
+ *   Input    per pair a float32 plane gMap_i(p) = dLoss/dssim_i(p) in place of the scalar gOut[i]: k(p) = gMap_i(p).  There is no
+ *            division by W H.
+ *   Gradient  dLoss/da = Gt(k d_mu) + 2 a Gt(k d_aa) + b Gt(k d_ab) with k INSIDE Gt (it multiplies d_* at the pixel p of the map, before
+ *            the adjoint spreads them);  dLoss/db: the same with a and b exchanged.
+ *   Everything else is ssimf's, word for word: samples, dataRange and the constants, the window G, the clamped edges and their adjoint
+ *            Gt, the centring per 128-column strip column, d_mu, d_aa, d_ab in the centred variables, 32 x 32 tiles at absolute positions
+ *            with one writer per gradient pixel and no floating-point atomics.
+ *   Products  k(p) d(p) is a plain fp32 product.  A zero weight does not hide a NaN or Inf statistic: 0 * NaN is NaN, and it reaches the up
+ *            to 11 x 11 gradient pixels whose window holds p.  Mask such samples out of the images, not only out of gMap.
+ *   Identity  for a plane gMap_i whose every element is the float  float(double(gOut[i]) / (double(W) * double(H)))  the gradients have
+ *            the BITS rmgr_ssim_hip_enqueue_ssimf_grad stores for gOut[i]; for 16-bit samples, those of rmgr_ssim_hip_enqueue_ssimh_grad.
+ *   float16 / bfloat16 samples (_ssimh_map_grad)  as rmgr_ssim_hip_enqueue_ssimh: the gradient is the float32 value of the widened planes,
+ *            rounded ONCE, to nearest-even, into the inputs' encoding (subnormals kept, overflow to Inf, NaN stays NaN).  gMap stays
+ *            float32, so a loss scale that arrives in it is applied before the single rounding.
+ *   Determinism  as for ssimf: the same bits alone or anywhere in a batch, after any sub-batch split, on every call, with one gradient
+ *            or both, and for negative-step or interleaved views of the samples, of gMap or of the gradient planes compared with the
+ *            same pixels stored contiguously.
+ *
+ * gradOutMaps: an array of count rmgr_ssim_hip_GradOutF in HOST memory, each describing a plane in DEVICE memory: gMap_i(x, y) is
+ *            topLeft[x * step + y * stride], step and stride in floats, negatives and 0 included -- with step = stride = 0 one float
+ *            stands for the whole plane (what a framework hands over as the expanded gradient of a mean).
+ * gradA / gradB: as for _enqueue_ssimf_grad / _enqueue_ssimh_grad (either may be NULL, not both).  Gradients are WRITTEN, not accumulated.  A
+ *            gradient plane must not overlap an input plane, a gMap plane or another gradient plane: this is not checked.
+ *            params[i].ssimMap is ignored.  Everything is device-resident; the call is asynchronous on the context's stream and never
+ *            waits for the host.  One fused launch recomputes the statistics: no scratch memory beyond the descriptors.
+ * The arguments before gradOutMaps are those of the corresponding _grad entry, in its order (sampleType before dataRange for 16-bit samples).
+ * EINVAL: every EINVAL of rmgr_ssim_hip_enqueue_ssimf_grad / _enqueue_ssimh_grad, a NULL gradOutMaps, a gMap topLeft that is NULL or not
+ *         4-byte aligned -- all checked before any device is touched.  ENODEV: no device.
+ */
+typedef struct rmgr_ssim_hip_GradOutF {
+    const float* topLeft;
+    ptrdiff_t    step, stride;                  /* in floats; 0 allowed */
+} rmgr_ssim_hip_GradOutF;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                  float dataRange, const rmgr_ssim_hip_GradOutF* gradOutMaps,
+                                                  const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_GradOutF* gradOutMaps,
+                                                  const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

@@ -77,6 +77,12 @@ class GradH(ctypes.Structure):
     _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
 
 
+class GradOutF(ctypes.Structure):
+    """rmgr_ssim_hip_GradOutF: one float32 plane dLoss/dssim(p) in device memory; step and stride count floats, 0 allowed (both 0: one
+    float stands for the whole plane)."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
+
+
 SAMPLE_F16, SAMPLE_BF16 = 0, 1      # RMGR_SSIM_HIP_SAMPLE_F16 / _BF16
 _SAMPLE_TYPES = {"float16": SAMPLE_F16, "bfloat16": SAMPLE_BF16}
 
@@ -134,6 +140,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssimf", "rmgr_ssim_hip_compute_ssimf_device", "rmgr_ssim_hip_compute_ssimf_host", "rmgr_ssim_hip_enqueue_ssimf_grad",
     "rmgr_ssim_hip_enqueue_msssimf", "rmgr_ssim_hip_compute_msssimf_device", "rmgr_ssim_hip_compute_msssimf_host", "rmgr_ssim_hip_enqueue_msssimf_grad",
     "rmgr_ssim_hip_enqueue_ssimh", "rmgr_ssim_hip_compute_ssimh_device", "rmgr_ssim_hip_compute_ssimh_host", "rmgr_ssim_hip_enqueue_ssimh_grad",
+    "rmgr_ssim_hip_enqueue_ssimf_map_grad", "rmgr_ssim_hip_enqueue_ssimh_map_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -218,6 +225,8 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssimh_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_compute_ssimh_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssimh_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
+        "rmgr_ssim_hip_enqueue_ssimf_map_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
+        "rmgr_ssim_hip_enqueue_ssimh_map_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
         "rmgr_ssim_hip_enqueue_msssimf": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
         "rmgr_ssim_hip_compute_msssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
@@ -830,6 +839,19 @@ class Context(object):
         arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values; asynchronous, no host synchronisation."""
         _check("rmgr_ssim_hip_enqueue_ssimh_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_grad(
             self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_dev_ptr, grad_a, grad_b))
+
+    def enqueue_ssimf_map_grad(self, params_array, count, data_range, grad_out_maps, grad_a=None, grad_b=None):
+        """rmgr_ssim_hip_enqueue_ssimf_map_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs for a per-pixel upstream
+        gradient: grad_out_maps is a GradOutF array of `count` float32 planes dLoss/dssim_i(p) in device memory (any step / stride, 0
+        included); asynchronous, written not accumulated."""
+        _check("rmgr_ssim_hip_enqueue_ssimf_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_map_grad(
+            self.handle, count, params_array, data_range, grad_out_maps, grad_a, grad_b))
+
+    def enqueue_ssimh_map_grad(self, params_array, count, data_range, sample_type, grad_out_maps, grad_a=None, grad_b=None):
+        """rmgr_ssim_hip_enqueue_ssimh_map_grad: the same for float16 / bfloat16 pairs (a Params16 array); the GradH planes receive the
+        float32 value rounded once into the inputs' encoding; the GradOutF planes stay float32."""
+        _check("rmgr_ssim_hip_enqueue_ssimh_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_map_grad(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_maps, grad_a, grad_b))
 
     def msssimf_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False):
         """MS-SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_msssimf_device: a float32

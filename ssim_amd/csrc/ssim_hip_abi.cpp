@@ -7,6 +7,7 @@
 #include "ssim_context.h"
 #include "msssim_kernels.h"
 #include "ssimh_kernels.h"
+#include "ssimw_kernels.h"
 
 #include <cmath>
 #include <condition_variable>
@@ -1646,6 +1647,120 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uin
         HIP_TRY(ssim_hip::launch_ssimh_grad(W, H, n, reinterpret_cast<const PairHDesc*>(s->dev.get()),
                                             reinterpret_cast<const GradHDesc*>(s->dev.get() + pair_bytes), ssimh_type(sampleType),
                                             gradOutDevice + i0, dataRange, which, c->stream));
+        HIP_TRY(hipEventRecord(s->used, c->stream));
+        s->pending = true;
+        i0 += n;
+    }
+    return 0;
+}
+
+// ---- gradient of the SSIM map for a per-pixel upstream gradient (rmgr_ssim_hip_enqueue_ssimf_map_grad, _enqueue_ssimh_map_grad) ---------------
+// The definition is in include/rmgr/ssim-hip.h, the kernels in ssimw_kernels.hip.  The host flow is that of _enqueue_ssimf_grad /
+// _enqueue_ssimh_grad on the same descriptor ring, with one more descriptor per pair: the gMap plane.  Gradient pixels run over fixed tiles,
+// so neither the sub-batches nor the launch a pair lands in change a bit.
+namespace {
+
+using ssim_hip::GradOutFDesc;
+
+// What the map-gradient entries check beyond the _grad entries, before any device is touched.
+int ssimw_validate_maps(rmgr_uint32_t count, const rmgr_ssim_hip_GradOutF* maps)
+{
+    for (uint32_t i = 0; i < count; ++i)
+        if (maps[i].topLeft == NULL || ((uintptr_t)maps[i].topLeft & 3u)) return EINVAL;
+    return 0;
+}
+
+GradOutFDesc make_gout(const rmgr_ssim_hip_GradOutF& m)
+{
+    const GradOutFDesc o = {m.topLeft, (int64_t)m.step, (int64_t)m.stride};
+    return o;
+}
+
+} // namespace
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                  float dataRange, const rmgr_ssim_hip_GradOutF* gradOutMaps,
+                                                  const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    int rc = ssimf_validate(count, params, dataRange, gradOutMaps);
+    if (rc) return rc;
+    if ((rc = ssimw_validate_maps(count, gradOutMaps))) return rc;
+    if (gradA == NULL && gradB == NULL) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const rmgr_ssim_hip_GradF* g = k ? gradB : gradA;
+            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 3u))) return EINVAL;
+        }
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
+    const uint32_t nmax = ssim_hip::ssimf_max_count(W, H);
+    for (uint32_t i0 = 0; i0 < count;) {
+        const uint32_t n = std::min(count - i0, nmax);
+        rmgr_ssim_hip_Context_::SfSlot* s;
+        const size_t pair_bytes = n * sizeof(PairFDesc), grad_bytes = n * sizeof(GradFDesc), bytes = pair_bytes + grad_bytes + n * sizeof(GradOutFDesc);
+        if ((rc = ssimf_slot(c, bytes, s))) return rc;
+        PairFDesc* pd = reinterpret_cast<PairFDesc*>(s->pin.get());
+        GradFDesc* gd = reinterpret_cast<GradFDesc*>(s->pin.get() + pair_bytes);
+        GradOutFDesc* od = reinterpret_cast<GradOutFDesc*>(s->pin.get() + pair_bytes + grad_bytes);
+        for (uint32_t i = 0; i < n; ++i) {
+            pd[i] = make_descf(params[i0 + i], false);
+            GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
+            if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
+            if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
+            gd[i] = g;
+            od[i] = make_gout(gradOutMaps[i0 + i]);
+        }
+        HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(ssim_hip::launch_ssimw_grad_f(W, H, n, reinterpret_cast<const PairFDesc*>(s->dev.get()),
+                reinterpret_cast<const GradFDesc*>(s->dev.get() + pair_bytes),
+                reinterpret_cast<const GradOutFDesc*>(s->dev.get() + pair_bytes + grad_bytes), dataRange, which, c->stream));
+        HIP_TRY(hipEventRecord(s->used, c->stream));
+        s->pending = true;
+        i0 += n;
+    }
+    return 0;
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_GradOutF* gradOutMaps,
+                                                  const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
+{
+    int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutMaps);
+    if (rc) return rc;
+    if ((rc = ssimw_validate_maps(count, gradOutMaps))) return rc;
+    if (gradA == NULL && gradB == NULL) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const rmgr_ssim_hip_GradH* g = k ? gradB : gradA;
+            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 1u))) return EINVAL;
+        }
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0), type = ssimh_type(sampleType);
+    const uint32_t nmax = ssim_hip::ssimh_max_count(W, H);
+    for (uint32_t i0 = 0; i0 < count;) {
+        const uint32_t n = std::min(count - i0, nmax);
+        rmgr_ssim_hip_Context_::SfSlot* s;
+        const size_t pair_bytes = n * sizeof(PairHDesc), grad_bytes = n * sizeof(GradHDesc), bytes = pair_bytes + grad_bytes + n * sizeof(GradOutFDesc);
+        if ((rc = ssimf_slot(c, bytes, s))) return rc;
+        PairHDesc* pd = reinterpret_cast<PairHDesc*>(s->pin.get());
+        GradHDesc* gd = reinterpret_cast<GradHDesc*>(s->pin.get() + pair_bytes);
+        GradOutFDesc* od = reinterpret_cast<GradOutFDesc*>(s->pin.get() + pair_bytes + grad_bytes);
+        for (uint32_t i = 0; i < n; ++i) {
+            pd[i] = make_desch(params[i0 + i], false);
+            GradHDesc g = {NULL, 0, 0, NULL, 0, 0};
+            if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
+            if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
+            gd[i] = g;
+            od[i] = make_gout(gradOutMaps[i0 + i]);
+        }
+        HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(ssim_hip::launch_ssimw_grad_h(W, H, n, reinterpret_cast<const PairHDesc*>(s->dev.get()),
+                reinterpret_cast<const GradHDesc*>(s->dev.get() + pair_bytes), type,
+                reinterpret_cast<const GradOutFDesc*>(s->dev.get() + pair_bytes + grad_bytes), dataRange, which, c->stream));
         HIP_TRY(hipEventRecord(s->used, c->stream));
         s->pending = true;
         i0 += n;

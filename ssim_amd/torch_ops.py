@@ -1,7 +1,7 @@
 """SSIM of float32, float16 and bfloat16 tensors and multi-scale SSIM of float32 tensors as differentiable PyTorch operations, on the
 library's fused gfx950 kernels.
 
-    from ssim_amd.torch_ops import ssim, SSIMLoss, ms_ssim, MSSSIMLoss
+    from ssim_amd.torch_ops import ssim, ssim_map, SSIMLoss, ms_ssim, MSSSIMLoss
     loss = 0.8 * (x - y).abs().mean() + 0.2 * SSIMLoss()(x, y)      # x, y: (N, C, H, W) float32 on the GPU
     loss = 0.16 * (x - y).abs().mean() + 0.84 * MSSSIMLoss()(x, y)
     loss.backward()
@@ -22,6 +22,19 @@ tensor with one rounding and no float32 intermediate.  Two things to know:
     scale * round(g).
 ms_ssim and MSSSIMLoss keep refusing 16-bit tensors (TypeError): that is the follow-up, and needs only scale 0's loads and stores.
 
+The map.  ssim_map(x, y, data_range) returns the per-pixel SSIM, float32 of shape x.shape, for losses that are not a plain mean per plane.
+The forward is the same kernel writing its map; the backward is rmgr_ssim_hip_enqueue_ssimf_map_grad / _ssimh_map_grad, the fused gradient
+kernel with the upstream gradient read per pixel, in place through grad_out's own strides (the expanded zero-stride tensor that sum()
+hands back is one float, not a plane).  It saves x and y only.
+
+    m = ssim_map(x, y)                                              # (N, C, H, W), float32
+    loss = 1 - (w * m).sum() / w.sum()                              # a validity mask or a saliency weight w
+    photo = 0.85 * (1 - ssim_map(warped, target)) / 2 + 0.15 * (warped - target).abs()      # monodepth-style, warped: (V, N, C, H, W)
+    loss = (auto_mask * photo.mean(2).min(0).values).mean()         # per-pixel minimum over the V source views, then the auto-mask
+
+A zero weight does not hide a NaN: 0 * NaN is NaN, and the gradient of the pixels around it is NaN too.  Replace invalid samples in x and
+y, not only in the weights.
+
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
 import ctypes
@@ -32,6 +45,7 @@ from . import api
 _contexts = {}      # (device index, stream handle) -> (Context, the torch stream it is bound to)
 _side = {}          # device index -> torch stream that stands in for the legacy default stream
 _function = None
+_map_function = None
 _ms_function = None
 
 
@@ -184,6 +198,95 @@ def ssim(x, y, data_range=1.0):
     if _function is None:
         _function = _make_function()
     return _function.apply(x, y, r)
+
+
+def _with_maps(params, n, m, h, w):
+    """params with ssimMap pointing at the n contiguous (H, W) planes of the float32 tensor m."""
+    base = m.data_ptr()
+    for i in range(n):
+        params[i].ssimMap, params[i].ssimStep, params[i].ssimStride = base + 4 * i * h * w, 1, w
+    return params
+
+
+def _grad_out_planes(g, n):
+    """GradOutF array over the n (H, W) planes of the float32 tensor g, each where it is: any strides, 0 (an expanded tensor) included."""
+    arr = (api.GradOutF * max(n, 1))()
+    base, step, stride = g.data_ptr(), g.stride(-1), g.stride(-2)
+    for i, off in enumerate(_plane_offsets(g)):
+        arr[i] = api.GradOutF(base + 4 * off, step, stride)
+    return arr
+
+
+def _make_map_function():
+    import torch
+
+    class _SSIMMap(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, data_range):
+            h, w = x.shape[-2], x.shape[-1]
+            params, n = _params(x, y)
+            out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            if n:
+                sums = torch.empty(n, dtype=torch.float64, device=x.device)      # the kernel's other output, thrown away; freed into the
+                                                                                 # current stream's pool, which waits for the work below
+                _with_maps(params, n, out, h, w)
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                st = _sample_type(torch, x.dtype)
+                if st is None:
+                    _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr())
+                else:
+                    _context(x.device, work).enqueue_ssimh(params, n, data_range, st, sums.data_ptr())
+                if work is not cur:
+                    cur.wait_stream(work)
+            ctx.save_for_backward(x, y)
+            ctx.data_range = data_range
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            x, y = ctx.saved_tensors
+            h, w = x.shape[-2], x.shape[-1]
+            want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_x or want_y):
+                return None, None, None
+            params, n = _params(x, y)
+            g = grad_out if grad_out.dtype == torch.float32 else grad_out.to(torch.float32)      # read in place, through its own strides
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
+            gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                st = _sample_type(torch, x.dtype)
+                maps = _grad_out_planes(g, n)
+                ga = _grad_planes(gx, n, h, w) if want_x else None
+                gb = _grad_planes(gy, n, h, w) if want_y else None
+                if st is None:
+                    _context(x.device, work).enqueue_ssimf_map_grad(params, n, ctx.data_range, maps, ga, gb)
+                else:
+                    _context(x.device, work).enqueue_ssimh_map_grad(params, n, ctx.data_range, st, maps, ga, gb)
+                if work is not cur:
+                    cur.wait_stream(work)
+            return gx, gy, None
+
+    return _SSIMMap
+
+
+def ssim_map(x, y, data_range=1.0):
+    """Per-pixel SSIM of two GPU tensors of identical shape (..., H, W), both float32, both float16 or both bfloat16, any strides (each
+    plane is addressed in place, no copy): a float32 tensor of shape x.shape at every input dtype, the map rmgr_ssim_hip_enqueue_ssimf /
+    _ssimh write.  Differentiable with respect to x, y or both for ANY upstream gradient: the backward reads grad_out per pixel, in place
+    (expanded and non-contiguous tensors included; another dtype is cast to float32 once), computes the gradient only for the inputs
+    that need it and returns it in the inputs' dtype (float16 and bfloat16: the float32 value rounded once).  It keeps x and y, not the
+    map.  A zero in grad_out does not hide a NaN in the images.  Errors: as ssim()."""
+    global _map_function
+    r = _check(x, y, data_range, half=True)
+    if _map_function is None:
+        _map_function = _make_map_function()
+    return _map_function.apply(x, y, r)
 
 
 class SSIMLoss(object):
