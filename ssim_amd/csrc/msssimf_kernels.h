@@ -1,4 +1,4 @@
-// msssimf_kernels.h -- internal interface between the C ABI (ssim_hip_abi.cpp, multi-scale SSIM of float32 samples and its
+// msssimf_kernels.h -- internal interface between the C ABI (ssim_samples_abi.cpp, multi-scale SSIM of float32 samples and its
 // gradient) and the kernels (msssimf_kernels.hip).  Not installed.  The definition the kernels implement is written out in
 // include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_msssimf, rmgr_ssim_hip_enqueue_msssimf_grad).
 #ifndef SSIM_AMD_MSSSIMF_KERNELS_H

@@ -1,4 +1,4 @@
-// ssim16_kernels.h -- internal interface between the C ABI (ssim_hip_abi.cpp, high-bit-depth SSIM) and the SSIM kernels of
+// ssim16_kernels.h -- internal interface between the C ABI (ssim_samples_abi.cpp, high-bit-depth SSIM) and the SSIM kernels of
 // 9- to 16-bit samples (ssim16_kernels.hip).  Not installed.  The definition the kernels implement is written out in
 // include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssim16).
 #ifndef SSIM_AMD_SSIM16_KERNELS_H

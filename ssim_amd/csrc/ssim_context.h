@@ -1,6 +1,7 @@
 // ssim_context.h -- internal to the C ABI (include/rmgr/ssim-hip.h): the context, the resources it owns, and what the host-layer
-// files share.  ssim_context.cpp creates and destroys contexts and keeps the default pool; ssim_hip_abi.cpp holds the SSIM
-// entry points; ssim_comm.cpp the RCCL all-reduce; ssim_tune.cpp profiling and tuning.  Not installed.
+// files share.  ssim_context.cpp creates and destroys contexts and keeps the default pool; ssim_hip_abi.cpp holds the entry points
+// of 8-bit samples, ssim_samples_abi.cpp those of 16-bit, float32 and float16 / bfloat16 samples; ssim_comm.cpp the RCCL all-reduce;
+// ssim_tune.cpp profiling and tuning.  Not installed.
 #ifndef SSIM_AMD_CONTEXT_H
 #define SSIM_AMD_CONTEXT_H
 
@@ -179,17 +180,10 @@ struct rmgr_ssim_hip_Context_ {
     PinnedBuffer<ssim_hip::PairDesc> ms_desc_pin;
     DeviceBuffer<double>   ms_sums;
     PinnedBuffer<double>   ms_sums_pin;
-    // SSIM of 16-bit samples (rmgr_ssim_hip_*_ssim16): descriptor table (its pinned mirror is rewritten only once the launch that
-    // read it has run: s16_desc_used), cell partials, per-pair sums written by the GPU
-    DeviceBuffer<ssim_hip::Pair16Desc> s16_desc;
-    PinnedBuffer<ssim_hip::Pair16Desc> s16_desc_pin;
-    LazyEvent              s16_desc_used;
-    bool                   s16_desc_pending = false;
-    DeviceBuffer<double>   s16_partials;
-    PinnedBuffer<double>   s16_sums_pin;
-    // SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_ssimf*): a ring of descriptor tables (pair descriptors, then the
-    // gradient descriptors of a gradient launch), so that an enqueue waits at most for the launch kSfSlots enqueues ago -- a training
-    // step's forward and backward never wait for each other --, cell partials, per-pair sums written by the GPU
+    // SSIM of 16-bit, float32 and float16 / bfloat16 samples and the gradients (rmgr_ssim_hip_*_ssim16, _ssimf*, _ssimh*): a ring of
+    // descriptor tables (pair descriptors, then the gradient descriptors of a gradient launch), so that an enqueue waits at most for the
+    // launch kSfSlots enqueues ago -- a training step's forward and backward never wait for each other --, cell partials, per-pair sums
+    // written by the GPU.  Every family shares them: one stream, stream order.
     enum { kSfSlots = 8 };
     struct SfSlot {
         DeviceBuffer<uint8_t> dev;
@@ -216,7 +210,6 @@ struct rmgr_ssim_hip_Context_ {
         for (int i = 0; i < 2; ++i) { f(slot_dev[i]); f(slot_pin[i]); f(h_map[i]); }
         f(batch_sums);
         f(ms_scratch); f(ms_desc); f(ms_desc_pin); f(ms_sums); f(ms_sums_pin);
-        f(s16_desc); f(s16_desc_pin); f(s16_partials); f(s16_sums_pin);
         for (SfSlot& s : sf_slots) { f(s.dev); f(s.pin); }
         f(sf_partials); f(sf_sums_pin);
         f(msf_pyramid); f(msf_grads); f(msf_coef); f(msf_partials); f(msf_out); f(msf_out_pin);
@@ -293,6 +286,7 @@ struct Lease {
 int enqueue(rmgr_ssim_hip_Context* c, uint32_t width, uint32_t height, uint32_t count, const PairDesc* descs, bool any_map, double* sums_dev,
             uint32_t y_begin = 0, uint32_t y_rows = 0xFFFFFFFFu, bool reduce = true, double* cells_out = NULL);
 int drain_profile(rmgr_ssim_hip_Context* c);
+extern const double kWangWeights[5];     // the default weights of the multi-scale entry points (ssim_samples_abi.cpp uses them too)
 
 // ssim_comm.cpp
 int comm_bounded_sync(rmgr_ssim_hip_Context* c);

@@ -1,4 +1,5 @@
-// ssim_hip_abi.cpp -- the SSIM entry points of the C ABI declared in include/rmgr/ssim-hip.h (the context itself: ssim_context.cpp).
+// ssim_hip_abi.cpp -- the SSIM entry points of the C ABI declared in include/rmgr/ssim-hip.h for 8-bit samples: SSIM, multi-scale SSIM, the
+// multi-device entry, the channel and luminance entries (the context itself: ssim_context.cpp; other sample types: ssim_samples_abi.cpp).
 //
 // Host-side driver of the GPU path: what src/ssim.cpp:933-1106 (compute_ssim) is to the
 // reference's tile kernels, this file is to ssim_kernels.hip -- parameter validation with the
@@ -6,8 +7,6 @@
 // no gfx950 device is usable every entry point fails loudly with ENODEV.
 #include "ssim_context.h"
 #include "msssim_kernels.h"
-#include "ssimh_kernels.h"
-#include "ssimw_kernels.h"
 
 #include <cmath>
 #include <condition_variable>
@@ -16,6 +15,7 @@
 namespace ssim_host {
 
 const size_t kSmallStageBytes = size_t(768) << 10;   // image pairs up to this many bytes go through one pinned gather copy
+const double kWangWeights[5] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};     // msssim.m (Wang, Simoncelli & Bovik 2003)
 
 // The reference's parameter checks, in its order (src/ssim.cpp:962-978).
 int validate(const float* ssim, const rmgr_ssim_Params* p, const rmgr_ssim_ThreadPool* tp)
@@ -786,7 +786,6 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssim_host(rmgr_ssim_hip_Context* c, float* ss
 // fixed order, so the split changes nothing in the results.
 namespace {
 
-const double   kWangWeights[5] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};     // msssim.m (Wang, Simoncelli & Bovik 2003)
 const uint64_t kMsScratchCap = uint64_t(1) << 30;
 
 // Every check of the two entry points, before any device is touched.
@@ -916,1110 +915,6 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssim_host(rmgr_ssim_hip_Context* c, rmgr_ui
     c = lease.c;
     USE_DEVICE(c);
     return msssim_batches(c, count, params, scales, weights ? weights : kWangWeights, msssim, scaleMeans, true);
-}
-
-// ---- SSIM of 9- to 16-bit samples (rmgr_ssim_hip_enqueue_ssim16, rmgr_ssim_hip_compute_ssim16_*) ----------------------------------------------
-// The definition is in include/rmgr/ssim-hip.h, the kernels in ssim16_kernels.hip.  Each pair's sum runs over fixed cells in a fixed order, so
-// neither the sub-batches (kS16ScratchCap of partials, staged images and maps per sub-batch) nor the launch a pair lands in change a bit.
-namespace {
-
-using ssim_hip::Pair16Desc;
-const uint64_t kS16ScratchCap = uint64_t(1) << 30;
-
-// Every check of the three entry points, before any device is touched.
-int ssim16_validate(rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params, rmgr_uint32_t bitDepth, const void* out)
-{
-    if (count == 0 || params == NULL || out == NULL) return EINVAL;
-    if (bitDepth < RMGR_SSIM_HIP_SSIM16_MIN_DEPTH || bitDepth > RMGR_SSIM_HIP_SSIM16_MAX_DEPTH) return EINVAL;
-    const uint32_t W = params[0].width, H = params[0].height;
-    if (W == 0 || H == 0 || W > ssim_hip::kS16MaxDim || H > ssim_hip::kS16MaxDim) return EINVAL;
-    for (uint32_t i = 0; i < count; ++i) {
-        const rmgr_ssim_hip_Params16& p = params[i];
-        if (p.width != W || p.height != H) return EINVAL;
-        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
-        if (((uintptr_t)p.imgA.topLeft & 1u) || ((uintptr_t)p.imgB.topLeft & 1u)) return EINVAL;
-    }
-    if (ssim_hip::ssim16_max_count(W, H) == 0) return EINVAL;
-    return 0;
-}
-
-Pair16Desc make_desc16(const rmgr_ssim_hip_Params16& p)
-{
-    Pair16Desc d;
-    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride;
-    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride;
-    d.map = p.ssimMap;
-    d.map_step = p.ssimMap ? p.ssimStep : 0;
-    d.map_stride = p.ssimMap ? p.ssimStride : 0;
-    return d;
-}
-
-// Sample extent [lo, hi] (inclusive, relative to topLeft, in samples) of a width x height image.
-void extent16(const rmgr_ssim_hip_Img16& im, uint32_t w, uint32_t h, int64_t& lo, int64_t& hi)
-{
-    const int64_t dx = (int64_t)(w - 1) * (int64_t)im.step, dy = (int64_t)(h - 1) * (int64_t)im.stride;
-    lo = (dx < 0 ? dx : 0) + (dy < 0 ? dy : 0);
-    hi = (dx > 0 ? dx : 0) + (dy > 0 ? dy : 0);
-}
-
-uint64_t ssim16_partials_per_pair(uint32_t W, uint32_t H)
-{
-    const ssim_hip::Geometry16 g = ssim_hip::plan16(W, H, 1, 0);
-    return g.cells_per_image() * sizeof(double);
-}
-
-// Enqueues n pairs (descriptors in host memory, images on the device) on the context's stream: descriptor upload, strip kernel,
-// reduction into sums[0 .. n-1] (device or pinned host memory).  n <= ssim16_max_count and its partials within the cap.
-int ssim16_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const Pair16Desc* d, uint32_t W, uint32_t H, uint32_t depth, double* sums)
-{
-    int rc;
-    if (c->s16_desc_pending) {               // the pinned mirror is the source of the last queued upload
-        HIP_TRY(hipEventSynchronize(c->s16_desc_used));
-        c->s16_desc_pending = false;
-    }
-    HIP_TRY(c->s16_desc_used.ensure());
-    const ssim_hip::Geometry16 geo = ssim_hip::plan16(W, H, n, c->cu_count);
-    if ((rc = c->s16_desc_pin.grow(n))) return rc;
-    if ((rc = c->s16_desc.grow(n))) return rc;
-    if ((rc = c->s16_partials.grow((size_t)(geo.cells_per_image() * n)))) return rc;
-    bool map = false, unit = (W % 2) == 0, wide = false;
-    for (uint32_t i = 0; i < n; ++i) {
-        map = map || d[i].map != NULL;
-        unit = unit && (d[i].map == NULL || d[i].map_step == 1);
-        wide = wide || !ssim_hip::fits16_narrow(d[i]);
-    }
-    memcpy(c->s16_desc_pin.get(), d, n * sizeof(Pair16Desc));
-    HIP_TRY(hipMemcpyAsync(c->s16_desc, c->s16_desc_pin, n * sizeof(Pair16Desc), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(ssim_hip::launch_ssim16(geo, c->s16_desc, map, unit, wide, depth, c->xcd_count, c->s16_partials, sums, c->stream));
-    HIP_TRY(hipEventRecord(c->s16_desc_used, c->stream));
-    c->s16_desc_pending = true;
-    return 0;
-}
-
-// Pairs of params[i0 ..] that one sub-batch takes: at least one; within the launch limit and, with `stage_bytes` per pair of staged
-// images and maps (host pointers), kS16ScratchCap of device scratch.
-uint32_t ssim16_take(const rmgr_ssim_hip_Params16* params, uint32_t i0, uint32_t count, bool stage, uint64_t& staged)
-{
-    const uint32_t W = params[0].width, H = params[0].height;
-    const uint64_t part = ssim16_partials_per_pair(W, H);
-    const uint32_t nmax = ssim_hip::ssim16_max_count(W, H);
-    uint32_t n = 0;
-    staged = 0;
-    while (i0 + n < count && n < nmax) {
-        uint64_t bytes = 0;
-        if (stage) {
-            const rmgr_ssim_hip_Params16& p = params[i0 + n];
-            int64_t lo, hi;
-            extent16(p.imgA, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 2 + 63) & ~uint64_t(63);
-            extent16(p.imgB, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 2 + 63) & ~uint64_t(63);
-            if (p.ssimMap) bytes += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
-        }
-        if (n > 0 && part * (n + 1) + staged + bytes > kS16ScratchCap) break;
-        staged += bytes;
-        ++n;
-    }
-    return n;
-}
-
-// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the images are copied
-// (each image's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own step and stride.
-int ssim16_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t depth, float* ssim, bool stage)
-{
-    const uint32_t W = params[0].width, H = params[0].height;
-    const double px = (double)W * (double)H;
-    int rc;
-    if ((rc = c->s16_sums_pin.grow(count))) return rc;
-    try {
-        std::vector<Pair16Desc> d;
-        std::vector<float> back;
-        for (uint32_t i0 = 0; i0 < count;) {
-            uint64_t staged;
-            const uint32_t n = ssim16_take(params, i0, count, stage, staged);
-            d.resize(n);
-            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
-            uint64_t off = 0;
-            std::vector<uint64_t> map_off(n, 0);
-            for (uint32_t i = 0; i < n; ++i) {
-                const rmgr_ssim_hip_Params16& p = params[i0 + i];
-                d[i] = make_desc16(p);
-                if (!stage) continue;
-                for (int k = 0; k < 2; ++k) {
-                    const rmgr_ssim_hip_Img16& im = k ? p.imgB : p.imgA;
-                    int64_t lo, hi;
-                    extent16(im, W, H, lo, hi);
-                    const size_t bytes = (size_t)(hi - lo + 1) * 2;
-                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
-                    (k ? d[i].b : d[i].a) = reinterpret_cast<const uint16_t*>(c->stage_a + off) - lo;
-                    off += (bytes + 63) & ~uint64_t(63);
-                }
-                if (p.ssimMap) {
-                    map_off[i] = off;
-                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
-                    d[i].map_step = 1; d[i].map_stride = W;
-                    off += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
-                }
-            }
-            if ((rc = ssim16_enqueue(c, n, &d[0], W, H, depth, c->s16_sums_pin + i0))) return rc;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            for (uint32_t i = 0; i < n && stage; ++i) {
-                const rmgr_ssim_hip_Params16& p = params[i0 + i];
-                if (!p.ssimMap) continue;
-                const float* src = reinterpret_cast<const float*>(c->stage_a + map_off[i]);
-                if (p.ssimStep == 1 && p.ssimStride == (ptrdiff_t)W) {
-                    HIP_TRY(hipMemcpy(p.ssimMap, src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
-                    continue;
-                }
-                back.resize((size_t)W * H);
-                HIP_TRY(hipMemcpy(&back[0], src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
-                for (uint32_t y = 0; y < H; ++y) {
-                    float* row = p.ssimMap + (ptrdiff_t)y * p.ssimStride;
-                    const float* s = &back[(size_t)y * W];
-                    for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = s[x];
-                }
-            }
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->s16_sums_pin[i] / px);
-    return 0;
-}
-
-} // namespace
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_ssim16(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
-                                          rmgr_uint32_t bitDepth, double* sumsDevice) RMGR_NOEXCEPT
-{
-    int rc = ssim16_validate(count, params, bitDepth, sumsDevice);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    try {
-        std::vector<Pair16Desc> d;
-        for (uint32_t i0 = 0; i0 < count;) {
-            uint64_t staged;
-            const uint32_t n = ssim16_take(params, i0, count, false, staged);
-            d.resize(n);
-            for (uint32_t i = 0; i < n; ++i) d[i] = make_desc16(params[i0 + i]);
-            if ((rc = ssim16_enqueue(c, n, &d[0], params[0].width, params[0].height, bitDepth, sumsDevice + i0))) return rc;
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    return 0;
-}
-
-rmgr_int32_t rmgr_ssim_hip_compute_ssim16_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
-                                                 rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT
-{
-    int rc = ssim16_validate(count, params, bitDepth, ssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return ssim16_blocking(c, count, params, bitDepth, ssim, false);
-}
-
-rmgr_int32_t rmgr_ssim_hip_compute_ssim16_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
-                                               rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT
-{
-    int rc = ssim16_validate(count, params, bitDepth, ssim);
-    if (rc) return rc;
-    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
-    if ((rc = lease.take(c))) return rc;
-    c = lease.c;
-    USE_DEVICE(c);
-    return ssim16_blocking(c, count, params, bitDepth, ssim, true);
-}
-
-// ---- SSIM of float32 samples and its gradient (rmgr_ssim_hip_enqueue_ssimf, _compute_ssimf_*, _enqueue_ssimf_grad) ---------------------------
-// The definition is in include/rmgr/ssim-hip.h, the kernels in ssimf_kernels.hip.  The forward path is the ssim16 one with float samples; the
-// gradient is one fused launch without scratch.  Sums run over fixed cells and gradient pixels over fixed tiles, so neither the sub-batches
-// nor the launch a pair lands in change a bit.
-namespace {
-
-using ssim_hip::PairFDesc;
-using ssim_hip::GradFDesc;
-const uint64_t kSFScratchCap = uint64_t(1) << 30;
-
-// Every check the entry points share, before any device is touched.
-int ssimf_validate(rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const void* out)
-{
-    if (count == 0 || params == NULL || out == NULL) return EINVAL;
-    if (!(dataRange > 0.0f) || !std::isfinite(dataRange)) return EINVAL;
-    const uint32_t W = params[0].width, H = params[0].height;
-    if (W == 0 || H == 0 || W > ssim_hip::kSFMaxDim || H > ssim_hip::kSFMaxDim) return EINVAL;
-    for (uint32_t i = 0; i < count; ++i) {
-        const rmgr_ssim_hip_ParamsF& p = params[i];
-        if (p.width != W || p.height != H) return EINVAL;
-        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
-        if (((uintptr_t)p.imgA.topLeft & 3u) || ((uintptr_t)p.imgB.topLeft & 3u)) return EINVAL;
-    }
-    if (ssim_hip::ssimf_max_count(W, H) == 0) return EINVAL;
-    return 0;
-}
-
-PairFDesc make_descf(const rmgr_ssim_hip_ParamsF& p, bool with_map)
-{
-    PairFDesc d;
-    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride;
-    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride;
-    const bool m = with_map && p.ssimMap;
-    d.map = m ? p.ssimMap : NULL;
-    d.map_step = m ? p.ssimStep : 0;
-    d.map_stride = m ? p.ssimStride : 0;
-    return d;
-}
-
-// Sample extent [lo, hi] (inclusive, relative to topLeft, in floats) of a width x height image.
-void extentf(const rmgr_ssim_hip_ImgF& im, uint32_t w, uint32_t h, int64_t& lo, int64_t& hi)
-{
-    const int64_t dx = (int64_t)(w - 1) * (int64_t)im.step, dy = (int64_t)(h - 1) * (int64_t)im.stride;
-    lo = (dx < 0 ? dx : 0) + (dy < 0 ? dy : 0);
-    hi = (dx > 0 ? dx : 0) + (dy > 0 ? dy : 0);
-}
-
-uint64_t ssimf_partials_per_pair(uint32_t W, uint32_t H)
-{
-    const ssim_hip::GeometryF g = ssim_hip::planf(W, H, 1, 0);
-    return g.cells_per_image() * sizeof(double);
-}
-
-// The next descriptor table of the ring with room for `bytes`: waits, at most, for the launch that read it kSfSlots enqueues ago.
-int ssimf_slot(rmgr_ssim_hip_Context* c, size_t bytes, rmgr_ssim_hip_Context_::SfSlot*& out)
-{
-    rmgr_ssim_hip_Context_::SfSlot& s = c->sf_slots[c->sf_next];
-    c->sf_next = (c->sf_next + 1) % rmgr_ssim_hip_Context_::kSfSlots;
-    if (s.pending) {
-        HIP_TRY(hipEventSynchronize(s.used));
-        s.pending = false;
-    }
-    HIP_TRY(s.used.ensure());
-    int rc;
-    if ((rc = s.pin.grow(bytes))) return rc;
-    if ((rc = s.dev.grow(bytes))) return rc;
-    out = &s;
-    return 0;
-}
-
-// Enqueues n pairs (descriptors in host memory, images on the device) on the context's stream: descriptor upload, strip kernel,
-// reduction into sums[0 .. n-1] (device or pinned host memory).  n <= ssimf_max_count and its partials within the cap.
-int ssimf_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const PairFDesc* d, uint32_t W, uint32_t H, float range, double* sums)
-{
-    int rc;
-    rmgr_ssim_hip_Context_::SfSlot* s;
-    if ((rc = ssimf_slot(c, n * sizeof(PairFDesc), s))) return rc;
-    const ssim_hip::GeometryF geo = ssim_hip::planf(W, H, n, c->cu_count);
-    if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_image() * n)))) return rc;
-    bool map = false, unit = (W % 2) == 0, wide = false;
-    for (uint32_t i = 0; i < n; ++i) {
-        map = map || d[i].map != NULL;
-        unit = unit && (d[i].map == NULL || d[i].map_step == 1);
-        wide = wide || !ssim_hip::fitsf_narrow(d[i]);
-    }
-    memcpy(s->pin.get(), d, n * sizeof(PairFDesc));
-    HIP_TRY(hipMemcpyAsync(s->dev, s->pin, n * sizeof(PairFDesc), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(ssim_hip::launch_ssimf(geo, reinterpret_cast<const PairFDesc*>(s->dev.get()), map, unit, wide, range, c->xcd_count, c->sf_partials, sums, c->stream));
-    HIP_TRY(hipEventRecord(s->used, c->stream));
-    s->pending = true;
-    return 0;
-}
-
-// Pairs of params[i0 ..] that one sub-batch takes: at least one; within the launch limit and, with the staged images and maps of host
-// pointers, kSFScratchCap of device scratch.
-uint32_t ssimf_take(const rmgr_ssim_hip_ParamsF* params, uint32_t i0, uint32_t count, bool stage, uint64_t& staged)
-{
-    const uint32_t W = params[0].width, H = params[0].height;
-    const uint64_t part = ssimf_partials_per_pair(W, H);
-    const uint32_t nmax = ssim_hip::ssimf_max_count(W, H);
-    uint32_t n = 0;
-    staged = 0;
-    while (i0 + n < count && n < nmax) {
-        uint64_t bytes = 0;
-        if (stage) {
-            const rmgr_ssim_hip_ParamsF& p = params[i0 + n];
-            int64_t lo, hi;
-            extentf(p.imgA, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 4 + 63) & ~uint64_t(63);
-            extentf(p.imgB, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 4 + 63) & ~uint64_t(63);
-            if (p.ssimMap) bytes += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
-        }
-        if (n > 0 && part * (n + 1) + staged + bytes > kSFScratchCap) break;
-        staged += bytes;
-        ++n;
-    }
-    return n;
-}
-
-// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the images are copied
-// (each image's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own step and stride.
-int ssimf_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float range, float* ssim, bool stage)
-{
-    const uint32_t W = params[0].width, H = params[0].height;
-    const double px = (double)W * (double)H;
-    int rc;
-    if ((rc = c->sf_sums_pin.grow(count))) return rc;
-    try {
-        std::vector<PairFDesc> d;
-        std::vector<float> back;
-        for (uint32_t i0 = 0; i0 < count;) {
-            uint64_t staged;
-            const uint32_t n = ssimf_take(params, i0, count, stage, staged);
-            d.resize(n);
-            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
-            uint64_t off = 0;
-            std::vector<uint64_t> map_off(n, 0);
-            for (uint32_t i = 0; i < n; ++i) {
-                const rmgr_ssim_hip_ParamsF& p = params[i0 + i];
-                d[i] = make_descf(p, true);
-                if (!stage) continue;
-                for (int k = 0; k < 2; ++k) {
-                    const rmgr_ssim_hip_ImgF& im = k ? p.imgB : p.imgA;
-                    int64_t lo, hi;
-                    extentf(im, W, H, lo, hi);
-                    const size_t bytes = (size_t)(hi - lo + 1) * 4;
-                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
-                    (k ? d[i].b : d[i].a) = reinterpret_cast<const float*>(c->stage_a + off) - lo;
-                    off += (bytes + 63) & ~uint64_t(63);
-                }
-                if (p.ssimMap) {
-                    map_off[i] = off;
-                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
-                    d[i].map_step = 1; d[i].map_stride = W;
-                    off += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
-                }
-            }
-            if ((rc = ssimf_enqueue(c, n, &d[0], W, H, range, c->sf_sums_pin + i0))) return rc;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            for (uint32_t i = 0; i < n && stage; ++i) {
-                const rmgr_ssim_hip_ParamsF& p = params[i0 + i];
-                if (!p.ssimMap) continue;
-                const float* src = reinterpret_cast<const float*>(c->stage_a + map_off[i]);
-                if (p.ssimStep == 1 && p.ssimStride == (ptrdiff_t)W) {
-                    HIP_TRY(hipMemcpy(p.ssimMap, src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
-                    continue;
-                }
-                back.resize((size_t)W * H);
-                HIP_TRY(hipMemcpy(&back[0], src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
-                for (uint32_t y = 0; y < H; ++y) {
-                    float* row = p.ssimMap + (ptrdiff_t)y * p.ssimStride;
-                    const float* s = &back[(size_t)y * W];
-                    for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = s[x];
-                }
-            }
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->sf_sums_pin[i] / px);
-    return 0;
-}
-
-} // namespace
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
-                                         float dataRange, double* sumsDevice) RMGR_NOEXCEPT
-{
-    int rc = ssimf_validate(count, params, dataRange, sumsDevice);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    try {
-        std::vector<PairFDesc> d;
-        for (uint32_t i0 = 0; i0 < count;) {
-            uint64_t staged;
-            const uint32_t n = ssimf_take(params, i0, count, false, staged);
-            d.resize(n);
-            for (uint32_t i = 0; i < n; ++i) d[i] = make_descf(params[i0 + i], true);
-            if ((rc = ssimf_enqueue(c, n, &d[0], params[0].width, params[0].height, dataRange, sumsDevice + i0))) return rc;
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    return 0;
-}
-
-rmgr_int32_t rmgr_ssim_hip_compute_ssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
-                                                float dataRange, float* ssim) RMGR_NOEXCEPT
-{
-    int rc = ssimf_validate(count, params, dataRange, ssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return ssimf_blocking(c, count, params, dataRange, ssim, false);
-}
-
-rmgr_int32_t rmgr_ssim_hip_compute_ssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
-                                              float dataRange, float* ssim) RMGR_NOEXCEPT
-{
-    int rc = ssimf_validate(count, params, dataRange, ssim);
-    if (rc) return rc;
-    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
-    if ((rc = lease.take(c))) return rc;
-    c = lease.c;
-    USE_DEVICE(c);
-    return ssimf_blocking(c, count, params, dataRange, ssim, true);
-}
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
-                                              float dataRange, const float* gradOutDevice,
-                                              const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
-{
-    int rc = ssimf_validate(count, params, dataRange, gradOutDevice);
-    if (rc) return rc;
-    if (gradA == NULL && gradB == NULL) return EINVAL;
-    for (uint32_t i = 0; i < count; ++i)
-        for (int k = 0; k < 2; ++k) {
-            const rmgr_ssim_hip_GradF* g = k ? gradB : gradA;
-            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 3u))) return EINVAL;
-        }
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
-    const uint32_t nmax = ssim_hip::ssimf_max_count(W, H);
-    for (uint32_t i0 = 0; i0 < count;) {
-        const uint32_t n = std::min(count - i0, nmax);
-        rmgr_ssim_hip_Context_::SfSlot* s;
-        const size_t pair_bytes = n * sizeof(PairFDesc), bytes = pair_bytes + n * sizeof(GradFDesc);
-        if ((rc = ssimf_slot(c, bytes, s))) return rc;
-        PairFDesc* pd = reinterpret_cast<PairFDesc*>(s->pin.get());
-        GradFDesc* gd = reinterpret_cast<GradFDesc*>(s->pin.get() + pair_bytes);
-        for (uint32_t i = 0; i < n; ++i) {
-            pd[i] = make_descf(params[i0 + i], false);
-            GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
-            if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
-            if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
-            gd[i] = g;
-        }
-        HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(ssim_hip::launch_ssimf_grad(W, H, n, reinterpret_cast<const PairFDesc*>(s->dev.get()),
-                                            reinterpret_cast<const GradFDesc*>(s->dev.get() + pair_bytes), gradOutDevice + i0, dataRange, which, c->stream));
-        HIP_TRY(hipEventRecord(s->used, c->stream));
-        s->pending = true;
-        i0 += n;
-    }
-    return 0;
-}
-
-// ---- SSIM of float16 / bfloat16 samples and its gradient (rmgr_ssim_hip_enqueue_ssimh, _compute_ssimh_*, _enqueue_ssimh_grad) -------------------
-// The definition is in include/rmgr/ssim-hip.h, the kernels in ssimh_kernels.hip.  The host flow is the ssimf one with 2-byte samples; it
-// runs on the float path's descriptor ring, partials and pinned sums (one stream, stream order), so the enqueue forms never wait for the
-// host either.  Sums run over fixed cells and gradient pixels over fixed tiles: neither the sub-batches nor the launch a pair lands in
-// change a bit.
-namespace {
-
-using ssim_hip::PairHDesc;
-using ssim_hip::GradHDesc;
-
-// Every check the entry points share, before any device is touched.
-int ssimh_validate(rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params, rmgr_uint32_t sampleType, float dataRange, const void* out)
-{
-    if (count == 0 || params == NULL || out == NULL) return EINVAL;
-    if (sampleType != RMGR_SSIM_HIP_SAMPLE_F16 && sampleType != RMGR_SSIM_HIP_SAMPLE_BF16) return EINVAL;
-    if (!(dataRange > 0.0f) || !std::isfinite(dataRange)) return EINVAL;
-    const uint32_t W = params[0].width, H = params[0].height;
-    if (W == 0 || H == 0 || W > ssim_hip::kSHMaxDim || H > ssim_hip::kSHMaxDim) return EINVAL;
-    for (uint32_t i = 0; i < count; ++i) {
-        const rmgr_ssim_hip_Params16& p = params[i];
-        if (p.width != W || p.height != H) return EINVAL;
-        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
-        if (((uintptr_t)p.imgA.topLeft & 1u) || ((uintptr_t)p.imgB.topLeft & 1u)) return EINVAL;
-    }
-    if (ssim_hip::ssimh_max_count(W, H) == 0) return EINVAL;
-    return 0;
-}
-
-int ssimh_type(rmgr_uint32_t sampleType) { return sampleType == RMGR_SSIM_HIP_SAMPLE_BF16 ? ssim_hip::kSHTypeBF16 : ssim_hip::kSHTypeF16; }
-
-PairHDesc make_desch(const rmgr_ssim_hip_Params16& p, bool with_map)
-{
-    PairHDesc d;
-    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride;
-    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride;
-    const bool m = with_map && p.ssimMap;
-    d.map = m ? p.ssimMap : NULL;
-    d.map_step = m ? p.ssimStep : 0;
-    d.map_stride = m ? p.ssimStride : 0;
-    return d;
-}
-
-uint64_t ssimh_partials_per_pair(uint32_t W, uint32_t H)
-{
-    const ssim_hip::GeometryH g = ssim_hip::planh(W, H, 1, 0);
-    return g.cells_per_image() * sizeof(double);
-}
-
-// Enqueues n pairs (descriptors in host memory, images on the device) on the context's stream: descriptor upload, strip kernel,
-// reduction into sums[0 .. n-1] (device or pinned host memory).  n <= ssimh_max_count and its partials within the cap.
-int ssimh_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const PairHDesc* d, uint32_t W, uint32_t H, int type, float range, double* sums)
-{
-    int rc;
-    rmgr_ssim_hip_Context_::SfSlot* s;
-    if ((rc = ssimf_slot(c, n * sizeof(PairHDesc), s))) return rc;
-    const ssim_hip::GeometryH geo = ssim_hip::planh(W, H, n, c->cu_count);
-    if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_image() * n)))) return rc;
-    bool map = false, unit = (W % 2) == 0, wide = false;
-    for (uint32_t i = 0; i < n; ++i) {
-        map = map || d[i].map != NULL;
-        unit = unit && (d[i].map == NULL || d[i].map_step == 1);
-        wide = wide || !ssim_hip::fitsh_narrow(d[i]);
-    }
-    memcpy(s->pin.get(), d, n * sizeof(PairHDesc));
-    HIP_TRY(hipMemcpyAsync(s->dev, s->pin, n * sizeof(PairHDesc), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(ssim_hip::launch_ssimh(geo, reinterpret_cast<const PairHDesc*>(s->dev.get()), type, map, unit, wide, range, c->xcd_count, c->sf_partials, sums, c->stream));
-    HIP_TRY(hipEventRecord(s->used, c->stream));
-    s->pending = true;
-    return 0;
-}
-
-// Pairs of params[i0 ..] that one sub-batch takes: at least one; within the launch limit and, with the staged images and maps of host
-// pointers, kSFScratchCap of device scratch.
-uint32_t ssimh_take(const rmgr_ssim_hip_Params16* params, uint32_t i0, uint32_t count, bool stage, uint64_t& staged)
-{
-    const uint32_t W = params[0].width, H = params[0].height;
-    const uint64_t part = ssimh_partials_per_pair(W, H);
-    const uint32_t nmax = ssim_hip::ssimh_max_count(W, H);
-    uint32_t n = 0;
-    staged = 0;
-    while (i0 + n < count && n < nmax) {
-        uint64_t bytes = 0;
-        if (stage) {
-            const rmgr_ssim_hip_Params16& p = params[i0 + n];
-            int64_t lo, hi;
-            extent16(p.imgA, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 2 + 63) & ~uint64_t(63);
-            extent16(p.imgB, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 2 + 63) & ~uint64_t(63);
-            if (p.ssimMap) bytes += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
-        }
-        if (n > 0 && part * (n + 1) + staged + bytes > kSFScratchCap) break;
-        staged += bytes;
-        ++n;
-    }
-    return n;
-}
-
-// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the images are copied
-// (each image's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own step and stride.
-int ssimh_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params16* params, int type, float range, float* ssim, bool stage)
-{
-    const uint32_t W = params[0].width, H = params[0].height;
-    const double px = (double)W * (double)H;
-    int rc;
-    if ((rc = c->sf_sums_pin.grow(count))) return rc;
-    try {
-        std::vector<PairHDesc> d;
-        std::vector<float> back;
-        for (uint32_t i0 = 0; i0 < count;) {
-            uint64_t staged;
-            const uint32_t n = ssimh_take(params, i0, count, stage, staged);
-            d.resize(n);
-            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
-            uint64_t off = 0;
-            std::vector<uint64_t> map_off(n, 0);
-            for (uint32_t i = 0; i < n; ++i) {
-                const rmgr_ssim_hip_Params16& p = params[i0 + i];
-                d[i] = make_desch(p, true);
-                if (!stage) continue;
-                for (int k = 0; k < 2; ++k) {
-                    const rmgr_ssim_hip_Img16& im = k ? p.imgB : p.imgA;
-                    int64_t lo, hi;
-                    extent16(im, W, H, lo, hi);
-                    const size_t bytes = (size_t)(hi - lo + 1) * 2;
-                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
-                    (k ? d[i].b : d[i].a) = reinterpret_cast<const uint16_t*>(c->stage_a + off) - lo;
-                    off += (bytes + 63) & ~uint64_t(63);
-                }
-                if (p.ssimMap) {
-                    map_off[i] = off;
-                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
-                    d[i].map_step = 1; d[i].map_stride = W;
-                    off += ((uint64_t)W * H * 4 + 63) & ~uint64_t(63);
-                }
-            }
-            if ((rc = ssimh_enqueue(c, n, &d[0], W, H, type, range, c->sf_sums_pin + i0))) return rc;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            for (uint32_t i = 0; i < n && stage; ++i) {
-                const rmgr_ssim_hip_Params16& p = params[i0 + i];
-                if (!p.ssimMap) continue;
-                const float* src = reinterpret_cast<const float*>(c->stage_a + map_off[i]);
-                if (p.ssimStep == 1 && p.ssimStride == (ptrdiff_t)W) {
-                    HIP_TRY(hipMemcpy(p.ssimMap, src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
-                    continue;
-                }
-                back.resize((size_t)W * H);
-                HIP_TRY(hipMemcpy(&back[0], src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
-                for (uint32_t y = 0; y < H; ++y) {
-                    float* row = p.ssimMap + (ptrdiff_t)y * p.ssimStride;
-                    const float* sr = &back[(size_t)y * W];
-                    for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = sr[x];
-                }
-            }
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->sf_sums_pin[i] / px);
-    return 0;
-}
-
-} // namespace
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
-                                         rmgr_uint32_t sampleType, float dataRange, double* sumsDevice) RMGR_NOEXCEPT
-{
-    int rc = ssimh_validate(count, params, sampleType, dataRange, sumsDevice);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    try {
-        std::vector<PairHDesc> d;
-        for (uint32_t i0 = 0; i0 < count;) {
-            uint64_t staged;
-            const uint32_t n = ssimh_take(params, i0, count, false, staged);
-            d.resize(n);
-            for (uint32_t i = 0; i < n; ++i) d[i] = make_desch(params[i0 + i], true);
-            if ((rc = ssimh_enqueue(c, n, &d[0], params[0].width, params[0].height, ssimh_type(sampleType), dataRange, sumsDevice + i0))) return rc;
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    return 0;
-}
-
-rmgr_int32_t rmgr_ssim_hip_compute_ssimh_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
-                                                rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
-{
-    int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return ssimh_blocking(c, count, params, ssimh_type(sampleType), dataRange, ssim, false);
-}
-
-rmgr_int32_t rmgr_ssim_hip_compute_ssimh_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
-                                              rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
-{
-    int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
-    if (rc) return rc;
-    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
-    if ((rc = lease.take(c))) return rc;
-    c = lease.c;
-    USE_DEVICE(c);
-    return ssimh_blocking(c, count, params, ssimh_type(sampleType), dataRange, ssim, true);
-}
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
-                                              rmgr_uint32_t sampleType, float dataRange, const float* gradOutDevice,
-                                              const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
-{
-    int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutDevice);
-    if (rc) return rc;
-    if (gradA == NULL && gradB == NULL) return EINVAL;
-    for (uint32_t i = 0; i < count; ++i)
-        for (int k = 0; k < 2; ++k) {
-            const rmgr_ssim_hip_GradH* g = k ? gradB : gradA;
-            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 1u))) return EINVAL;
-        }
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
-    const uint32_t nmax = ssim_hip::ssimh_max_count(W, H);
-    for (uint32_t i0 = 0; i0 < count;) {
-        const uint32_t n = std::min(count - i0, nmax);
-        rmgr_ssim_hip_Context_::SfSlot* s;
-        const size_t pair_bytes = n * sizeof(PairHDesc), bytes = pair_bytes + n * sizeof(GradHDesc);
-        if ((rc = ssimf_slot(c, bytes, s))) return rc;
-        PairHDesc* pd = reinterpret_cast<PairHDesc*>(s->pin.get());
-        GradHDesc* gd = reinterpret_cast<GradHDesc*>(s->pin.get() + pair_bytes);
-        for (uint32_t i = 0; i < n; ++i) {
-            pd[i] = make_desch(params[i0 + i], false);
-            GradHDesc g = {NULL, 0, 0, NULL, 0, 0};
-            if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
-            if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
-            gd[i] = g;
-        }
-        HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(ssim_hip::launch_ssimh_grad(W, H, n, reinterpret_cast<const PairHDesc*>(s->dev.get()),
-                                            reinterpret_cast<const GradHDesc*>(s->dev.get() + pair_bytes), ssimh_type(sampleType),
-                                            gradOutDevice + i0, dataRange, which, c->stream));
-        HIP_TRY(hipEventRecord(s->used, c->stream));
-        s->pending = true;
-        i0 += n;
-    }
-    return 0;
-}
-
-// ---- gradient of the SSIM map for a per-pixel upstream gradient (rmgr_ssim_hip_enqueue_ssimf_map_grad, _enqueue_ssimh_map_grad) ---------------
-// The definition is in include/rmgr/ssim-hip.h, the kernels in ssimw_kernels.hip.  The host flow is that of _enqueue_ssimf_grad /
-// _enqueue_ssimh_grad on the same descriptor ring, with one more descriptor per pair: the gMap plane.  Gradient pixels run over fixed tiles,
-// so neither the sub-batches nor the launch a pair lands in change a bit.
-namespace {
-
-using ssim_hip::GradOutFDesc;
-
-// What the map-gradient entries check beyond the _grad entries, before any device is touched.
-int ssimw_validate_maps(rmgr_uint32_t count, const rmgr_ssim_hip_GradOutF* maps)
-{
-    for (uint32_t i = 0; i < count; ++i)
-        if (maps[i].topLeft == NULL || ((uintptr_t)maps[i].topLeft & 3u)) return EINVAL;
-    return 0;
-}
-
-GradOutFDesc make_gout(const rmgr_ssim_hip_GradOutF& m)
-{
-    const GradOutFDesc o = {m.topLeft, (int64_t)m.step, (int64_t)m.stride};
-    return o;
-}
-
-} // namespace
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
-                                                  float dataRange, const rmgr_ssim_hip_GradOutF* gradOutMaps,
-                                                  const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
-{
-    int rc = ssimf_validate(count, params, dataRange, gradOutMaps);
-    if (rc) return rc;
-    if ((rc = ssimw_validate_maps(count, gradOutMaps))) return rc;
-    if (gradA == NULL && gradB == NULL) return EINVAL;
-    for (uint32_t i = 0; i < count; ++i)
-        for (int k = 0; k < 2; ++k) {
-            const rmgr_ssim_hip_GradF* g = k ? gradB : gradA;
-            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 3u))) return EINVAL;
-        }
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
-    const uint32_t nmax = ssim_hip::ssimf_max_count(W, H);
-    for (uint32_t i0 = 0; i0 < count;) {
-        const uint32_t n = std::min(count - i0, nmax);
-        rmgr_ssim_hip_Context_::SfSlot* s;
-        const size_t pair_bytes = n * sizeof(PairFDesc), grad_bytes = n * sizeof(GradFDesc), bytes = pair_bytes + grad_bytes + n * sizeof(GradOutFDesc);
-        if ((rc = ssimf_slot(c, bytes, s))) return rc;
-        PairFDesc* pd = reinterpret_cast<PairFDesc*>(s->pin.get());
-        GradFDesc* gd = reinterpret_cast<GradFDesc*>(s->pin.get() + pair_bytes);
-        GradOutFDesc* od = reinterpret_cast<GradOutFDesc*>(s->pin.get() + pair_bytes + grad_bytes);
-        for (uint32_t i = 0; i < n; ++i) {
-            pd[i] = make_descf(params[i0 + i], false);
-            GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
-            if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
-            if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
-            gd[i] = g;
-            od[i] = make_gout(gradOutMaps[i0 + i]);
-        }
-        HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(ssim_hip::launch_ssimw_grad_f(W, H, n, reinterpret_cast<const PairFDesc*>(s->dev.get()),
-                reinterpret_cast<const GradFDesc*>(s->dev.get() + pair_bytes),
-                reinterpret_cast<const GradOutFDesc*>(s->dev.get() + pair_bytes + grad_bytes), dataRange, which, c->stream));
-        HIP_TRY(hipEventRecord(s->used, c->stream));
-        s->pending = true;
-        i0 += n;
-    }
-    return 0;
-}
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
-                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_GradOutF* gradOutMaps,
-                                                  const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
-{
-    int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutMaps);
-    if (rc) return rc;
-    if ((rc = ssimw_validate_maps(count, gradOutMaps))) return rc;
-    if (gradA == NULL && gradB == NULL) return EINVAL;
-    for (uint32_t i = 0; i < count; ++i)
-        for (int k = 0; k < 2; ++k) {
-            const rmgr_ssim_hip_GradH* g = k ? gradB : gradA;
-            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 1u))) return EINVAL;
-        }
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0), type = ssimh_type(sampleType);
-    const uint32_t nmax = ssim_hip::ssimh_max_count(W, H);
-    for (uint32_t i0 = 0; i0 < count;) {
-        const uint32_t n = std::min(count - i0, nmax);
-        rmgr_ssim_hip_Context_::SfSlot* s;
-        const size_t pair_bytes = n * sizeof(PairHDesc), grad_bytes = n * sizeof(GradHDesc), bytes = pair_bytes + grad_bytes + n * sizeof(GradOutFDesc);
-        if ((rc = ssimf_slot(c, bytes, s))) return rc;
-        PairHDesc* pd = reinterpret_cast<PairHDesc*>(s->pin.get());
-        GradHDesc* gd = reinterpret_cast<GradHDesc*>(s->pin.get() + pair_bytes);
-        GradOutFDesc* od = reinterpret_cast<GradOutFDesc*>(s->pin.get() + pair_bytes + grad_bytes);
-        for (uint32_t i = 0; i < n; ++i) {
-            pd[i] = make_desch(params[i0 + i], false);
-            GradHDesc g = {NULL, 0, 0, NULL, 0, 0};
-            if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
-            if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
-            gd[i] = g;
-            od[i] = make_gout(gradOutMaps[i0 + i]);
-        }
-        HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(ssim_hip::launch_ssimw_grad_h(W, H, n, reinterpret_cast<const PairHDesc*>(s->dev.get()),
-                reinterpret_cast<const GradHDesc*>(s->dev.get() + pair_bytes), type,
-                reinterpret_cast<const GradOutFDesc*>(s->dev.get() + pair_bytes + grad_bytes), dataRange, which, c->stream));
-        HIP_TRY(hipEventRecord(s->used, c->stream));
-        s->pending = true;
-        i0 += n;
-    }
-    return 0;
-}
-
-// ---- multi-scale SSIM of float32 samples and its gradient (rmgr_ssim_hip_enqueue_msssimf, _compute_msssimf_*, _enqueue_msssimf_grad) --------
-// The definition is in include/rmgr/ssim-hip.h, the kernels in msssimf_kernels.hip.  Scale 0 is read where the caller has it; the planes
-// of scales >= 1 (and, in the backward, their gradient planes) are dense planes of the context's scratch, one set per pair, rewritten by
-// every sub-batch in stream order.  Every plane, cell and tile belongs to one pair, so neither the sub-batches nor the launch a pair lands
-// in change a bit.
-namespace {
-
-const uint64_t kMsfScratchCap = uint64_t(1) << 30;
-
-// Every check the entry points share, before any device is touched.
-int msssimf_validate(rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, rmgr_uint32_t scales, const double* weights,
-                     const void* out)
-{
-    int rc = ssimf_validate(count, params, dataRange, out);
-    if (rc) return rc;
-    if (scales < 1 || scales > RMGR_SSIM_HIP_MSSSIM_MAX_SCALES) return EINVAL;
-    if (weights == NULL) {
-        if (scales != 5) return EINVAL;
-    } else {
-        for (uint32_t s = 0; s < scales; ++s)
-            if (!std::isfinite(weights[s]) || weights[s] < 0.0) return EINVAL;
-    }
-    for (uint32_t i = 0; i < count; ++i)
-        if (params[i].ssimMap != NULL) return EINVAL;
-    if (ssim_hip::msssimf_max_count(params[0].width, params[0].height) == 0) return EINVAL;
-    return 0;
-}
-
-// Device scratch one pair needs: the pyramid of both images, grad_planes (0 forward, 1 or 2 backward) coarse gradient pyramids, its
-// cell partials (forward) or coefficients (backward).
-uint64_t msf_pair_bytes(uint32_t W, uint32_t H, uint32_t scales, int grad_planes)
-{
-    const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
-    return (2 + (uint64_t)grad_planes) * pyr * sizeof(float) +
-           (grad_planes ? scales * sizeof(float) : ssim_hip::msf_partials(W, H, 1, scales) * sizeof(double));
-}
-
-// Pairs one sub-batch takes when none of them is staged: at least one.
-uint32_t msf_take(uint32_t W, uint32_t H, uint32_t scales, int grad_planes, uint32_t left)
-{
-    const uint64_t fit = std::max<uint64_t>(1, kMsfScratchCap / msf_pair_bytes(W, H, scales, grad_planes));
-    return (uint32_t)std::min<uint64_t>(std::min<uint64_t>(left, ssim_hip::msssimf_max_count(W, H)), fit);
-}
-
-// Fills table[scale][pair] (scales x n): scale 0 from d, scales >= 1 dense planes of `pyramid`, scale by scale, A then B of each pair.
-void msf_fill_descs(PairFDesc* table, const PairFDesc* d, uint32_t n, uint32_t W, uint32_t H, uint32_t scales, float* pyramid)
-{
-    for (uint32_t i = 0; i < n; ++i) { table[i] = d[i]; table[i].map = NULL; table[i].map_step = table[i].map_stride = 0; }
-    float* at = pyramid;
-    for (uint32_t s = 1; s < scales; ++s) {
-        const uint64_t plane = ssim_hip::msf_plane(W, H, s);
-        const int64_t stride = ssim_hip::msf_dim(W, s);
-        for (uint32_t i = 0; i < n; ++i) {
-            PairFDesc& t = table[(size_t)s * n + i];
-            t.a = at; t.a_step = 1; t.a_stride = stride; at += plane;
-            t.b = at; t.b_step = 1; t.b_stride = stride; at += plane;
-            t.map = NULL; t.map_step = t.map_stride = 0;
-        }
-    }
-}
-
-// Enqueues the forward of n pairs (scale-0 descriptors in host memory, images on the device) on the context's stream: n x scales x 2
-// means and n values into device memory.
-int msssimf_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const PairFDesc* d, uint32_t W, uint32_t H, float range, uint32_t scales,
-                    const double* w, double* means, double* values)
-{
-    int rc;
-    if ((rc = c->msf_pyramid.grow((size_t)(2 * ssim_hip::msf_pyramid_floats(W, H, scales) * n)))) return rc;
-    if ((rc = c->msf_partials.grow((size_t)ssim_hip::msf_partials(W, H, n, scales)))) return rc;
-    rmgr_ssim_hip_Context_::SfSlot* s;
-    const size_t bytes = (size_t)scales * n * sizeof(PairFDesc);
-    if ((rc = ssimf_slot(c, bytes, s))) return rc;
-    msf_fill_descs(reinterpret_cast<PairFDesc*>(s->pin.get()), d, n, W, H, scales, c->msf_pyramid);
-    bool wide = false;
-    for (uint32_t i = 0; i < n; ++i) wide = wide || !ssim_hip::fitsf_narrow(d[i]);
-    HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(ssim_hip::launch_msssimf(reinterpret_cast<const PairFDesc*>(s->dev.get()), n, W, H, scales, wide, range, w, c->cu_count, c->xcd_count,
-                                     c->msf_partials, means, values, c->stream));
-    HIP_TRY(hipEventRecord(s->used, c->stream));
-    s->pending = true;
-    return 0;
-}
-
-// The blocking entry points: every sub-batch into c->msf_out (count values, then count x scales x 2 means), one copy back, one wait.
-// stage: host pointers -- each sub-batch's images are copied (each image's sample range) into c->stage_a first.
-int msssimf_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float range, uint32_t scales, const double* w,
-                     float* msssim, double* scaleMeans, bool stage)
-{
-    const uint32_t W = params[0].width, H = params[0].height;
-    const size_t per = 1 + 2 * (size_t)scales, total = per * count;
-    const uint64_t pair_bytes = msf_pair_bytes(W, H, scales, 0);
-    int rc;
-    if ((rc = c->msf_out.grow(total))) return rc;
-    if ((rc = c->msf_out_pin.grow(total))) return rc;
-    double* values = c->msf_out;
-    double* means = c->msf_out + count;
-    try {
-        std::vector<PairFDesc> d;
-        for (uint32_t i0 = 0; i0 < count;) {
-            uint32_t n = msf_take(W, H, scales, 0, count - i0);
-            uint64_t staged = 0;
-            if (stage) {                    // the staged images count against the same cap
-                uint32_t m = 0;
-                while (m < n) {
-                    uint64_t bytes = 0;
-                    int64_t lo, hi;
-                    extentf(params[i0 + m].imgA, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 4 + 63) & ~uint64_t(63);
-                    extentf(params[i0 + m].imgB, W, H, lo, hi); bytes += ((uint64_t)(hi - lo + 1) * 4 + 63) & ~uint64_t(63);
-                    if (m > 0 && pair_bytes * (m + 1) + staged + bytes > kMsfScratchCap) break;
-                    staged += bytes;
-                    ++m;
-                }
-                n = m;
-                if ((rc = c->stage_a.grow((size_t)staged))) return rc;
-            }
-            d.resize(n);
-            uint64_t off = 0;
-            for (uint32_t i = 0; i < n; ++i) {
-                const rmgr_ssim_hip_ParamsF& p = params[i0 + i];
-                d[i] = make_descf(p, false);
-                for (int k = 0; k < 2 && stage; ++k) {
-                    const rmgr_ssim_hip_ImgF& im = k ? p.imgB : p.imgA;
-                    int64_t lo, hi;
-                    extentf(im, W, H, lo, hi);
-                    const size_t bytes = (size_t)(hi - lo + 1) * 4;
-                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
-                    (k ? d[i].b : d[i].a) = reinterpret_cast<const float*>(c->stage_a + off) - lo;
-                    off += (bytes + 63) & ~uint64_t(63);
-                }
-            }
-            if ((rc = msssimf_enqueue(c, n, &d[0], W, H, range, scales, w, means + (size_t)i0 * scales * 2, values + i0))) return rc;
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    HIP_TRY(hipMemcpyAsync(c->msf_out_pin, c->msf_out, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < count; ++i) msssim[i] = (float)c->msf_out_pin[i];
-    if (scaleMeans) memcpy(scaleMeans, c->msf_out_pin + count, (size_t)count * scales * 2 * sizeof(double));
-    return 0;
-}
-
-} // namespace
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
-                                           rmgr_uint32_t scales, const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
-{
-    int rc = msssimf_validate(count, params, dataRange, scales, weights, valuesDevice);
-    if (rc) return rc;
-    if (scaleMeansDevice == NULL || !c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    try {
-        std::vector<PairFDesc> d;
-        for (uint32_t i0 = 0; i0 < count;) {
-            const uint32_t n = msf_take(W, H, scales, 0, count - i0);
-            d.resize(n);
-            for (uint32_t i = 0; i < n; ++i) d[i] = make_descf(params[i0 + i], false);
-            if ((rc = msssimf_enqueue(c, n, &d[0], W, H, dataRange, scales, weights ? weights : kWangWeights,
-                                      scaleMeansDevice + (size_t)i0 * scales * 2, valuesDevice + i0))) return rc;
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    return 0;
-}
-
-rmgr_int32_t rmgr_ssim_hip_compute_msssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
-                                                  rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
-{
-    int rc = msssimf_validate(count, params, dataRange, scales, weights, msssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return msssimf_blocking(c, count, params, dataRange, scales, weights ? weights : kWangWeights, msssim, scaleMeans, false);
-}
-
-rmgr_int32_t rmgr_ssim_hip_compute_msssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
-                                                rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
-{
-    int rc = msssimf_validate(count, params, dataRange, scales, weights, msssim);
-    if (rc) return rc;
-    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
-    if ((rc = lease.take(c))) return rc;
-    c = lease.c;
-    USE_DEVICE(c);
-    return msssimf_blocking(c, count, params, dataRange, scales, weights ? weights : kWangWeights, msssim, scaleMeans, true);
-}
-
-rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
-                                                rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
-                                                const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
-{
-    int rc = msssimf_validate(count, params, dataRange, scales, weights, gradOutDevice);
-    if (rc) return rc;
-    if (scaleMeansDevice == NULL || (gradA == NULL && gradB == NULL)) return EINVAL;
-    for (uint32_t i = 0; i < count; ++i)
-        for (int k = 0; k < 2; ++k) {
-            const rmgr_ssim_hip_GradF* g = k ? gradB : gradA;
-            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 3u))) return EINVAL;
-        }
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0), planes = (gradA ? 1 : 0) + (gradB ? 1 : 0);
-    const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
-    const double* w = weights ? weights : kWangWeights;
-    try {
-        std::vector<PairFDesc> d;
-        for (uint32_t i0 = 0; i0 < count;) {
-            const uint32_t n = msf_take(W, H, scales, planes, count - i0);
-            if ((rc = c->msf_pyramid.grow((size_t)(2 * pyr * n)))) return rc;
-            if ((rc = c->msf_grads.grow((size_t)((uint64_t)planes * pyr * n)))) return rc;
-            if ((rc = c->msf_coef.grow((size_t)n * scales))) return rc;
-            rmgr_ssim_hip_Context_::SfSlot* s;
-            const size_t pair_bytes = (size_t)scales * n * sizeof(PairFDesc), bytes = pair_bytes + (size_t)scales * n * sizeof(GradFDesc);
-            if ((rc = ssimf_slot(c, bytes, s))) return rc;
-            d.resize(n);
-            for (uint32_t i = 0; i < n; ++i) d[i] = make_descf(params[i0 + i], false);
-            msf_fill_descs(reinterpret_cast<PairFDesc*>(s->pin.get()), &d[0], n, W, H, scales, c->msf_pyramid);
-            // gradient planes: scale 0 the caller's, scales >= 1 dense scratch, scale by scale, dA then dB of each pair
-            GradFDesc* gd = reinterpret_cast<GradFDesc*>(s->pin.get() + pair_bytes);
-            float* at = c->msf_grads;
-            for (uint32_t sc = 0; sc < scales; ++sc) {
-                const uint64_t plane = ssim_hip::msf_plane(W, H, sc);
-                const int64_t stride = ssim_hip::msf_dim(W, sc);
-                for (uint32_t i = 0; i < n; ++i) {
-                    GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
-                    if (sc == 0) {
-                        if (gradA) { g.ga = gradA[i0 + i].topLeft; g.ga_step = gradA[i0 + i].step; g.ga_stride = gradA[i0 + i].stride; }
-                        if (gradB) { g.gb = gradB[i0 + i].topLeft; g.gb_step = gradB[i0 + i].step; g.gb_stride = gradB[i0 + i].stride; }
-                    } else {
-                        if (gradA) { g.ga = at; g.ga_step = 1; g.ga_stride = stride; at += plane; }
-                        if (gradB) { g.gb = at; g.gb_step = 1; g.gb_stride = stride; at += plane; }
-                    }
-                    gd[(size_t)sc * n + i] = g;
-                }
-            }
-            HIP_TRY(hipMemcpyAsync(s->dev, s->pin, bytes, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(ssim_hip::launch_msssimf_grad(reinterpret_cast<const PairFDesc*>(s->dev.get()), reinterpret_cast<const GradFDesc*>(s->dev.get() + pair_bytes),
-                                                  n, W, H, scales, dataRange, w, scaleMeansDevice + (size_t)i0 * scales * 2, gradOutDevice + i0,
-                                                  c->msf_coef, which, c->stream));
-            HIP_TRY(hipEventRecord(s->used, c->stream));
-            s->pending = true;
-            i0 += n;
-        }
-    } catch (...) {
-        return ENOMEM;
-    }
-    return 0;
 }
 
 // ---- one process, several devices ------------------------------------------------------------------------------------

@@ -1,0 +1,794 @@
+// ssim_samples_abi.cpp -- the entry points of the C ABI for samples other than 8-bit ones (the 8-bit path: ssim_hip_abi.cpp): SSIM of
+// 9- to 16-bit integers (ssim16), of float32 (ssimf) and of float16 / bfloat16 samples (ssimh), the gradients of the latter two for a
+// scalar and for a per-pixel upstream gradient (ssimw), and multi-scale SSIM of float32 samples with its gradient (msssimf).  The
+// definitions are in include/rmgr/ssim-hip.h, the kernels in ssim16_ / ssimf_ / ssimh_ / ssimw_ / msssimf_kernels.hip.
+//
+// The three single-scale families differ in their sample type and in what a launch is told (bit depth; data range; encoding and data
+// range); each is described once by a small struct (Family16 / FamilyF / FamilyH) and the host flow -- validation, sub-batches, staging
+// of host images, enqueue, strided map copy-back -- is written once over it.  The multi-scale path uses the same pieces.
+//
+// Every pair's sum runs over fixed cells in a fixed order, every gradient pixel belongs to one fixed tile, and every pyramid plane, cell
+// and tile of the multi-scale path belongs to one pair: neither the sub-batches (kScratchCap of partials, pyramids, staged images and
+// maps per sub-batch) nor the launch a pair lands in change a bit.
+//
+// Every family runs on one ring of descriptor tables, one buffer of cell partials and one of pinned sums (sf_slots, sf_partials,
+// sf_sums_pin of the context): one stream, stream order.  An enqueue form therefore never waits for the host, except -- at most -- for
+// the launch that read its ring slot kSfSlots enqueues ago.
+#include "ssim_context.h"
+#include "ssimh_kernels.h"
+#include "ssimw_kernels.h"
+
+#include <cmath>
+
+using namespace ssim_host;
+
+namespace {
+
+using ssim_hip::Pair16Desc;
+using ssim_hip::PairFDesc;
+using ssim_hip::GradFDesc;
+using ssim_hip::PairHDesc;
+using ssim_hip::GradHDesc;
+using ssim_hip::GradOutFDesc;
+
+const uint64_t kScratchCap = uint64_t(1) << 30;     // device scratch (partials, pyramids, staged images and maps) of one sub-batch
+
+// ---- the families ------------------------------------------------------------------------------------------------------------------------------
+// Params / Desc / Sample: the public parameter block, the kernels' descriptor of a pair, the type of a sample.  launch() enqueues the
+// strip kernel and the reduction of geo.count pairs into sums (device or pinned host memory); the per-call arguments are its members.
+
+struct Family16 {
+    typedef rmgr_ssim_hip_Params16 Params;
+    typedef Pair16Desc Desc;
+    typedef uint16_t Sample;
+    typedef ssim_hip::Geometry16 Geometry;
+    static constexpr uint32_t kMaxDim = ssim_hip::kS16MaxDim;
+    static uint32_t max_count(uint32_t W, uint32_t H) { return ssim_hip::ssim16_max_count(W, H); }
+    static Geometry plan(uint32_t W, uint32_t H, uint32_t n, int cus) { return ssim_hip::plan16(W, H, n, cus); }
+    static bool fits_narrow(const Desc& d) { return ssim_hip::fits16_narrow(d); }
+    uint32_t depth;
+    hipError_t launch(rmgr_ssim_hip_Context* c, const Geometry& geo, const Desc* dev, bool map, bool unit, bool wide, double* sums) const
+    { return ssim_hip::launch_ssim16(geo, dev, map, unit, wide, depth, c->xcd_count, c->sf_partials, sums, c->stream); }
+};
+
+struct FamilyF {
+    typedef rmgr_ssim_hip_ParamsF Params;
+    typedef rmgr_ssim_hip_GradF Grad;
+    typedef PairFDesc Desc;
+    typedef GradFDesc GradDesc;
+    typedef float Sample;
+    typedef ssim_hip::GeometryF Geometry;
+    static constexpr uint32_t kMaxDim = ssim_hip::kSFMaxDim;
+    static uint32_t max_count(uint32_t W, uint32_t H) { return ssim_hip::ssimf_max_count(W, H); }
+    static Geometry plan(uint32_t W, uint32_t H, uint32_t n, int cus) { return ssim_hip::planf(W, H, n, cus); }
+    static bool fits_narrow(const Desc& d) { return ssim_hip::fitsf_narrow(d); }
+    float range;
+    hipError_t launch(rmgr_ssim_hip_Context* c, const Geometry& geo, const Desc* dev, bool map, bool unit, bool wide, double* sums) const
+    { return ssim_hip::launch_ssimf(geo, dev, map, unit, wide, range, c->xcd_count, c->sf_partials, sums, c->stream); }
+};
+
+struct FamilyH {
+    typedef rmgr_ssim_hip_Params16 Params;
+    typedef rmgr_ssim_hip_GradH Grad;
+    typedef PairHDesc Desc;
+    typedef GradHDesc GradDesc;
+    typedef uint16_t Sample;
+    typedef ssim_hip::GeometryH Geometry;
+    static constexpr uint32_t kMaxDim = ssim_hip::kSHMaxDim;
+    static uint32_t max_count(uint32_t W, uint32_t H) { return ssim_hip::ssimh_max_count(W, H); }
+    static Geometry plan(uint32_t W, uint32_t H, uint32_t n, int cus) { return ssim_hip::planh(W, H, n, cus); }
+    static bool fits_narrow(const Desc& d) { return ssim_hip::fitsh_narrow(d); }
+    int type;           // kSHTypeF16 / kSHTypeBF16
+    float range;
+    hipError_t launch(rmgr_ssim_hip_Context* c, const Geometry& geo, const Desc* dev, bool map, bool unit, bool wide, double* sums) const
+    { return ssim_hip::launch_ssimh(geo, dev, type, map, unit, wide, range, c->xcd_count, c->sf_partials, sums, c->stream); }
+};
+
+// ---- validation, before any device is touched -----------------------------------------------------------------------------------------------
+
+// What every entry point checks of its pairs; `out` is whichever output the entry requires.
+template <typename F>
+int validate_pairs(uint32_t count, const typename F::Params* params, const void* out)
+{
+    if (count == 0 || params == NULL || out == NULL) return EINVAL;
+    const uint32_t W = params[0].width, H = params[0].height;
+    if (W == 0 || H == 0 || W > F::kMaxDim || H > F::kMaxDim) return EINVAL;
+    const uintptr_t mask = sizeof(typename F::Sample) - 1;
+    for (uint32_t i = 0; i < count; ++i) {
+        const typename F::Params& p = params[i];
+        if (p.width != W || p.height != H) return EINVAL;
+        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
+        if (((uintptr_t)p.imgA.topLeft & mask) || ((uintptr_t)p.imgB.topLeft & mask)) return EINVAL;
+    }
+    if (F::max_count(W, H) == 0) return EINVAL;
+    return 0;
+}
+
+bool valid_range(float r) { return r > 0.0f && std::isfinite(r); }
+
+int ssim16_validate(uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t bitDepth, const void* out)
+{
+    if (bitDepth < RMGR_SSIM_HIP_SSIM16_MIN_DEPTH || bitDepth > RMGR_SSIM_HIP_SSIM16_MAX_DEPTH) return EINVAL;
+    return validate_pairs<Family16>(count, params, out);
+}
+
+int ssimf_validate(uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const void* out)
+{
+    if (!valid_range(dataRange)) return EINVAL;
+    return validate_pairs<FamilyF>(count, params, out);
+}
+
+int ssimh_validate(uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t sampleType, float dataRange, const void* out)
+{
+    if (sampleType != RMGR_SSIM_HIP_SAMPLE_F16 && sampleType != RMGR_SSIM_HIP_SAMPLE_BF16) return EINVAL;
+    if (!valid_range(dataRange)) return EINVAL;
+    return validate_pairs<FamilyH>(count, params, out);
+}
+
+int ssimh_type(uint32_t sampleType) { return sampleType == RMGR_SSIM_HIP_SAMPLE_BF16 ? ssim_hip::kSHTypeBF16 : ssim_hip::kSHTypeF16; }
+
+// The planes of a gradient entry: gradA and / or gradB, every plane non-NULL and aligned to its samples.
+template <typename G>
+int validate_grads(uint32_t count, const G* gradA, const G* gradB)
+{
+    if (gradA == NULL && gradB == NULL) return EINVAL;
+    const uintptr_t mask = sizeof(*gradA->topLeft) - 1;
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const G* g = k ? gradB : gradA;
+            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & mask))) return EINVAL;
+        }
+    return 0;
+}
+
+// What the map-gradient entries check beyond the _grad entries.
+int validate_grad_maps(uint32_t count, const rmgr_ssim_hip_GradOutF* maps)
+{
+    for (uint32_t i = 0; i < count; ++i)
+        if (maps[i].topLeft == NULL || ((uintptr_t)maps[i].topLeft & 3u)) return EINVAL;
+    return 0;
+}
+
+// ---- descriptors ---------------------------------------------------------------------------------------------------------------------------------
+
+template <typename F>
+typename F::Desc make_desc(const typename F::Params& p, bool with_map)
+{
+    typename F::Desc d;
+    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride;
+    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride;
+    const bool m = with_map && p.ssimMap;
+    d.map = m ? p.ssimMap : NULL;
+    d.map_step = m ? p.ssimStep : 0;
+    d.map_stride = m ? p.ssimStride : 0;
+    return d;
+}
+
+// The gradient planes of pair i: those of gradA / gradB that the caller wants.
+template <typename F>
+typename F::GradDesc make_grad_desc(const typename F::Grad* gradA, const typename F::Grad* gradB, uint32_t i)
+{
+    typename F::GradDesc g = {NULL, 0, 0, NULL, 0, 0};
+    if (gradA) { g.ga = gradA[i].topLeft; g.ga_step = gradA[i].step; g.ga_stride = gradA[i].stride; }
+    if (gradB) { g.gb = gradB[i].topLeft; g.gb_step = gradB[i].step; g.gb_stride = gradB[i].stride; }
+    return g;
+}
+
+template <typename G> int grad_which(const G* gradA, const G* gradB) { return (gradA ? 1 : 0) | (gradB ? 2 : 0); }
+
+GradOutFDesc make_gout(const rmgr_ssim_hip_GradOutF& m)
+{
+    const GradOutFDesc o = {m.topLeft, (int64_t)m.step, (int64_t)m.stride};
+    return o;
+}
+
+// ---- sub-batches and staging -------------------------------------------------------------------------------------------------------------------
+
+uint64_t round64(uint64_t bytes) { return (bytes + 63) & ~uint64_t(63); }
+
+// The bytes of the sample range of a width x height image; lo: where the range starts, in samples relative to topLeft (<= 0).
+template <typename F, typename Img>
+size_t image_bytes(const Img& im, uint32_t w, uint32_t h, int64_t& lo)
+{
+    const int64_t dx = (int64_t)(w - 1) * (int64_t)im.step, dy = (int64_t)(h - 1) * (int64_t)im.stride;
+    lo = (dx < 0 ? dx : 0) + (dy < 0 ? dy : 0);
+    const int64_t hi = (dx > 0 ? dx : 0) + (dy > 0 ? dy : 0);
+    return (size_t)(hi - lo + 1) * sizeof(typename F::Sample);
+}
+
+template <typename F> uint64_t partials_per_pair(uint32_t W, uint32_t H) { return F::plan(W, H, 1, 0).cells_per_image() * sizeof(double); }
+
+// Pairs of params[i0 ..] that one sub-batch takes: at least one; at most nmax (the launch limit) and, with `scratch` bytes per pair and
+// -- stage: host pointers -- the staged images (with_maps: and maps) of each pair, kScratchCap of device scratch.  staged: the bytes
+// its staged images and maps take, each rounded up to 64.
+template <typename F>
+uint32_t take(const typename F::Params* params, uint32_t i0, uint32_t count, uint32_t nmax, uint64_t scratch, bool stage, bool with_maps,
+              uint64_t& staged)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    uint32_t n = 0;
+    staged = 0;
+    while (i0 + n < count && n < nmax) {
+        uint64_t bytes = 0;
+        if (stage) {
+            const typename F::Params& p = params[i0 + n];
+            int64_t lo;
+            bytes += round64(image_bytes<F>(p.imgA, W, H, lo)) + round64(image_bytes<F>(p.imgB, W, H, lo));
+            if (with_maps && p.ssimMap) bytes += round64((uint64_t)W * H * 4);
+        }
+        if (n > 0 && scratch * (n + 1) + staged + bytes > kScratchCap) break;
+        staged += bytes;
+        ++n;
+    }
+    return n;
+}
+
+// Host pointers: copies the sample range of both images of p to c->stage_a + off (off moves on, in steps of 64) on the context's stream
+// and points d at the copies.
+template <typename F>
+int stage_images(rmgr_ssim_hip_Context* c, const typename F::Params& p, uint32_t W, uint32_t H, typename F::Desc& d, uint64_t& off)
+{
+    for (int k = 0; k < 2; ++k) {
+        const auto& im = k ? p.imgB : p.imgA;
+        int64_t lo;
+        const size_t bytes = image_bytes<F>(im, W, H, lo);
+        HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
+        (k ? d.b : d.a) = reinterpret_cast<const typename F::Sample*>(c->stage_a + off) - lo;
+        off += round64(bytes);
+    }
+    return 0;
+}
+
+// Copies a dense W x H map in device memory to the caller's map at its own step and stride (blocking).
+int copy_map_back(const float* src, float* map, ptrdiff_t step, ptrdiff_t stride, uint32_t W, uint32_t H, std::vector<float>& back)
+{
+    if (step == 1 && stride == (ptrdiff_t)W) {
+        HIP_TRY(hipMemcpy(map, src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    back.resize((size_t)W * H);
+    HIP_TRY(hipMemcpy(&back[0], src, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+    for (uint32_t y = 0; y < H; ++y) {
+        float* row = map + (ptrdiff_t)y * stride;
+        const float* s = &back[(size_t)y * W];
+        for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * step] = s[x];
+    }
+    return 0;
+}
+
+// ---- the ring of descriptor tables -----------------------------------------------------------------------------------------------------------
+
+// One launch that reads a table of `bytes` from the next slot of the ring: waits, at most, for the launch that read the slot kSfSlots
+// enqueues ago; fill(pinned) writes the table, launch(device) enqueues its reader.
+template <typename Fill, typename Launch>
+int ring_launch(rmgr_ssim_hip_Context* c, size_t bytes, Fill fill, Launch launch)
+{
+    rmgr_ssim_hip_Context_::SfSlot& s = c->sf_slots[c->sf_next];
+    c->sf_next = (c->sf_next + 1) % rmgr_ssim_hip_Context_::kSfSlots;
+    if (s.pending) {
+        HIP_TRY(hipEventSynchronize(s.used));
+        s.pending = false;
+    }
+    HIP_TRY(s.used.ensure());
+    int rc;
+    if ((rc = s.pin.grow(bytes))) return rc;
+    if ((rc = s.dev.grow(bytes))) return rc;
+    fill(s.pin.get());
+    HIP_TRY(hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch(const_cast<const uint8_t*>(s.dev.get())));
+    HIP_TRY(hipEventRecord(s.used, c->stream));
+    s.pending = true;
+    return 0;
+}
+
+// ---- the forward flow -----------------------------------------------------------------------------------------------------------------------------
+
+// Enqueues n pairs (descriptors in host memory, images on the device) on the context's stream: descriptor upload, strip kernel,
+// reduction into sums[0 .. n-1] (device or pinned host memory).  n <= F::max_count and its partials within the cap.
+template <typename F>
+int enqueue_pairs(rmgr_ssim_hip_Context* c, const F& fam, uint32_t n, const typename F::Desc* d, uint32_t W, uint32_t H, double* sums)
+{
+    typedef typename F::Desc Desc;
+    const typename F::Geometry geo = F::plan(W, H, n, c->cu_count);
+    int rc;
+    if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_image() * n)))) return rc;
+    bool map = false, unit = (W % 2) == 0, wide = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        map = map || d[i].map != NULL;
+        unit = unit && (d[i].map == NULL || d[i].map_step == 1);
+        wide = wide || !F::fits_narrow(d[i]);
+    }
+    return ring_launch(c, n * sizeof(Desc),
+        [&](uint8_t* pin) { memcpy(pin, d, n * sizeof(Desc)); },
+        [&](const uint8_t* dev) { return fam.launch(c, geo, reinterpret_cast<const Desc*>(dev), map, unit, wide, sums); });
+}
+
+// The enqueue entry points: every sub-batch of device-resident pairs into sums[0 .. count-1] (device), no host synchronisation.
+template <typename F>
+int enqueue_all(rmgr_ssim_hip_Context* c, const F& fam, uint32_t count, const typename F::Params* params, double* sums)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    try {
+        std::vector<typename F::Desc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = take<F>(params, i0, count, F::max_count(W, H), partials_per_pair<F>(W, H), false, false, staged);
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) d[i] = make_desc<F>(params[i0 + i], true);
+            const int rc = enqueue_pairs(c, fam, n, &d[0], W, H, sums + i0);
+            if (rc) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the images are copied
+// (each image's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own step and stride.
+template <typename F>
+int blocking(rmgr_ssim_hip_Context* c, const F& fam, uint32_t count, const typename F::Params* params, float* ssim, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    const double px = (double)W * (double)H;
+    int rc;
+    if ((rc = c->sf_sums_pin.grow(count))) return rc;
+    try {
+        std::vector<typename F::Desc> d;
+        std::vector<uint64_t> map_off;
+        std::vector<float> back;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = take<F>(params, i0, count, F::max_count(W, H), partials_per_pair<F>(W, H), stage, true, staged);
+            d.resize(n);
+            map_off.assign(n, 0);
+            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
+            uint64_t off = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                const typename F::Params& p = params[i0 + i];
+                d[i] = make_desc<F>(p, true);
+                if (!stage) continue;
+                if ((rc = stage_images<F>(c, p, W, H, d[i], off))) return rc;
+                if (p.ssimMap) {
+                    map_off[i] = off;
+                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
+                    d[i].map_step = 1; d[i].map_stride = W;
+                    off += round64((uint64_t)W * H * 4);
+                }
+            }
+            if ((rc = enqueue_pairs(c, fam, n, &d[0], W, H, c->sf_sums_pin + i0))) return rc;
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (uint32_t i = 0; i < n && stage; ++i) {
+                const typename F::Params& p = params[i0 + i];
+                if (!p.ssimMap) continue;
+                const float* src = reinterpret_cast<const float*>(c->stage_a + map_off[i]);
+                if ((rc = copy_map_back(src, p.ssimMap, p.ssimStep, p.ssimStride, W, H, back))) return rc;
+            }
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->sf_sums_pin[i] / px);
+    return 0;
+}
+
+// The blocking entry point of host pointers: ctx == NULL runs on one of the default contexts, for this call only.
+template <typename F>
+int blocking_host(rmgr_ssim_hip_Context* c, const F& fam, uint32_t count, const typename F::Params* params, float* ssim)
+{
+    Lease lease;
+    int rc = lease.take(c);
+    if (rc) return rc;
+    USE_DEVICE(lease.c);
+    return blocking(lease.c, fam, count, params, ssim, true);
+}
+
+// ---- the single-scale gradients -----------------------------------------------------------------------------------------------------------------
+
+// The gradient entries of one scale: one fused launch per sub-batch of at most F::max_count pairs, without scratch.  Its ring slot holds
+// the pair descriptors, the gradient descriptors and -- maps != NULL: the map gradient -- the descriptors of the upstream planes;
+// launch(n, i0, pairs, grads, maps) enqueues the kernel on the device copies of the three tables.
+template <typename F, typename Launch>
+int enqueue_grads(rmgr_ssim_hip_Context* c, uint32_t count, const typename F::Params* params, const typename F::Grad* gradA,
+                  const typename F::Grad* gradB, const rmgr_ssim_hip_GradOutF* maps, Launch launch)
+{
+    typedef typename F::Desc Desc;
+    typedef typename F::GradDesc GradDesc;
+    const uint32_t nmax = F::max_count(params[0].width, params[0].height);
+    for (uint32_t i0 = 0; i0 < count;) {
+        const uint32_t n = std::min(count - i0, nmax);
+        const size_t pair_bytes = n * sizeof(Desc), grad_bytes = n * sizeof(GradDesc), bytes = pair_bytes + grad_bytes + (maps ? n * sizeof(GradOutFDesc) : 0);
+        const int rc = ring_launch(c, bytes,
+            [&](uint8_t* pin) {
+                Desc* pd = reinterpret_cast<Desc*>(pin);
+                GradDesc* gd = reinterpret_cast<GradDesc*>(pin + pair_bytes);
+                GradOutFDesc* od = reinterpret_cast<GradOutFDesc*>(pin + pair_bytes + grad_bytes);
+                for (uint32_t i = 0; i < n; ++i) {
+                    pd[i] = make_desc<F>(params[i0 + i], false);
+                    gd[i] = make_grad_desc<F>(gradA, gradB, i0 + i);
+                    if (maps) od[i] = make_gout(maps[i0 + i]);
+                }
+            },
+            [&](const uint8_t* dev) {
+                return launch(n, i0, reinterpret_cast<const Desc*>(dev), reinterpret_cast<const GradDesc*>(dev + pair_bytes),
+                              reinterpret_cast<const GradOutFDesc*>(dev + pair_bytes + grad_bytes));
+            });
+        if (rc) return rc;
+        i0 += n;
+    }
+    return 0;
+}
+
+// ---- multi-scale SSIM of float32 samples ---------------------------------------------------------------------------------------------------
+// Scale 0 is read where the caller has it; the planes of scales >= 1 (and, in the backward, their gradient planes) are dense planes of
+// the context's scratch, one set per pair, rewritten by every sub-batch in stream order.
+
+// Every check the entry points share.
+int msssimf_validate(uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, uint32_t scales, const double* weights, const void* out)
+{
+    int rc = ssimf_validate(count, params, dataRange, out);
+    if (rc) return rc;
+    if (scales < 1 || scales > RMGR_SSIM_HIP_MSSSIM_MAX_SCALES) return EINVAL;
+    if (weights == NULL) {
+        if (scales != 5) return EINVAL;
+    } else {
+        for (uint32_t s = 0; s < scales; ++s)
+            if (!std::isfinite(weights[s]) || weights[s] < 0.0) return EINVAL;
+    }
+    for (uint32_t i = 0; i < count; ++i)
+        if (params[i].ssimMap != NULL) return EINVAL;
+    if (ssim_hip::msssimf_max_count(params[0].width, params[0].height) == 0) return EINVAL;
+    return 0;
+}
+
+// Device scratch one pair needs: the pyramid of both images, grad_planes (0 forward, 1 or 2 backward) coarse gradient pyramids, its
+// cell partials (forward) or coefficients (backward).
+uint64_t msf_pair_bytes(uint32_t W, uint32_t H, uint32_t scales, int grad_planes)
+{
+    const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
+    return (2 + (uint64_t)grad_planes) * pyr * sizeof(float) +
+           (grad_planes ? scales * sizeof(float) : ssim_hip::msf_partials(W, H, 1, scales) * sizeof(double));
+}
+
+// Pairs of params[i0 ..] one sub-batch takes (take() with a pair's multi-scale scratch; staged images count against the same cap).
+uint32_t msf_take(const rmgr_ssim_hip_ParamsF* params, uint32_t i0, uint32_t count, uint32_t scales, int grad_planes, bool stage, uint64_t& staged)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    return take<FamilyF>(params, i0, count, ssim_hip::msssimf_max_count(W, H), msf_pair_bytes(W, H, scales, grad_planes), stage, false, staged);
+}
+
+
+// Fills rows 1 .. scales-1 of table[scale][pair] (scales x n; row 0, the caller's scale-0 descriptors without maps, is the caller's to
+// write): dense planes of `pyramid`, scale by scale, A then B of each pair.
+void msf_fill_coarse(PairFDesc* table, uint32_t n, uint32_t W, uint32_t H, uint32_t scales, float* pyramid)
+{
+    float* at = pyramid;
+    for (uint32_t s = 1; s < scales; ++s) {
+        const uint64_t plane = ssim_hip::msf_plane(W, H, s);
+        const int64_t stride = ssim_hip::msf_dim(W, s);
+        for (uint32_t i = 0; i < n; ++i) {
+            PairFDesc& t = table[(size_t)s * n + i];
+            t.a = at; t.a_step = 1; t.a_stride = stride; at += plane;
+            t.b = at; t.b_step = 1; t.b_stride = stride; at += plane;
+            t.map = NULL; t.map_step = t.map_stride = 0;
+        }
+    }
+}
+
+// Enqueues the forward of n pairs (scale-0 descriptors without maps in host memory, images on the device) on the context's stream:
+// n x scales x 2 means and n values into device memory.
+int msssimf_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const PairFDesc* d, uint32_t W, uint32_t H, float range, uint32_t scales,
+                    const double* w, double* means, double* values)
+{
+    int rc;
+    if ((rc = c->msf_pyramid.grow((size_t)(2 * ssim_hip::msf_pyramid_floats(W, H, scales) * n)))) return rc;
+    if ((rc = c->msf_partials.grow((size_t)ssim_hip::msf_partials(W, H, n, scales)))) return rc;
+    bool wide = false;
+    for (uint32_t i = 0; i < n; ++i) wide = wide || !ssim_hip::fitsf_narrow(d[i]);
+    return ring_launch(c, (size_t)scales * n * sizeof(PairFDesc),
+        [&](uint8_t* pin) {
+            memcpy(pin, d, n * sizeof(PairFDesc));
+            msf_fill_coarse(reinterpret_cast<PairFDesc*>(pin), n, W, H, scales, c->msf_pyramid);
+        },
+        [&](const uint8_t* dev) {
+            return ssim_hip::launch_msssimf(reinterpret_cast<const PairFDesc*>(dev), n, W, H, scales, wide, range, w, c->cu_count, c->xcd_count,
+                                            c->msf_partials, means, values, c->stream);
+        });
+}
+
+// Every sub-batch of the forward into values[0 .. count-1] and means[count x scales x 2] (device).  stage: host pointers -- each
+// sub-batch's images are copied (each image's sample range) into c->stage_a first.
+int msssimf_forward(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float range, uint32_t scales, const double* w,
+                    double* means, double* values, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height;
+    int rc;
+    try {
+        std::vector<PairFDesc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged, off = 0;
+            const uint32_t n = msf_take(params, i0, count, scales, 0, stage, staged);
+            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                d[i] = make_desc<FamilyF>(params[i0 + i], false);
+                if (stage && (rc = stage_images<FamilyF>(c, params[i0 + i], W, H, d[i], off))) return rc;
+            }
+            if ((rc = msssimf_enqueue(c, n, &d[0], W, H, range, scales, w, means + (size_t)i0 * scales * 2, values + i0))) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+// The blocking entry points: every sub-batch into c->msf_out (count values, then count x scales x 2 means), one copy back, one wait.
+int msssimf_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float range, uint32_t scales, const double* w,
+                     float* msssim, double* scaleMeans, bool stage)
+{
+    const size_t total = (1 + 2 * (size_t)scales) * count;
+    int rc;
+    if ((rc = c->msf_out.grow(total))) return rc;
+    if ((rc = c->msf_out_pin.grow(total))) return rc;
+    if ((rc = msssimf_forward(c, count, params, range, scales, w, c->msf_out + count, c->msf_out, stage))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->msf_out_pin, c->msf_out, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < count; ++i) msssim[i] = (float)c->msf_out_pin[i];
+    if (scaleMeans) memcpy(scaleMeans, c->msf_out_pin + count, (size_t)count * scales * 2 * sizeof(double));
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- SSIM of 9- to 16-bit samples ---------------------------------------------------------------------------------------------------------------
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim16(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                          rmgr_uint32_t bitDepth, double* sumsDevice) RMGR_NOEXCEPT
+{
+    const int rc = ssim16_validate(count, params, bitDepth, sumsDevice);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, Family16{bitDepth}, count, params, sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim16_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                 rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = ssim16_validate(count, params, bitDepth, ssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, Family16{bitDepth}, count, params, ssim, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim16_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                               rmgr_uint32_t bitDepth, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = ssim16_validate(count, params, bitDepth, ssim);
+    return rc ? rc : blocking_host(c, Family16{bitDepth}, count, params, ssim);
+}
+
+// ---- SSIM of float32 samples and its gradient (one fused launch without scratch) ------------------------------------------------------------------
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                         float dataRange, double* sumsDevice) RMGR_NOEXCEPT
+{
+    const int rc = ssimf_validate(count, params, dataRange, sumsDevice);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, FamilyF{dataRange}, count, params, sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = ssimf_validate(count, params, dataRange, ssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, FamilyF{dataRange}, count, params, ssim, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                              float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = ssimf_validate(count, params, dataRange, ssim);
+    return rc ? rc : blocking_host(c, FamilyF{dataRange}, count, params, ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                              float dataRange, const float* gradOutDevice,
+                                              const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    int rc = ssimf_validate(count, params, dataRange, gradOutDevice);
+    if (rc) return rc;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = grad_which(gradA, gradB);
+    return enqueue_grads<FamilyF>(c, count, params, gradA, gradB, NULL,
+        [&](uint32_t n, uint32_t i0, const PairFDesc* pd, const GradFDesc* gd, const GradOutFDesc*) {
+            return ssim_hip::launch_ssimf_grad(W, H, n, pd, gd, gradOutDevice + i0, dataRange, which, c->stream);
+        });
+}
+
+// ---- SSIM of float16 / bfloat16 samples and its gradient: the ssimf flow with 2-byte samples ---------------------------------------------------
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                         rmgr_uint32_t sampleType, float dataRange, double* sumsDevice) RMGR_NOEXCEPT
+{
+    const int rc = ssimh_validate(count, params, sampleType, dataRange, sumsDevice);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, FamilyH{ssimh_type(sampleType), dataRange}, count, params, sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, FamilyH{ssimh_type(sampleType), dataRange}, count, params, ssim, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                              rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
+    return rc ? rc : blocking_host(c, FamilyH{ssimh_type(sampleType), dataRange}, count, params, ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                              rmgr_uint32_t sampleType, float dataRange, const float* gradOutDevice,
+                                              const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
+{
+    int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutDevice);
+    if (rc) return rc;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = grad_which(gradA, gradB), type = ssimh_type(sampleType);
+    return enqueue_grads<FamilyH>(c, count, params, gradA, gradB, NULL,
+        [&](uint32_t n, uint32_t i0, const PairHDesc* pd, const GradHDesc* gd, const GradOutFDesc*) {
+            return ssim_hip::launch_ssimh_grad(W, H, n, pd, gd, type, gradOutDevice + i0, dataRange, which, c->stream);
+        });
+}
+
+// ---- gradient of the SSIM map for a per-pixel upstream gradient: the _grad flow with one more descriptor per pair, the gMap plane ----------------
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                  float dataRange, const rmgr_ssim_hip_GradOutF* gradOutMaps,
+                                                  const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    int rc = ssimf_validate(count, params, dataRange, gradOutMaps);
+    if (rc) return rc;
+    if ((rc = validate_grad_maps(count, gradOutMaps))) return rc;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = grad_which(gradA, gradB);
+    return enqueue_grads<FamilyF>(c, count, params, gradA, gradB, gradOutMaps,
+        [&](uint32_t n, uint32_t, const PairFDesc* pd, const GradFDesc* gd, const GradOutFDesc* od) {
+            return ssim_hip::launch_ssimw_grad_f(W, H, n, pd, gd, od, dataRange, which, c->stream);
+        });
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_GradOutF* gradOutMaps,
+                                                  const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
+{
+    int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutMaps);
+    if (rc) return rc;
+    if ((rc = validate_grad_maps(count, gradOutMaps))) return rc;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = grad_which(gradA, gradB), type = ssimh_type(sampleType);
+    return enqueue_grads<FamilyH>(c, count, params, gradA, gradB, gradOutMaps,
+        [&](uint32_t n, uint32_t, const PairHDesc* pd, const GradHDesc* gd, const GradOutFDesc* od) {
+            return ssim_hip::launch_ssimw_grad_h(W, H, n, pd, gd, type, od, dataRange, which, c->stream);
+        });
+}
+
+// ---- multi-scale SSIM of float32 samples and its gradient -------------------------------------------------------------------------------------
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
+                                           rmgr_uint32_t scales, const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
+{
+    const int rc = msssimf_validate(count, params, dataRange, scales, weights, valuesDevice);
+    if (rc) return rc;
+    if (scaleMeansDevice == NULL || !c) return EINVAL;
+    USE_DEVICE(c);
+    return msssimf_forward(c, count, params, dataRange, scales, weights ? weights : kWangWeights, scaleMeansDevice, valuesDevice, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
+                                                  rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    const int rc = msssimf_validate(count, params, dataRange, scales, weights, msssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return msssimf_blocking(c, count, params, dataRange, scales, weights ? weights : kWangWeights, msssim, scaleMeans, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
+                                                rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    int rc = msssimf_validate(count, params, dataRange, scales, weights, msssim);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    USE_DEVICE(lease.c);
+    return msssimf_blocking(lease.c, count, params, dataRange, scales, weights ? weights : kWangWeights, msssim, scaleMeans, true);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
+                                                rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
+                                                const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    int rc = msssimf_validate(count, params, dataRange, scales, weights, gradOutDevice);
+    if (rc) return rc;
+    if (scaleMeansDevice == NULL) return EINVAL;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = grad_which(gradA, gradB), planes = (gradA ? 1 : 0) + (gradB ? 1 : 0);
+    const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
+    const double* w = weights ? weights : kWangWeights;
+    for (uint32_t i0 = 0; i0 < count;) {
+        uint64_t staged;
+        const uint32_t n = msf_take(params, i0, count, scales, planes, false, staged);
+        if ((rc = c->msf_pyramid.grow((size_t)(2 * pyr * n)))) return rc;
+        if ((rc = c->msf_grads.grow((size_t)((uint64_t)planes * pyr * n)))) return rc;
+        if ((rc = c->msf_coef.grow((size_t)n * scales))) return rc;
+        const size_t pair_bytes = (size_t)scales * n * sizeof(PairFDesc);
+        rc = ring_launch(c, pair_bytes + (size_t)scales * n * sizeof(GradFDesc),
+            [&](uint8_t* pin) {
+                PairFDesc* pd = reinterpret_cast<PairFDesc*>(pin);
+                GradFDesc* gd = reinterpret_cast<GradFDesc*>(pin + pair_bytes);
+                for (uint32_t i = 0; i < n; ++i) {
+                    pd[i] = make_desc<FamilyF>(params[i0 + i], false);
+                    gd[i] = make_grad_desc<FamilyF>(gradA, gradB, i0 + i);
+                }
+                msf_fill_coarse(pd, n, W, H, scales, c->msf_pyramid);
+                // gradient planes of scales >= 1: dense scratch, scale by scale, dA then dB of each pair
+                float* at = c->msf_grads;
+                for (uint32_t sc = 1; sc < scales; ++sc) {
+                    const uint64_t plane = ssim_hip::msf_plane(W, H, sc);
+                    const int64_t stride = ssim_hip::msf_dim(W, sc);
+                    for (uint32_t i = 0; i < n; ++i) {
+                        GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
+                        if (gradA) { g.ga = at; g.ga_step = 1; g.ga_stride = stride; at += plane; }
+                        if (gradB) { g.gb = at; g.gb_step = 1; g.gb_stride = stride; at += plane; }
+                        gd[(size_t)sc * n + i] = g;
+                    }
+                }
+            },
+            [&](const uint8_t* dev) {
+                return ssim_hip::launch_msssimf_grad(reinterpret_cast<const PairFDesc*>(dev), reinterpret_cast<const GradFDesc*>(dev + pair_bytes),
+                                                     n, W, H, scales, dataRange, w, scaleMeansDevice + (size_t)i0 * scales * 2, gradOutDevice + i0,
+                                                     c->msf_coef, which, c->stream);
+            });
+        if (rc) return rc;
+        i0 += n;
+    }
+    return 0;
+}
+
+} // extern "C"

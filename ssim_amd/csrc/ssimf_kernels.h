@@ -1,4 +1,4 @@
-// ssimf_kernels.h -- internal interface between the C ABI (ssim_hip_abi.cpp, SSIM of float32 samples and its gradient) and the
+// ssimf_kernels.h -- internal interface between the C ABI (ssim_samples_abi.cpp, SSIM of float32 samples and its gradient) and the
 // kernels (ssimf_kernels.hip).  Not installed.  The definition the kernels implement is written out in include/rmgr/ssim-hip.h
 // (rmgr_ssim_hip_enqueue_ssimf, rmgr_ssim_hip_enqueue_ssimf_grad).
 #ifndef SSIM_AMD_SSIMF_KERNELS_H

@@ -1,4 +1,4 @@
-// ssimh_kernels.h -- internal interface between the C ABI (ssim_hip_abi.cpp, SSIM of float16 / bfloat16 samples and its gradient) and
+// ssimh_kernels.h -- internal interface between the C ABI (ssim_samples_abi.cpp, SSIM of float16 / bfloat16 samples and its gradient) and
 // the kernels (ssimh_kernels.hip).  Not installed.  The definition the kernels implement is written out in include/rmgr/ssim-hip.h
 // (rmgr_ssim_hip_enqueue_ssimh, rmgr_ssim_hip_enqueue_ssimh_grad).
 #ifndef SSIM_AMD_SSIMH_KERNELS_H

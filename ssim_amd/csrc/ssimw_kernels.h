@@ -1,4 +1,4 @@
-// ssimw_kernels.h -- internal interface between the C ABI (ssim_hip_abi.cpp, gradient of the SSIM map for a per-pixel upstream
+// ssimw_kernels.h -- internal interface between the C ABI (ssim_samples_abi.cpp, gradient of the SSIM map for a per-pixel upstream
 // gradient) and the kernels (ssimw_kernels.hip).  Not installed.  The definition the kernels implement is written out in
 // include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssimf_map_grad, rmgr_ssim_hip_enqueue_ssimh_map_grad).
 #ifndef SSIM_AMD_SSIMW_KERNELS_H
