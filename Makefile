@@ -21,8 +21,8 @@ lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr
 
 # The objects both flavours share: kernels, the C ABI's host layer apart from ssim_context (the only one that reads
 # RMGR_SSIM_USE_DOUBLE: $(OBJ)/ssim_context.o / ssim_context_double.o), the drop-in layer.
-ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
-HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/ssimw_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
+HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
 
 # Static flavour under the reference's archive name (CMakeLists.txt:205): the same objects, linked into ONE relocatable
 # object whose only global symbols are the API (the shared libraries' export list has no counterpart for archives: the
@@ -92,6 +92,12 @@ $(OBJ)/ssimh_kernels.o: $(SRC)/ssimh_kernels.hip $(SRC)/ssimh_kernels.h
 # the tests of ssimf_kernels.hip and ssimh_kernels.hip count those files' kernels -- and the same flags: its results are held to those
 # objects', bit for bit.
 $(OBJ)/ssimw_kernels.o: $(SRC)/ssimw_kernels.hip $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# SSIM of float32 samples under a window of 3, 5, 7 or 9 taps, its gradient for both upstream forms, and the taps of every window
+# (rmgr_ssim_hip_*_ssimf_win*): its own file for the same reason, and the same flags as ssimf_kernels.o, whose flow it copies.
+$(OBJ)/ssimk_kernels.o: $(SRC)/ssimk_kernels.hip $(SRC)/ssimk_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -664,6 +664,57 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* ctx, rm
                                                   const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
 
 /*
+ * SSIM of float32 samples under a caller-chosen WINDOW: the five entries of the float32 family -- _enqueue_ssimf, _compute_ssimf_device,
+ * _compute_ssimf_host, _enqueue_ssimf_grad, _enqueue_ssimf_map_grad -- with one more argument, `window`, after dataRange.  What other
+ * libraries call win_size / win_sigma, kernel_size / sigma, filter_size / filter_sigma or window_size, and the 7 x 7 or 3 x 3 box of
+ * skimage and of monodepth-style photometric losses.  No reference counterpart: tests/ssimk_model.py restates it in float64.  Additions
+ * only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ *   Window   size is 3, 5, 7, 9 or 11 taps per axis; R = (size - 1) / 2.
+ *            GAUSSIAN  sigma is finite and > 0.  With s = double(sigma): g_i = exp(-(i i) / (2 s s)) for i = 0 .. R; the norm is accumulated
+ *                      in double in the order i = 0 .. R, g_0 once and the others twice; tap i is float(g_i / norm).
+ *                      {11, GAUSSIAN, 1.5f} yields the engine's taps bit for bit.
+ *            UNIFORM   every tap is float(1.0 / size) (a box); sigma is ignored.
+ *            A NULL window means {11, GAUSSIAN, 1.5f}: the entry without _win, with its bits.
+ *   Everything else is the text of the entry without _win with 5 replaced by R: the window is separable, edges are clamped, the output has
+ *            the input's size; the per-pixel formula, C1 and C2 from dataRange, the fp64 sum over double(W) * double(H); the gradient with
+ *            Gt, the adjoint of the clamped window -- the R results beyond each end fold onto the end pixel: tail[d] = g_d + ... + g_R and
+ *            the total of all taps are summed in double and rounded once, and the rule holds for axes shorter than the window, down to
+ *            1 x 1 --; the centre of every 128-column strip column at the same position with the same |c| <= dataRange test; fp32
+ *            arithmetic, the row pass centre tap first with folded symmetric sums, then the column pass in source-row order; 64-column
+ *            cells, 32 x 32 gradient tiles at absolute positions, one writer per pixel, no floating-point atomics; and every determinism
+ *            promise of ssimf.  For the map gradient: a plane of float(double(gOut[i]) / (double(W) * double(H))) gives the bits of
+ *            _enqueue_ssimf_win_grad for gOut[i] under the same window.
+ *   Reach    a window reads nothing beyond its radius: a NaN sample makes NaN exactly the map pixels within R of it on both axes (edge
+ *            clamping taken into account) and the gradient pixels within 2R; it is not a zero-padded 11-tap window.
+ *   Borders  box windows here CLAMP where monodepth-style code reflects: the interior is identical, the outermost R pixels differ.
+ *   Accuracy measured per window against the float64 model: tests/ssimk_model.py (EMU_*, *_TOL) and DESIGN.md section 16.
+ *
+ * Arguments, EINVAL / ENODEV rules, sub-batches, scratch and stream behaviour are those of the entry without _win.  Additional EINVAL,
+ * checked before any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
+ *
+ * Follow-up, not in this interface: float16 / bfloat16 samples (the ssimh entries) and multi-scale SSIM (the msssim and msssimf entries)
+ * keep the fixed window {11, GAUSSIAN, 1.5f}.
+ */
+enum { RMGR_SSIM_HIP_WINDOW_GAUSSIAN = 0, RMGR_SSIM_HIP_WINDOW_UNIFORM = 1 };
+typedef struct rmgr_ssim_hip_Window {
+    rmgr_uint32_t size, kind;                   /* taps per axis: 3, 5, 7, 9 or 11; RMGR_SSIM_HIP_WINDOW_* */
+    float         sigma;                        /* GAUSSIAN: finite, > 0; UNIFORM: ignored */
+} rmgr_ssim_hip_Window;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                             float dataRange, const rmgr_ssim_hip_Window* window, double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_win_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                    float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_win_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                  float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                  float dataRange, const rmgr_ssim_hip_Window* window, const float* gradOutDevice,
+                                                  const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                      float dataRange, const rmgr_ssim_hip_Window* window, const rmgr_ssim_hip_GradOutF* gradOutMaps,
+                                                      const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
+
+/*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image
  * data crosses GPUs), every rank enqueues its shard into ITS slice of a zero-initialised device vector
  * of per-image fp64 sums, then all ranks call comm_allreduce_sums on the whole vector: one RCCL

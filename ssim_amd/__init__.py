@@ -12,5 +12,6 @@ from .api import (  # noqa: F401
     Img16, Params16, compute_ssim16, compute_ssim16_batch, make_params16,
     ImgF, ParamsF, GradF, compute_ssimf, compute_ssimf_batch, make_params_f,
     compute_msssimf, compute_msssimf_batch,
+    Window, WINDOW_GAUSSIAN, WINDOW_UNIFORM, WINDOW_SIZES, make_window,
     GradH, GradOutF, SAMPLE_F16, SAMPLE_BF16, compute_ssimh, compute_ssimh_batch, sample_type_code,
 )

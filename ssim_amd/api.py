@@ -83,6 +83,46 @@ class GradOutF(ctypes.Structure):
     _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
 
 
+class Window(ctypes.Structure):
+    """rmgr_ssim_hip_Window: the window of the _ssimf_win entries -- size taps per axis (3, 5, 7, 9 or 11), kind WINDOW_GAUSSIAN (sigma
+    finite, > 0) or WINDOW_UNIFORM (a box; sigma ignored)."""
+    _fields_ = [("size", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("sigma", ctypes.c_float)]
+
+
+WINDOW_GAUSSIAN, WINDOW_UNIFORM = 0, 1      # RMGR_SSIM_HIP_WINDOW_GAUSSIAN / _UNIFORM
+WINDOW_SIZES = (3, 5, 7, 9, 11)
+_WINDOW_KINDS = {"gaussian": WINDOW_GAUSSIAN, "uniform": WINDOW_UNIFORM}
+
+
+def make_window(size=11, sigma=1.5, kind="gaussian"):
+    """A Window of `size` taps per axis: kind "gaussian" with `sigma`, or "uniform" (a box; sigma is ignored).  TypeError: a size that is
+    not an int, a kind that is not a str.  ValueError: a size outside 3, 5, 7, 9, 11, an unknown kind, a Gaussian sigma that is not finite
+    or not > 0 as a float32 -- what the library answers with EINVAL."""
+    if isinstance(size, bool) or not isinstance(size, int):
+        raise TypeError("window size must be an int, not %s" % type(size).__name__)
+    if not isinstance(kind, str):
+        raise TypeError("window kind must be a str, not %s" % type(kind).__name__)
+    if size not in WINDOW_SIZES:
+        raise ValueError("window size %d: must be one of 3, 5, 7, 9, 11" % size)
+    if kind not in _WINDOW_KINDS:
+        raise ValueError("window kind %r: must be 'gaussian' or 'uniform'" % (kind,))
+    if kind == "uniform":
+        return Window(size, WINDOW_UNIFORM, 0.0)
+    s = float(np.float32(sigma))
+    if not (s > 0.0 and s != float("inf")):
+        raise ValueError("window sigma %r: must be finite and > 0" % (sigma,))
+    return Window(size, WINDOW_GAUSSIAN, s)
+
+
+def _window_ref(window):
+    """The `window` argument of a _win entry: a Window by reference (None: NULL, the engine's window)."""
+    if window is None:
+        return None
+    if not isinstance(window, Window):
+        raise TypeError("window must be an ssim_amd.Window (make_window) or None")
+    return ctypes.byref(window)
+
+
 SAMPLE_F16, SAMPLE_BF16 = 0, 1      # RMGR_SSIM_HIP_SAMPLE_F16 / _BF16
 _SAMPLE_TYPES = {"float16": SAMPLE_F16, "bfloat16": SAMPLE_BF16}
 
@@ -141,6 +181,8 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_msssimf", "rmgr_ssim_hip_compute_msssimf_device", "rmgr_ssim_hip_compute_msssimf_host", "rmgr_ssim_hip_enqueue_msssimf_grad",
     "rmgr_ssim_hip_enqueue_ssimh", "rmgr_ssim_hip_compute_ssimh_device", "rmgr_ssim_hip_compute_ssimh_host", "rmgr_ssim_hip_enqueue_ssimh_grad",
     "rmgr_ssim_hip_enqueue_ssimf_map_grad", "rmgr_ssim_hip_enqueue_ssimh_map_grad",
+    "rmgr_ssim_hip_enqueue_ssimf_win", "rmgr_ssim_hip_compute_ssimf_win_device", "rmgr_ssim_hip_compute_ssimf_win_host",
+    "rmgr_ssim_hip_enqueue_ssimf_win_grad", "rmgr_ssim_hip_enqueue_ssimf_win_map_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -164,6 +206,7 @@ def load_library(path=None):
     lib = ctypes.CDLL(p)
     vp, i32, u32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32
     PP = ctypes.POINTER(Params)
+    PW = ctypes.POINTER(Window)
     sig = {
         "rmgr_ssim_get_version": [ctypes.POINTER(Version)],
         "rmgr_ssim_init_interleaved": [ctypes.POINTER(ImgParams), vp, c_pd, u32, u32],
@@ -227,6 +270,11 @@ def load_library(path=None):
         "rmgr_ssim_hip_enqueue_ssimh_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
         "rmgr_ssim_hip_enqueue_ssimf_map_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
         "rmgr_ssim_hip_enqueue_ssimh_map_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
+        "rmgr_ssim_hip_enqueue_ssimf_win": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, vp],
+        "rmgr_ssim_hip_compute_ssimf_win_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssimf_win_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssimf_win_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
+        "rmgr_ssim_hip_enqueue_ssimf_win_map_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, ctypes.POINTER(GradOutF), ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
         "rmgr_ssim_hip_enqueue_msssimf": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
         "rmgr_ssim_hip_compute_msssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
@@ -540,9 +588,19 @@ def _params_f_of(a, b, map_ptr=None):
                          map_ptr, 1, w)
 
 
-def compute_ssimf(a, b, data_range, want_map=False, ctx=None):
+def _ssimf_host(handle, count, params, data_range, window, out):
+    """rmgr_ssim_hip_compute_ssimf_host, or -- a window given -- rmgr_ssim_hip_compute_ssimf_win_host."""
+    lib = load_library()
+    if window is None:
+        _check("rmgr_ssim_hip_compute_ssimf_host", lib.rmgr_ssim_hip_compute_ssimf_host(handle, count, params, data_range, out))
+    else:
+        _check("rmgr_ssim_hip_compute_ssimf_win_host", lib.rmgr_ssim_hip_compute_ssimf_win_host(handle, count, params, data_range, _window_ref(window), out))
+
+
+def compute_ssimf(a, b, data_range, want_map=False, ctx=None, window=None):
     """SSIM of two H x W float32 host arrays at `data_range` (any strides numpy can express, negative ones included) through
-    rmgr_ssim_hip_compute_ssimf_host.  Returns (float32 value, H x W float32 map or None)."""
+    rmgr_ssim_hip_compute_ssimf_host; window (a Window, make_window): through rmgr_ssim_hip_compute_ssimf_win_host under that window.
+    Returns (float32 value, H x W float32 map or None)."""
     a, b = _f32_view(a), _f32_view(b)
     assert a.shape == b.shape
     h, w = a.shape
@@ -550,12 +608,11 @@ def compute_ssimf(a, b, data_range, want_map=False, ctx=None):
     params = (ParamsF * 1)()
     params[0] = _params_f_of(a, b, m.ctypes.data if want_map else None)
     out = (ctypes.c_float * 1)()
-    _check("rmgr_ssim_hip_compute_ssimf_host", load_library().rmgr_ssim_hip_compute_ssimf_host(
-        ctx.handle if ctx is not None else None, 1, params, data_range, out))
+    _ssimf_host(ctx.handle if ctx is not None else None, 1, params, data_range, window, out)
     return np.float32(out[0]), m
 
 
-def compute_ssimf_batch(pairs, data_range, ctx=None):
+def compute_ssimf_batch(pairs, data_range, ctx=None, window=None):
     """compute_ssimf() of many host pairs of one size in one call (no maps): a float32 array."""
     pairs = [(_f32_view(a), _f32_view(b)) for a, b in pairs]
     n = len(pairs)
@@ -563,8 +620,7 @@ def compute_ssimf_batch(pairs, data_range, ctx=None):
     for i, (a, b) in enumerate(pairs):
         params[i] = _params_f_of(a, b)
     out = (ctypes.c_float * max(n, 1))()
-    _check("rmgr_ssim_hip_compute_ssimf_host", load_library().rmgr_ssim_hip_compute_ssimf_host(
-        ctx.handle if ctx is not None else None, n, params, data_range, out))
+    _ssimf_host(ctx.handle if ctx is not None else None, n, params, data_range, window, out)
     return np.array(out[:n], np.float32)
 
 
@@ -806,20 +862,37 @@ class Context(object):
         """rmgr_ssim_hip_enqueue_ssim16: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
         _check("rmgr_ssim_hip_enqueue_ssim16", self.lib.rmgr_ssim_hip_enqueue_ssim16(self.handle, count, params_array, bit_depth, sums_dev_ptr))
 
-    def ssimf_device(self, params_array, count, data_range):
-        """SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_ssimf_device: a float32 array."""
+    # The float32 family takes window=None (the engine's 11-tap Gaussian of sigma 1.5: the entry without _win) or a Window
+    # (make_window): the _win entry under that window.
+
+    def ssimf_device(self, params_array, count, data_range, window=None):
+        """SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_ssimf_device (window: _win_device):
+        a float32 array."""
         out = (ctypes.c_float * max(count, 1))()
-        _check("rmgr_ssim_hip_compute_ssimf_device", self.lib.rmgr_ssim_hip_compute_ssimf_device(self.handle, count, params_array, data_range, out))
+        if window is None:
+            _check("rmgr_ssim_hip_compute_ssimf_device", self.lib.rmgr_ssim_hip_compute_ssimf_device(self.handle, count, params_array, data_range, out))
+        else:
+            _check("rmgr_ssim_hip_compute_ssimf_win_device", self.lib.rmgr_ssim_hip_compute_ssimf_win_device(
+                self.handle, count, params_array, data_range, _window_ref(window), out))
         return np.array(out[:count], np.float32)
 
-    def enqueue_ssimf(self, params_array, count, data_range, sums_dev_ptr):
-        """rmgr_ssim_hip_enqueue_ssimf: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
-        _check("rmgr_ssim_hip_enqueue_ssimf", self.lib.rmgr_ssim_hip_enqueue_ssimf(self.handle, count, params_array, data_range, sums_dev_ptr))
+    def enqueue_ssimf(self, params_array, count, data_range, sums_dev_ptr, window=None):
+        """rmgr_ssim_hip_enqueue_ssimf (window: _ssimf_win): per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssimf", self.lib.rmgr_ssim_hip_enqueue_ssimf(self.handle, count, params_array, data_range, sums_dev_ptr))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssimf_win", self.lib.rmgr_ssim_hip_enqueue_ssimf_win(
+                self.handle, count, params_array, data_range, _window_ref(window), sums_dev_ptr))
 
-    def enqueue_ssimf_grad(self, params_array, count, data_range, grad_out_dev_ptr, grad_a=None, grad_b=None):
-        """rmgr_ssim_hip_enqueue_ssimf_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs into the planes the GradF arrays
-        grad_a / grad_b describe (None: not wanted), from `count` floats dLoss/dS_i in device memory; asynchronous, written not accumulated."""
-        _check("rmgr_ssim_hip_enqueue_ssimf_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_grad(self.handle, count, params_array, data_range, grad_out_dev_ptr, grad_a, grad_b))
+    def enqueue_ssimf_grad(self, params_array, count, data_range, grad_out_dev_ptr, grad_a=None, grad_b=None, window=None):
+        """rmgr_ssim_hip_enqueue_ssimf_grad (window: _ssimf_win_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs into the
+        planes the GradF arrays grad_a / grad_b describe (None: not wanted), from `count` floats dLoss/dS_i in device memory; asynchronous,
+        written not accumulated."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssimf_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_grad(self.handle, count, params_array, data_range, grad_out_dev_ptr, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssimf_win_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_win_grad(
+                self.handle, count, params_array, data_range, _window_ref(window), grad_out_dev_ptr, grad_a, grad_b))
 
     def ssimh_device(self, params_array, count, data_range, sample_type):
         """SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_ssimh_device: a
@@ -840,12 +913,16 @@ class Context(object):
         _check("rmgr_ssim_hip_enqueue_ssimh_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_grad(
             self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_dev_ptr, grad_a, grad_b))
 
-    def enqueue_ssimf_map_grad(self, params_array, count, data_range, grad_out_maps, grad_a=None, grad_b=None):
-        """rmgr_ssim_hip_enqueue_ssimf_map_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs for a per-pixel upstream
+    def enqueue_ssimf_map_grad(self, params_array, count, data_range, grad_out_maps, grad_a=None, grad_b=None, window=None):
+        """rmgr_ssim_hip_enqueue_ssimf_map_grad (window: _ssimf_win_map_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs for a per-pixel upstream
         gradient: grad_out_maps is a GradOutF array of `count` float32 planes dLoss/dssim_i(p) in device memory (any step / stride, 0
         included); asynchronous, written not accumulated."""
-        _check("rmgr_ssim_hip_enqueue_ssimf_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_map_grad(
-            self.handle, count, params_array, data_range, grad_out_maps, grad_a, grad_b))
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssimf_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_map_grad(
+                self.handle, count, params_array, data_range, grad_out_maps, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssimf_win_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_win_map_grad(
+                self.handle, count, params_array, data_range, _window_ref(window), grad_out_maps, grad_a, grad_b))
 
     def enqueue_ssimh_map_grad(self, params_array, count, data_range, sample_type, grad_out_maps, grad_a=None, grad_b=None):
         """rmgr_ssim_hip_enqueue_ssimh_map_grad: the same for float16 / bfloat16 pairs (a Params16 array); the GradH planes receive the

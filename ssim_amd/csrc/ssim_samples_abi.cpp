@@ -1,7 +1,7 @@
 // ssim_samples_abi.cpp -- the entry points of the C ABI for samples other than 8-bit ones (the 8-bit path: ssim_hip_abi.cpp): SSIM of
 // 9- to 16-bit integers (ssim16), of float32 (ssimf) and of float16 / bfloat16 samples (ssimh), the gradients of the latter two for a
 // scalar and for a per-pixel upstream gradient (ssimw), and multi-scale SSIM of float32 samples with its gradient (msssimf).  The
-// definitions are in include/rmgr/ssim-hip.h, the kernels in ssim16_ / ssimf_ / ssimh_ / ssimw_ / msssimf_kernels.hip.
+// definitions are in include/rmgr/ssim-hip.h, the kernels in ssim16_ / ssimf_ / ssimh_ / ssimw_ / ssimk_ / msssimf_kernels.hip.
 //
 // The three single-scale families differ in their sample type and in what a launch is told (bit depth; data range; encoding and data
 // range); each is described once by a small struct (Family16 / FamilyF / FamilyH) and the host flow -- validation, sub-batches, staging
@@ -17,6 +17,7 @@
 #include "ssim_context.h"
 #include "ssimh_kernels.h"
 #include "ssimw_kernels.h"
+#include "ssimk_kernels.h"
 
 #include <cmath>
 
@@ -51,6 +52,22 @@ struct Family16 {
     { return ssim_hip::launch_ssim16(geo, dev, map, unit, wide, depth, c->xcd_count, c->sf_partials, sums, c->stream); }
 };
 
+// The window of a float32 launch: its radius and taps, centre first (ssimk_kernels.h: window_taps).  Radius 5 runs on the kernels of
+// ssimf_kernels.hip / ssimw_kernels.hip, the smaller ones on ssimk_kernels.hip.
+struct WindowF {
+    uint32_t radius;
+    float    gf[ssim_hip::kSKMaxRadius + 1];
+};
+
+// The engine's window, that of every entry without _win: 11 taps, Gaussian, sigma 1.5.
+WindowF default_window()
+{
+    WindowF w;
+    w.radius = 5;
+    ssim_hip::window_taps(5, ssim_hip::kSKGaussian, 1.5f, w.gf);
+    return w;
+}
+
 struct FamilyF {
     typedef rmgr_ssim_hip_ParamsF Params;
     typedef rmgr_ssim_hip_GradF Grad;
@@ -63,8 +80,16 @@ struct FamilyF {
     static Geometry plan(uint32_t W, uint32_t H, uint32_t n, int cus) { return ssim_hip::planf(W, H, n, cus); }
     static bool fits_narrow(const Desc& d) { return ssim_hip::fitsf_narrow(d); }
     float range;
+    WindowF win;
+    // geo is planf()'s: the cells (and with them the partials) are the same for every radius; a smaller window re-plans its strips, which
+    // pay fewer warm-up rows
     hipError_t launch(rmgr_ssim_hip_Context* c, const Geometry& geo, const Desc* dev, bool map, bool unit, bool wide, double* sums) const
-    { return ssim_hip::launch_ssimf(geo, dev, map, unit, wide, range, c->xcd_count, c->sf_partials, sums, c->stream); }
+    {
+        if (win.radius == 5)
+            return ssim_hip::launch_ssimf(geo, dev, map, unit, wide, range, win.gf, c->xcd_count, c->sf_partials, sums, c->stream);
+        return ssim_hip::launch_ssimk(win.radius, win.gf, ssim_hip::plank(win.radius, geo.width, geo.height, geo.count, c->cu_count), dev, map, wide,
+                                      range, c->xcd_count, c->sf_partials, sums, c->stream);
+    }
 };
 
 struct FamilyH {
@@ -116,6 +141,18 @@ int ssimf_validate(uint32_t count, const rmgr_ssim_hip_ParamsF* params, float da
 {
     if (!valid_range(dataRange)) return EINVAL;
     return validate_pairs<FamilyF>(count, params, out);
+}
+
+// The window of a _win entry: NULL is the engine's; else size 3, 5, 7, 9 or 11, a known kind and -- Gaussian -- a finite sigma > 0.
+int window_validate(const rmgr_ssim_hip_Window* window, WindowF& w)
+{
+    if (window == NULL) { w = default_window(); return 0; }
+    const uint32_t size = window->size;
+    if (size < 3 || size > 11 || (size & 1u) == 0) return EINVAL;
+    if (window->kind != RMGR_SSIM_HIP_WINDOW_GAUSSIAN && window->kind != RMGR_SSIM_HIP_WINDOW_UNIFORM) return EINVAL;
+    w.radius = (size - 1) / 2;
+    return ssim_hip::window_taps(w.radius, window->kind == RMGR_SSIM_HIP_WINDOW_UNIFORM ? ssim_hip::kSKUniform : ssim_hip::kSKGaussian, window->sigma, w.gf)
+               ? 0 : EINVAL;
 }
 
 int ssimh_validate(uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t sampleType, float dataRange, const void* out)
@@ -541,6 +578,41 @@ int msssimf_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_h
     return 0;
 }
 
+// ---- SSIM of float32 samples: what an entry does once its arguments are valid; `win` is the engine's window or the caller's ------------------
+
+int ssimf_enqueue_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const WindowF& win,
+                        double* sumsDevice)
+{
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, FamilyF{dataRange, win}, count, params, sumsDevice);
+}
+
+int ssimf_device_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const WindowF& win, float* ssim)
+{
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, FamilyF{dataRange, win}, count, params, ssim, false);
+}
+
+// gradOutDevice: the scalar upstream form; gradOutMaps: the per-pixel form.  Exactly one is given.
+int ssimf_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const WindowF& win,
+                     const float* gradOutDevice, const rmgr_ssim_hip_GradOutF* gradOutMaps, const rmgr_ssim_hip_GradF* gradA,
+                     const rmgr_ssim_hip_GradF* gradB)
+{
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = grad_which(gradA, gradB);
+    return enqueue_grads<FamilyF>(c, count, params, gradA, gradB, gradOutMaps,
+        [&](uint32_t n, uint32_t i0, const PairFDesc* pd, const GradFDesc* gd, const GradOutFDesc* od) {
+            const float* g_out = gradOutMaps ? NULL : gradOutDevice + i0;
+            if (win.radius != 5) return ssim_hip::launch_ssimk_grad(win.radius, win.gf, W, H, n, pd, gd, g_out, gradOutMaps ? od : NULL, dataRange, which, c->stream);
+            if (gradOutMaps)     return ssim_hip::launch_ssimw_grad_f(W, H, n, pd, gd, od, dataRange, win.gf, which, c->stream);
+            return ssim_hip::launch_ssimf_grad(W, H, n, pd, gd, g_out, dataRange, win.gf, which, c->stream);
+        });
+}
+
 } // namespace
 
 extern "C" {
@@ -575,32 +647,55 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssim16_host(rmgr_ssim_hip_Context* c, rmgr_ui
 }
 
 // ---- SSIM of float32 samples and its gradient (one fused launch without scratch) ------------------------------------------------------------------
+// Every entry exists twice: under the engine's window and, _win, under the caller's (include/rmgr/ssim-hip.h: rmgr_ssim_hip_Window).
+// Both run the same flow; the window is one more input of the family.
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                          float dataRange, double* sumsDevice) RMGR_NOEXCEPT
 {
     const int rc = ssimf_validate(count, params, dataRange, sumsDevice);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return enqueue_all(c, FamilyF{dataRange}, count, params, sumsDevice);
+    return rc ? rc : ssimf_enqueue_entry(c, count, params, dataRange, default_window(), sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                             float dataRange, const rmgr_ssim_hip_Window* window, double* sumsDevice) RMGR_NOEXCEPT
+{
+    WindowF win;
+    int rc = ssimf_validate(count, params, dataRange, sumsDevice);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    return ssimf_enqueue_entry(c, count, params, dataRange, win, sumsDevice);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                                 float dataRange, float* ssim) RMGR_NOEXCEPT
 {
     const int rc = ssimf_validate(count, params, dataRange, ssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return blocking(c, FamilyF{dataRange}, count, params, ssim, false);
+    return rc ? rc : ssimf_device_entry(c, count, params, dataRange, default_window(), ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                    float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT
+{
+    WindowF win;
+    int rc = ssimf_validate(count, params, dataRange, ssim);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    return ssimf_device_entry(c, count, params, dataRange, win, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                               float dataRange, float* ssim) RMGR_NOEXCEPT
 {
     const int rc = ssimf_validate(count, params, dataRange, ssim);
-    return rc ? rc : blocking_host(c, FamilyF{dataRange}, count, params, ssim);
+    return rc ? rc : blocking_host(c, FamilyF{dataRange, default_window()}, count, params, ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimf_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                  float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT
+{
+    WindowF win;
+    int rc = ssimf_validate(count, params, dataRange, ssim);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    return blocking_host(c, FamilyF{dataRange, win}, count, params, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
@@ -610,14 +705,18 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uin
     int rc = ssimf_validate(count, params, dataRange, gradOutDevice);
     if (rc) return rc;
     if ((rc = validate_grads(count, gradA, gradB))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = grad_which(gradA, gradB);
-    return enqueue_grads<FamilyF>(c, count, params, gradA, gradB, NULL,
-        [&](uint32_t n, uint32_t i0, const PairFDesc* pd, const GradFDesc* gd, const GradOutFDesc*) {
-            return ssim_hip::launch_ssimf_grad(W, H, n, pd, gd, gradOutDevice + i0, dataRange, which, c->stream);
-        });
+    return ssimf_grad_entry(c, count, params, dataRange, default_window(), gradOutDevice, NULL, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                  float dataRange, const rmgr_ssim_hip_Window* window, const float* gradOutDevice,
+                                                  const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    WindowF win;
+    int rc = ssimf_validate(count, params, dataRange, gradOutDevice);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    return ssimf_grad_entry(c, count, params, dataRange, win, gradOutDevice, NULL, gradA, gradB);
 }
 
 // ---- SSIM of float16 / bfloat16 samples and its gradient: the ssimf flow with 2-byte samples ---------------------------------------------------
@@ -676,14 +775,19 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_map_grad(rmgr_ssim_hip_Context* c, rmgr
     if (rc) return rc;
     if ((rc = validate_grad_maps(count, gradOutMaps))) return rc;
     if ((rc = validate_grads(count, gradA, gradB))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = grad_which(gradA, gradB);
-    return enqueue_grads<FamilyF>(c, count, params, gradA, gradB, gradOutMaps,
-        [&](uint32_t n, uint32_t, const PairFDesc* pd, const GradFDesc* gd, const GradOutFDesc* od) {
-            return ssim_hip::launch_ssimw_grad_f(W, H, n, pd, gd, od, dataRange, which, c->stream);
-        });
+    return ssimf_grad_entry(c, count, params, dataRange, default_window(), NULL, gradOutMaps, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                      float dataRange, const rmgr_ssim_hip_Window* window, const rmgr_ssim_hip_GradOutF* gradOutMaps,
+                                                      const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    WindowF win;
+    int rc = ssimf_validate(count, params, dataRange, gradOutMaps);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    if ((rc = validate_grad_maps(count, gradOutMaps))) return rc;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    return ssimf_grad_entry(c, count, params, dataRange, win, NULL, gradOutMaps, gradA, gradB);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,

@@ -62,19 +62,21 @@ GeometryF planf(uint32_t width, uint32_t height, uint32_t count, int cu_count);
 //   map_unit    every map has ssimStep == 1 and the width is even (8-byte map stores)
 //   wide        some pair fails fitsf_narrow()
 //   data_range  R > 0, finite: sets C1 and C2, and bounds the centre (see ssimf_kernels.hip)
+//   taps        the window's six taps, centre first (ssimk_kernels.h: window_taps with radius 5; the default is the Gaussian of sigma 1.5)
 //   partials    geo.count * geo.cells_per_image() doubles of device scratch
 //   sums        geo.count doubles (device): each image's fp64 sum of its per-pixel values, in a fixed order
 hipError_t launch_ssimf(const GeometryF& geo, const PairFDesc* descs_dev, bool map, bool map_unit, bool wide, float data_range,
-                        int xcd_count, double* partials, double* sums, hipStream_t stream);
+                        const float (&taps)[6], int xcd_count, double* partials, double* sums, hipStream_t stream);
 
 // Enqueues the gradient kernel of `count` pairs of width x height on `stream`: one fused launch that recomputes the statistics.
 //   descs_dev   count PairFDesc in device memory (map ignored)
 //   grads_dev   count GradFDesc in device memory
 //   g_out       count floats in device memory: dLoss/dS_i
+//   taps        the window's six taps, centre first, as launch_ssimf
 //   which       1: dLoss/dA into ga; 2: dLoss/dB into gb; 3: both, in one pass, each with the bits it has alone
 // Gradient planes are written, not accumulated; every pixel by exactly one work-item.
 hipError_t launch_ssimf_grad(uint32_t width, uint32_t height, uint32_t count, const PairFDesc* descs_dev, const GradFDesc* grads_dev,
-                             const float* g_out, float data_range, int which, hipStream_t stream);
+                             const float* g_out, float data_range, const float (&taps)[6], int which, hipStream_t stream);
 
 // C1 and C2 of a data range, as the kernels use them: float((0.01 R)^2), float((0.03 R)^2) with the products in double.
 void ssimf_constants(float data_range, float& c1, float& c2);

@@ -1,35 +1,21 @@
-// ssimf_kernels.hip -- gfx950 kernels of SSIM on float32 samples and of its gradient, behind rmgr_ssim_hip_enqueue_ssimf,
-// rmgr_ssim_hip_compute_ssimf_device / _host and rmgr_ssim_hip_enqueue_ssimf_grad.  The definition they implement is in
-// include/rmgr/ssim-hip.h; tests/ssimf_model.py restates it in float64 and restates the arithmetic below in fp32.
+// ssimk_kernels.hip -- gfx950 kernels of SSIM on float32 samples, and of its gradient, under a window of 3, 5, 7 or 9 taps (radius
+// R = 1 .. 4), behind rmgr_ssim_hip_enqueue_ssimf_win, rmgr_ssim_hip_compute_ssimf_win_device / _host, rmgr_ssim_hip_enqueue_ssimf_win_grad
+// and rmgr_ssim_hip_enqueue_ssimf_win_map_grad.  The definition they implement is in include/rmgr/ssim-hip.h (rmgr_ssim_hip_Window);
+// tests/ssimk_model.py restates it in float64 and restates the arithmetic below in fp32.  Windows of 11 taps run on ssimf_kernels.hip and
+// ssimw_kernels.hip with the window's taps; this file also holds the taps rule of every window (window_taps).
 //
-// Kept apart from ssim_kernels.hip on purpose: that file's sha256 is the kernel source id measurements are tied to
-// (Makefile, profiles/traffic.json).  The forward kernel is the strip choreography of ssim16_kernels.hip with float loads, copied
-// here, not included.
-//
-//  * ssimf_strip_kernel: one 64-lane wavefront = one workgroup = one vertical strip of 128 output columns (two per lane) x
-//    strip_rows rows.  Per source row the wave loads the row's float samples of A and B (edge-clamped, any step / stride) one
-//    row ahead into registers, centres them (below), writes the (a', b') and (a'^2 + b'^2, a'b') planes of the row into a 2-slot
-//    LDS ring, reads each lane's 12-pixel window back with 16-byte reads, runs the horizontal pass on the folded sums and
-//    scatters the result into 11-deep register rings (the vertical pass); the ring's oldest entry is a finished output row:
-//    SSIM formula, fp64 column sums, optional map store.  Intermediates never touch HBM: 8 B of samples per pixel (+4 B with a
-//    map).  Plain fp32 VALU, no MFMA.
-//  * ssimf_reduce_kernel: each image's cell partials summed in a fixed order.
-//  * ssimf_grad_kernel: the gradient, one fused launch that recomputes the statistics (DESIGN.md section 12 has the reasons).
-//    Its own comment is above it.
-//
-// Centring.  Both kernels blur a' = a - cA, b' = b - cB.  The centre of the 128 columns from x0 = 128 k on is A's and B's sample
-// at (min(x0 + 64, W - 1), (H - 1) / 2), as in ssim16_kernels.hip, when its magnitude is at most dataRange, else 0 (so a NaN, an
-// Inf or a far outlier at that one position cannot spoil a whole strip column: it then behaves like any other sample).  The
-// position is fixed by the image, so every strip height, tile, batch, split and entry point sees the same centre.  Unlike
-// integer samples the subtraction rounds: a' is a - c to half an ulp of a', an input perturbation below the samples' own
-// resolution wherever |a - c| <= |a|, and it leaves numbers near 0 in smooth areas, where the cancellation in E[a'^2] - mu_a'^2
-// would otherwise cost the most.  The emulation in tests/ssimf_model.py makes the same subtraction.
-//
-// Per-pixel values and cells.  Every output pixel receives the 11 row-pass values of its source rows in source-row order, first
-// one multiplied into zero, whatever row the strip starts at; a cell (64 columns x cell_rows rows at an absolute position) is
-// the per-column sum in row order, the column pairs, then a fixed tree.  The sums are therefore bit-identical for any strip
-// height, batch or split.
-#include "ssimf_kernels.h"
+// This is the flow of ssimf_kernels.hip, copied -- not included: that file's kernels are counted by its tests -- and templated on the
+// radius, and built with the same flags (-ffp-contract=off).  What the radius changes:
+//  * ssimk_strip_kernel<R, MAP, WIDE>: register rings of 2R + 1 entries, 2R warm-up rows from source row y0 - R on, the finished row is
+//    r - R; a lane reads its 2R + 2 window pixels (columns x - R .. x + R + 1 of its first column x) as R + 1 aligned 16-byte LDS reads from
+//    a slot that starts R columns left of the strip (PAD = R keeps 2 lane + PAD - R even).  A window never reads beyond its radius: a NaN
+//    sample reaches the (2R + 1)^2 map pixels around it and no others.
+//  * ssimk_grad_kernel<R, WHICH>: the tile + 2R of samples, the tile + R of statistics, adjoint weights over |j| <= R.  One kernel serves
+//    both upstream forms: k = float(double(gOut) / (double(W) double(H))) for the whole launch, or k(p) = gMap(p) read per pixel -- a
+//    branch on a kernel argument; the product k d is the same instruction in both, so a constant plane gives the scalar form's bits.
+//  * ssimk_reduce_kernel: a copy of ssimf_reduce_kernel.
+// Centring, cells, tiles and summation orders: see the top of ssimf_kernels.hip; they are position-based and do not depend on the radius.
+#include "ssimk_kernels.h"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -58,43 +44,42 @@ __device__ __forceinline__ int64_t uniform64(int64_t v)
 }
 
 // Row pass of the lane's two columns, centre tap first, the two dependent chains interleaved.
-__device__ __forceinline__ void rows_pair(f2& hA, f2& hB, const f2 (&a)[6], const f2 (&b)[6], const float (&g)[6])
+template <int R>
+__device__ __forceinline__ void rows_pair(f2& hA, f2& hB, const f2 (&a)[R + 1], const f2 (&b)[R + 1], const float (&g)[R + 1])
 {
     hA = a[0] * f2{g[0], g[0]};
     hB = b[0] * f2{g[0], g[0]};
 #pragma unroll
-    for (int k = 1; k < 6; ++k) {
+    for (int k = 1; k <= R; ++k) {
         hA = fma_(a[k], f2{g[k], g[k]}, hA);
         hB = fma_(b[k], f2{g[k], g[k]}, hB);
     }
 }
-// Column pass: the ring scatter.  acc[k] is the running sum of output row (r - 5 + k) while source row r is processed.
+// Column pass: the ring scatter.  acc[k] is the running sum of output row (r - R + k) while source row r is processed.
 // KMIN (warm-up rows only): ring entries below KMIN stand for rows above the strip and are never read.
-template <int KMIN = 0>
-__device__ __forceinline__ void columns_pair(f2 (&accA)[11], f2 (&accB)[11], f2 hA, f2 hB, const float (&g)[6])
+template <int R, int KMIN>
+__device__ __forceinline__ void columns_pair(f2 (&accA)[2 * R + 1], f2 (&accB)[2 * R + 1], f2 hA, f2 hB, const float (&g)[R + 1])
 {
 #pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        const int t = k < 5 ? 5 - k : k - 5;
+    for (int k = 0; k < 2 * R; ++k) {
+        const int t = k < R ? R - k : k - R;
         if (k >= KMIN) {
             accA[k] = fma_(hA, f2{g[t], g[t]}, accA[k + 1]);
             accB[k] = fma_(hB, f2{g[t], g[t]}, accB[k + 1]);
         }
     }
-    accA[10] = hA * f2{g[5], g[5]};
-    accB[10] = hB * f2{g[5], g[5]};
+    accA[2 * R] = hA * f2{g[R], g[R]};
+    accB[2 * R] = hB * f2{g[R], g[R]};
 }
-template <int KMIN = 0>
-__device__ __forceinline__ void blur_pair(f2 (&accA)[11], f2 (&accB)[11], const f2 (&a)[6], const f2 (&b)[6], const float (&g)[6])
+template <int R, int KMIN>
+__device__ __forceinline__ void blur_pair(f2 (&accA)[2 * R + 1], f2 (&accB)[2 * R + 1], const f2 (&a)[R + 1], const f2 (&b)[R + 1], const float (&g)[R + 1])
 {
     f2 hA, hB;
-    rows_pair(hA, hB, a, b, g);
-    columns_pair<KMIN>(accA, accB, hA, hB, g);
+    rows_pair<R>(hA, hB, a, b, g);
+    columns_pair<R, KMIN>(accA, accB, hA, hB, g);
 }
 
-// SSIM of the lane's two columns from the centred moments: m0, m1 = (mu_a', mu_b') of each column, e0, e1 = (E[a'^2 + b'^2],
-// E[a'b']); cen = (cA, cB).  sigma_a^2 + sigma_b^2 = E[a'^2 + b'^2] - (mu_a'^2 + mu_b'^2), sigma_ab = E[a'b'] - mu_a' mu_b',
-// mu = mu' + centre.  The quotient is n * rcp(d) (1 ulp, as MODE_SEPARABLE).
+// SSIM of the lane's two columns from the centred moments (ssim_px2 of ssimf_kernels.hip).
 __device__ __forceinline__ f2 ssim_px2(f2 m0, f2 m1, f2 e0, f2 e1, f2 cen, float c1, float c2)
 {
     const f2 q0 = m0 * m0, q1 = m1 * m1;
@@ -113,14 +98,16 @@ __device__ __forceinline__ f2 ssim_px2(f2 m0, f2 m1, f2 e0, f2 e1, f2 cen, float
     return n * r;
 }
 
-struct KFArgs {
+enum { MAXR = 4 };
+
+struct KKArgs {
     const PairFDesc* descs;
     uint32_t width, height, strip_rows, strips_x, strips_y;
     uint32_t cells_x, cells_y, cell_shift;
     uint32_t count, xcds;
     double*  partials;            // [image][cell_y][cell_x]
     float    c1, c2, range;
-    float    gf[6];
+    float    gf[MAXR + 1];
 };
 
 __device__ __forceinline__ void wave_sync()
@@ -129,8 +116,7 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
-// Workgroup g of `total` -> its place in the strip list when each XCD is to walk one contiguous share of it (neighbouring strips
-// share halo cache lines; consecutive workgroup ids go to the XCDs round robin).  A bijection for any total.
+// Workgroup g of `total` -> its place in the strip list when each XCD walks one contiguous share of it (ssimf_kernels.hip).
 __device__ __forceinline__ uint32_t xcd_order(uint32_t g, uint32_t total, uint32_t xcds)
 {
     uint32_t xcd, slot, q, rem;
@@ -139,13 +125,11 @@ __device__ __forceinline__ uint32_t xcd_order(uint32_t g, uint32_t total, uint32
     return xcd * q + (xcd < rem ? xcd : rem) + slot;
 }
 
-// Cells are reduced eight at a time (ssim_kernels.hip has the long form): each lane parks its leaf of a cell in LDS, and a
-// batch of eight cells is summed as fixed trees -- eight leaves per lane as ((x0+x1)+(x2+x3))+((x4+x5)+(x6+x7)), then two DPP
-// levels over the four lanes of a 32-leaf tree.
+// Cells are reduced eight at a time, as fixed trees (ssimf_kernels.hip; ssim_kernels.hip has the long form).
 enum { CELL_BATCH = 8 };
 struct CellBatch { double leaf[CELL_BATCH][64]; };
 
-#define SF_DPP_ADD(t, CTRL) do {                                                                             \
+#define SK_DPP_ADD(t, CTRL) do {                                                                             \
         const int lo_ = __builtin_amdgcn_update_dpp(0, __double2loint(t), (CTRL), 0xF, 0xF, false);           \
         const int hi_ = __builtin_amdgcn_update_dpp(0, __double2hiint(t), (CTRL), 0xF, 0xF, false);           \
         (t) += __hiloint2double(hi_, lo_);                                                                    \
@@ -170,44 +154,51 @@ __device__ __forceinline__ double cell_batch_local(const CellBatch& cb, int lane
 }
 
 // A leaf is the lane's column pair; leaves 0-31 of a batch row are cell 2 sx, leaves 32-63 cell 2 sx + 1.
-__device__ __forceinline__ void cell_batch_flush(const KFArgs& args, uint32_t img, uint32_t sx, const CellBatch& cb, uint32_t cell_y_first, uint32_t n)
+__device__ __forceinline__ void cell_batch_flush(const KKArgs& args, uint32_t img, uint32_t sx, const CellBatch& cb, uint32_t cell_y_first, uint32_t n)
 {
     int lane = threadIdx.x;
     asm volatile("" : "+v"(lane));
     double t = cell_batch_local(cb, lane);
-    SF_DPP_ADD(t, DPP_QUAD_XOR1);
-    SF_DPP_ADD(t, DPP_QUAD_XOR2);
+    SK_DPP_ADD(t, DPP_QUAD_XOR1);
+    SK_DPP_ADD(t, DPP_QUAD_XOR2);
     const uint32_t c = (uint32_t)lane >> 3, cx = 2u * sx + (((uint32_t)lane >> 2) & 1u);
     if ((lane & 3) == 0 && c < n && cx < args.cells_x)
         ((gptr_f64)args.partials)[((size_t)img * args.cells_y + cell_y_first + c) * args.cells_x + cx] = t;
 }
 
-// LDS slot = one source row of 144 pixels starting seven columns left of the strip: a lane's twelve window pixels (columns x-5 ..
-// x+6 of its first column x) start on an even slot pixel and are six aligned 16-byte reads per plane.
+// LDS slot = one source row of 128 + 2R pixels starting R columns left of the strip: a lane's 2R + 2 window pixels (columns x - R ..
+// x + R + 1 of its first column x) start on the even slot pixel 2 lane and are R + 1 aligned 16-byte reads per plane; the last lane's
+// window ends on the slot's last pixel.
+template <int R>
 struct Slot {
-    static constexpr int STRIP_W = kSFStripW, PAD = 7, ROW_PX = 144;
+    static constexpr int STRIP_W = kSFStripW, PAD = R, ROW_PX = STRIP_W + 2 * R;
     f2 ab[ROW_PX];   // (a', b')
     f2 q[ROW_PX];    // (a'^2 + b'^2, a'b')
 };
 
 enum { ROW_WARMUP = 0, ROW_MAIN = 1, ROW_LAST = 2 };
 
-// MAP: 0 no map; 1 any ssimStep (one 4-byte store per column); 2 ssimStep == 1 and an even width (one 8-byte store per lane).
-// WIDE: 64-bit lane offsets for the samples and the map (pairs that fail fitsf_narrow()); the map then goes out as plain
-// guarded stores.
-template <int MAP, bool WIDE>
+// R: the window's radius.  MAP: 0 no map; 1 a map of any ssimStep (one 4-byte store per column).
+// WIDE: 64-bit lane offsets for the samples and the map (pairs that fail fitsf_narrow()); the map then goes out as plain guarded stores.
+template <int R, int MAP, bool WIDE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
-void ssimf_strip_kernel(const KFArgs args)
+void ssimk_strip_kernel(const KKArgs args)
 {
-    constexpr int PAD = Slot::PAD, ROW_PX = Slot::ROW_PX;
-    constexpr int NLOAD = 3;                         // samples each lane stages per row and image
+    static_assert(R >= 1 && R <= MAXR, "radius");
+    constexpr int PAD = Slot<R>::PAD, ROW_PX = Slot<R>::ROW_PX;
+    constexpr int N = 2 * R + 1;                     // ring entries
+    constexpr int NWIN = 2 * R + 2;                  // window pixels of a lane's two columns
+    constexpr int NLOAD = 3;                         // samples each lane stages per row and image (192 >= ROW_PX)
+    static_assert((PAD - R) % 2 == 0 && 126 + PAD - R + NWIN <= ROW_PX && ROW_PX <= 64 * NLOAD, "slot");
     typedef typename std::conditional<WIDE, int64_t, uint32_t>::type Off;
 
-    __shared__ __attribute__((aligned(16))) Slot ring[2];
+    __shared__ __attribute__((aligned(16))) Slot<R> ring[2];
     __shared__ __attribute__((aligned(16))) CellBatch cells;
 
     const int lane = threadIdx.x;
-    const float gf[6] = {args.gf[0], args.gf[1], args.gf[2], args.gf[3], args.gf[4], args.gf[5]};
+    float gf[R + 1];
+#pragma unroll
+    for (int i = 0; i <= R; ++i) gf[i] = args.gf[i];
 
     // the strip: image-major, then strip row, then strip column, each XCD walking a contiguous share of that list
     const uint32_t per_img = args.strips_x * args.strips_y;
@@ -222,10 +213,10 @@ void ssimf_strip_kernel(const KFArgs args)
         pd.map = (float*)uniform64((int64_t)gd->map); pd.map_step = uniform64(gd->map_step); pd.map_stride = uniform64(gd->map_stride);
     }
     const int W = (int)args.width, H = (int)args.height;
-    const int x0 = (int)(sx * Slot::STRIP_W), y0 = (int)(sy * args.strip_rows);
+    const int x0 = (int)(sx * Slot<R>::STRIP_W), y0 = (int)(sy * args.strip_rows);
     const int y_end = y0 + (int)args.strip_rows < H ? y0 + (int)args.strip_rows : H;
 
-    // the strip column's centre (see the top of the file), per image
+    // the strip column's centre (top of ssimf_kernels.hip), per image
     f2 cen;
     {
         const int64_t cx = x0 + 64 < W ? x0 + 64 : W - 1, cy = (H - 1) / 2;
@@ -266,7 +257,7 @@ void ssimf_strip_kernel(const KFArgs args)
         }
     };
     auto fetch = [&](int r) { fetch_to(r, va, vb); };
-    auto stage_from = [&](Slot& s, const float (&ia)[NLOAD], const float (&ib)[NLOAD]) {   // registers -> the two planes of a slot
+    auto stage_from = [&](Slot<R>& s, const float (&ia)[NLOAD], const float (&ib)[NLOAD]) {   // registers -> the two planes of a slot
 #pragma unroll
         for (int t = 0; t < NLOAD; ++t) {
             const f2 ab = f2{ia[t], ib[t]} - cen;         // (a', b')
@@ -276,14 +267,14 @@ void ssimf_strip_kernel(const KFArgs args)
             s.q[p] = f2{__builtin_fmaf(b, b, a * a), a * b};
         }
     };
-    auto stage = [&](Slot& s) { stage_from(s, va, vb); };
+    auto stage = [&](Slot<R>& s) { stage_from(s, va, vb); };
 
-    f2 accAB[2][11], accQ[2][11];
+    f2 accAB[2][N], accQ[2][N];
 #pragma unroll
-    for (int k = 0; k < 11; ++k) accAB[0][k] = accAB[1][k] = accQ[0][k] = accQ[1][k] = f2{0.0f, 0.0f};
+    for (int k = 0; k < N; ++k) accAB[0][k] = accAB[1][k] = accQ[0][k] = accQ[1][k] = f2{0.0f, 0.0f};
     double colsum[2] = {0.0, 0.0};
 
-    const int r_begin = y0 - 5;
+    const int r_begin = y0 - R;
     {
         float a0[NLOAD], b0[NLOAD], a1[NLOAD], b1[NLOAD];
         fetch_to(r_begin, a0, b0);
@@ -295,7 +286,7 @@ void ssimf_strip_kernel(const KFArgs args)
     wave_sync();
 
     // Map addressing: uniform row base + non-negative per-column offset (bytes; WIDE: elements).
-    const int refM = pd.map_step >= 0 ? x0 : (x0 + Slot::STRIP_W - 1 < W ? x0 + Slot::STRIP_W - 1 : W - 1);
+    const int refM = pd.map_step >= 0 ? x0 : (x0 + Slot<R>::STRIP_W - 1 < W ? x0 + Slot<R>::STRIP_W - 1 : W - 1);
     const bool has_map = pd.map != nullptr;
     const int  map_records = has_map ? 0x7FFFFFFF : 0;
     Off  offM[2] = {0, 0};
@@ -310,27 +301,31 @@ void ssimf_strip_kernel(const KFArgs args)
         }
     }
 
-    f2 wab[12], wq[12];
-    const int e = 2 * lane + PAD - 5;                     // even: the 16-byte reads are aligned
-    auto load_ab = [&](const Slot& s) {
+    f2 wab[NWIN], wq[NWIN];
+    const int e = 2 * lane + PAD - R;                     // even: the 16-byte reads are aligned
+    auto load_ab = [&](const Slot<R>& s) {
 #pragma unroll
-        for (int t = 0; t < 6; ++t) {
+        for (int t = 0; t <= R; ++t) {
             const f4 v = *reinterpret_cast<const f4*>(&s.ab[e + 2 * t]);
             wab[2 * t] = v.xy; wab[2 * t + 1] = v.zw;
+        }
+    };
+    // The folded sums of a window, centre first: column c of the lane's pair has its centre at window pixel R + c.
+    auto fold = [&](f2 (&s)[2][R + 1], const f2 (&w)[NWIN]) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int m = R + c;
+            s[c][0] = w[m];
+#pragma unroll
+            for (int i = 1; i <= R; ++i) s[c][i] = w[m + i] + w[m - i];
         }
     };
     // The (a', b') row pass of the row about to be blurred: computed at the end of the previous iteration and carried over.
     f2 hab[2];
     auto fold_ab = [&]() {
-        f2 s[2][6];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int m = 5 + c;
-            s[c][0] = wab[m];
-#pragma unroll
-            for (int i = 1; i <= 5; ++i) s[c][i] = wab[m + i] + wab[m - i];
-        }
-        rows_pair(hab[0], hab[1], s[0], s[1], gf);
+        f2 s[2][R + 1];
+        fold(s, wab);
+        rows_pair<R>(hab[0], hab[1], s[0], s[1], gf);
     };
     load_ab(ring[0]);
     fold_ab();
@@ -339,30 +334,30 @@ void ssimf_strip_kernel(const KFArgs args)
         constexpr int cur = decltype(slot)::value;
         constexpr int phase = decltype(phase_tag)::value;
         constexpr int KMIN = decltype(kmin_tag)::value;
-        const Slot& s = ring[cur];
+        const Slot<R>& s = ring[cur];
         __builtin_amdgcn_s_setprio(2);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int t = 0; t < 6; ++t) {
+        for (int t = 0; t <= R; ++t) {
             const f4 u = *reinterpret_cast<const f4*>(&s.q[e + 2 * t]);
             wq[2 * t] = u.xy;  wq[2 * t + 1] = u.zw;
         }
         __builtin_amdgcn_sched_barrier(0);
-        columns_pair<KMIN>(accAB[0], accAB[1], hab[0], hab[1], gf);
+        columns_pair<R, KMIN>(accAB[0], accAB[1], hab[0], hab[1], gf);
         __builtin_amdgcn_sched_barrier(0);
         {
-            const f2 s0[6] = {wq[5], wq[6] + wq[4], wq[7] + wq[3], wq[8] + wq[2], wq[9] + wq[1], wq[10] + wq[0]};
-            const f2 s1[6] = {wq[6], wq[7] + wq[5], wq[8] + wq[4], wq[9] + wq[3], wq[10] + wq[2], wq[11] + wq[1]};
-            blur_pair<KMIN>(accQ[0], accQ[1], s0, s1, gf);
+            f2 sq[2][R + 1];
+            fold(sq, wq);
+            blur_pair<R, KMIN>(accQ[0], accQ[1], sq[0], sq[1], gf);
         }
         __builtin_amdgcn_sched_barrier(0);
-        // ring entry 0 is now the finished output row r - 5
+        // ring entry 0 is now the finished output row r - R
         if constexpr (phase != ROW_WARMUP) {
             const f2 v = ssim_px2(accAB[0][0], accAB[1][0], accQ[0][0], accQ[1][0], cen, args.c1, args.c2);
             colsum[0] += (double)v.x;
             colsum[1] += (double)v.y;
             if constexpr (MAP != 0) {
-                const int y = r - 5;
+                const int y = r - R;
                 float* mrow = pd.map + ((int64_t)y * pd.map_stride + (int64_t)refM * pd.map_step);
                 const float v0 = v.x, v1 = v.y;
                 if constexpr (WIDE) {
@@ -372,14 +367,8 @@ void ssimf_strip_kernel(const KFArgs args)
                     // branch-free: a raw buffer over [row base, +2 GiB) -- empty for a pair without a map in a batch with maps --;
                     // lanes with nothing to store present an offset beyond it
                     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(mrow, 0, map_records, 0x00020000);
-                    if constexpr (MAP == 2) {
-                        typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-                        const u2 both = {__builtin_bit_cast(uint32_t, v0), __builtin_bit_cast(uint32_t, v1)};
-                        __builtin_amdgcn_raw_buffer_store_b64(both, rs, offM[0], 0, 2);
-                    } else {
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v0), rs, offM[0], 0, 2);
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v1), rs, offM[1], 0, 2);
-                    }
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v0), rs, offM[0], 0, 2);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v1), rs, offM[1], 0, 2);
                 }
             }
         }
@@ -401,13 +390,14 @@ void ssimf_strip_kernel(const KFArgs args)
     typedef std::integral_constant<int, ROW_WARMUP> Warm;
     typedef std::integral_constant<int, 0> K0;
     int r = r_begin;
-    // the ten warm-up rows in pairs (the two LDS slots); warm-up row i only feeds ring entries k >= 10 - i
-    row(r, S0(), Warm(), std::integral_constant<int, 9>());     row(r + 1, S1(), Warm(), std::integral_constant<int, 9>());
-    row(r + 2, S0(), Warm(), std::integral_constant<int, 7>()); row(r + 3, S1(), Warm(), std::integral_constant<int, 7>());
-    row(r + 4, S0(), Warm(), std::integral_constant<int, 5>()); row(r + 5, S1(), Warm(), std::integral_constant<int, 5>());
-    r += 6;
+    // the 2R warm-up rows in pairs (the two LDS slots); warm-up row i only feeds ring entries k >= 2R - i: the first pair skips the
+    // others, the later pairs run as one loop over the full ring (what they write below 2R - i stands for rows above the strip and
+    // leaves the ring before the first finished row is read)
+    row(r, S0(), Warm(), std::integral_constant<int, 2 * R - 1>());
+    row(r + 1, S1(), Warm(), std::integral_constant<int, 2 * R - 1>());
+    r += 2;
 #pragma unroll 1
-    for (int i = 0; i < 2; ++i, r += 2) {
+    for (int i = 1; i < R; ++i, r += 2) {
         row(r, S0(), Warm(), K0());
         row(r + 1, S1(), Warm(), K0());
     }
@@ -440,11 +430,11 @@ void ssimf_strip_kernel(const KFArgs args)
     }
 }
 
-// Per-image sum of the cell partials in a fixed order: thread t of 1024 adds cells t, t + 1024, ... in that order, each wave
-// runs a fixed xor butterfly, and the 16 wave totals are added in wave order.  One workgroup per image.
+// Per-image sum of the cell partials in a fixed order (ssimf_reduce_kernel): thread t of 1024 adds cells t, t + 1024, ... in that order,
+// each wave runs a fixed xor butterfly, and the 16 wave totals are added in wave order.  One workgroup per image.
 constexpr int kReduceThreads = 1024;
 
-__global__ __launch_bounds__(kReduceThreads) void ssimf_reduce_kernel(const double* __restrict__ partials, uint64_t per_image, double* __restrict__ sums)
+__global__ __launch_bounds__(kReduceThreads) void ssimk_reduce_kernel(const double* __restrict__ partials, uint64_t per_image, double* __restrict__ sums)
 {
     __shared__ double sh[kReduceThreads / 64];
     const double* p = partials + (size_t)blockIdx.x * per_image;
@@ -466,42 +456,37 @@ __global__ __launch_bounds__(kReduceThreads) void ssimf_reduce_kernel(const doub
     }
 }
 
-const uint64_t kMaxBlocks = (uint64_t(1) << 26) - 1;      // x 64 work-items stays below 2^32
-const uint64_t kMaxGradBlocks = (uint64_t(1) << 24) - 1;  // x 256 work-items stays below 2^32
-
-uint32_t cell_rows_of(uint32_t height) { return height >= 2048 ? 32u : 8u; }
+uint32_t cell_rows_of(uint32_t height) { return height >= 2048 ? 32u : 8u; }       // as ssimf_kernels.hip: the cells are the same
 
 // ---- the gradient ------------------------------------------------------------------------------------------------------------
-// ssimf_grad_kernel: one 256-lane workgroup = one 32 x 32 tile of gradient pixels at an absolute position; everything between the
-// samples and the gradient stays in LDS.
-//   1. the centred samples (a', b') of the tile + 10 (52 x 52, edge-clamped coordinates) -> LDS;
-//   2. row pass of (a', b') and (a'^2 + b'^2, a'b') on 52 rows x 42 columns, folded sums and tap order as the forward kernel;
-//   3. column pass on the tile + 5 (42 x 42), in source-row order as the forward kernel; per pixel the SSIM terms and the
-//      weighted partials k d_mu, k d_aa, k d_ab (k d_mu of both images when both gradients are wanted: d_bb equals d_aa) -> LDS;
-//      a position outside the image holds 0: it is not a clamped copy, the clamp is in the adjoint's weights;
-//   4. adjoint row pass (42 rows x 32 columns), 5. adjoint column pass (32 x 32), both as gathers: gradient pixel q collects
-//      w(q, j) v(q + j), j = -5 .. 5 in that order, the first product plain, the others fused;  w(q, j) is the tap g|j| in the
-//      interior, and on the first (last) row or column the sum of the taps the forward pass clamped onto it from p = q + j:
-//      tail[|j|] = g|j| + ... + g5 for j >= 0 (j <= 0), and the sum of all taps on an axis of size 1;
+// ssimk_grad_kernel: ssimf_grad_kernel / ssimw_grad_kernel for radius R.  One 256-lane workgroup = one 32 x 32 tile of gradient pixels
+// at an absolute position; everything between the samples and the gradient stays in LDS.
+//   1. the centred samples (a', b') of the tile + 2R (edge-clamped coordinates) -> LDS;
+//   2. row pass of (a', b') and (a'^2 + b'^2, a'b') on 32 + 4R rows x 32 + 2R columns, folded sums and tap order as the forward kernel;
+//   3. column pass on the tile + R, in source-row order as the forward kernel; per pixel the SSIM terms and the weighted partials
+//      k d_mu, k d_aa, k d_ab, plain fp32 products (k = 0 does not hide a NaN statistic) -> LDS; a position outside the image holds 0
+//      and reads nothing from gMap;
+//   4. adjoint row pass, 5. adjoint column pass, both as gathers: gradient pixel q collects w(q, j) v(q + j), j = -R .. R in that
+//      order, the first product plain, the others fused; w(q, j) is the tap g|j| in the interior, tail[|j|] = g|j| + ... + gR on the
+//      first (last) row or column for j >= 0 (j <= 0), and the sum of all taps on an axis of size 1;
 //   6. dLoss/da = Gt(k d_mu_a) + 2 a' Gt(k d_aa) + b' Gt(k d_ab), one store per pixel.
-// The derivative is taken in the centred variables: d_mu = 2 mu_b A2 / (B1 B2) - 2 mu_a ssim / B1 - 2 mu_a' d_aa - mu_b' d_ab with
-// mu = mu' + c.  With taps that sum to 1 this is the header's formula with the terms that cancel across its three summands
-// (2 c_a Gt(k d_aa) + c_b Gt(k d_ab) against Gt of the same inside k d_mu) taken out before they are rounded.
-// Every gradient pixel is written by one work-item in a fixed order, and the tile grid is fixed by the image: no atomics, the
-// same bits in any batch.
-enum { GT = kSFTile, GIN = GT + 20, GST = GT + 10 };
+// Every gradient pixel is written by one work-item in a fixed order, and the tile grid is fixed by the image: no atomics, the same
+// bits in any batch.
+enum { GT = kSFTile };
 
-struct KGArgs {
-    const PairFDesc* descs;
-    const GradFDesc* grads;
-    const float*     g_out;
+struct KKGArgs {
+    const PairFDesc*    descs;
+    const GradFDesc*    grads;
+    const float*        g_out;       // the scalar upstream form, or NULL
+    const GradOutFDesc* gouts;       // the per-pixel upstream form (g_out == NULL)
     uint32_t width, height, tiles_x, tiles_y;
     float    c1, c2, range;
-    float    gf[6], tail[6], total;
+    float    gf[MAXR + 1], tail[MAXR + 1], total;
 };
 
 // w(q, j) above for an axis of n pixels.
-__device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float (&g)[6], const float (&tail)[6], float total)
+template <int R>
+__device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float (&g)[R + 1], const float (&tail)[R + 1], float total)
 {
     const int aj = j < 0 ? -j : j;
     float w = g[aj];
@@ -513,13 +498,16 @@ __device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float
 
 // WHICH: 1 dLoss/dA, 2 dLoss/dB, 3 both.  The statistics are computed in the same (a, b) order in all three, so a gradient has
 // the same bits alone and together with the other.
-template <int WHICH>
+template <int R, int WHICH>
 __global__ __launch_bounds__(256)
-void ssimf_grad_kernel(const KGArgs args)
+void ssimk_grad_kernel(const KKGArgs args)
 {
+    static_assert(R >= 1 && R <= MAXR, "radius");
+    constexpr int GIN = GT + 4 * R, GST = GT + 2 * R, N = 2 * R + 1;
     constexpr int NP = WHICH == 3 ? 4 : 3;                       // partial planes: d_mu (of A, or of the one wanted), d_aa, d_ab, d_mu of B
     constexpr int XN = 2 * GIN * GIN > NP * GST * GST ? 2 * GIN * GIN : NP * GST * GST;
     constexpr int YN = 4 * GIN * GST;                            // >= NP * GST * GT
+    static_assert(YN >= NP * GST * GT, "Q fits");
     __shared__ __attribute__((aligned(16))) float lds[XN + YN];
     f2*    in  = reinterpret_cast<f2*>(lds);                     // [GIN][GIN] (a', b')
     float* P   = lds;                                            // [NP][GST][GST], after the row pass has consumed `in`
@@ -536,11 +524,18 @@ void ssimf_grad_kernel(const KGArgs args)
     const PairFDesc pd = args.descs[img];
     const GradFDesc gd = args.grads[img];
     const gptr_cf32 pa = (gptr_cf32)pd.a, pb = (gptr_cf32)pd.b;
-    const float gf[6] = {args.gf[0], args.gf[1], args.gf[2], args.gf[3], args.gf[4], args.gf[5]};
-    const float tail[6] = {args.tail[0], args.tail[1], args.tail[2], args.tail[3], args.tail[4], args.tail[5]};
-    const float k = (float)((double)((gptr_cf32)args.g_out)[img] / ((double)W * (double)H));
+    float gf[R + 1], tail[R + 1];
+#pragma unroll
+    for (int i = 0; i <= R; ++i) { gf[i] = args.gf[i]; tail[i] = args.tail[i]; }
+    // the upstream gradient: one k for the launch's pair, or a plane read per pixel
+    const bool per_pixel = args.g_out == nullptr;
+    GradOutFDesc go = {nullptr, 0, 0};
+    float k_uniform = 0.0f;
+    if (per_pixel) go = args.gouts[img];
+    else           k_uniform = (float)((double)((gptr_cf32)args.g_out)[img] / ((double)W * (double)H));
+    const gptr_cf32 pk = (gptr_cf32)go.g;
 
-    f2 cen;                                                      // the strip column's centre (top of the file)
+    f2 cen;                                                      // the strip column's centre (top of ssimf_kernels.hip)
     {
         const int xs = x0 & ~(kSFStripW - 1);
         const int64_t cx = xs + 64 < W ? xs + 64 : W - 1, cy = (H - 1) / 2;
@@ -551,7 +546,7 @@ void ssimf_grad_kernel(const KGArgs args)
     // 1. samples
     for (int idx = tid; idx < GIN * GIN; idx += 256) {
         const int j = idx / GIN, i = idx - j * GIN;
-        int x = x0 - 10 + i, y = y0 - 10 + j;
+        int x = x0 - 2 * R + i, y = y0 - 2 * R + j;
         x = x < 0 ? 0 : (x > W - 1 ? W - 1 : x);
         y = y < 0 ? 0 : (y > H - 1 ? H - 1 : y);
         const f2 v = {pa[(int64_t)x * pd.a_step + (int64_t)y * pd.a_stride], pb[(int64_t)x * pd.b_step + (int64_t)y * pd.b_stride]};
@@ -559,20 +554,22 @@ void ssimf_grad_kernel(const KGArgs args)
     }
     __syncthreads();
 
-    // 2. row pass: H*[j][u] is the blur along x at image column x0 - 5 + u of source row y0 - 10 + j
+    // 2. row pass: H*[j][u] is the blur along x at image column x0 - R + u of source row y0 - 2R + j
     for (int idx = tid; idx < GIN * GST; idx += 256) {
         const int j = idx / GST, u = idx - j * GST;
         const f2* row = in + j * GIN + u;
-        f2 ab[11], q[11];
+        f2 ab[N], q[N];
 #pragma unroll
-        for (int t = 0; t < 11; ++t) {
+        for (int t = 0; t < N; ++t) {
             ab[t] = row[t];
             q[t] = f2{__builtin_fmaf(ab[t].y, ab[t].y, ab[t].x * ab[t].x), ab[t].x * ab[t].y};
         }
-        const f2 sab[6] = {ab[5], ab[6] + ab[4], ab[7] + ab[3], ab[8] + ab[2], ab[9] + ab[1], ab[10] + ab[0]};
-        const f2 sq[6] = {q[5], q[6] + q[4], q[7] + q[3], q[8] + q[2], q[9] + q[1], q[10] + q[0]};
+        f2 sab[R + 1], sq[R + 1];
+        sab[0] = ab[R]; sq[0] = q[R];
+#pragma unroll
+        for (int i = 1; i <= R; ++i) { sab[i] = ab[R + i] + ab[R - i]; sq[i] = q[R + i] + q[R - i]; }
         f2 hab, hq;
-        rows_pair(hab, hq, sab, sq, gf);
+        rows_pair<R>(hab, hq, sab, sq, gf);
         Hab[idx] = hab;
         Hq[idx] = hq;
     }
@@ -581,15 +578,17 @@ void ssimf_grad_kernel(const KGArgs args)
     // 3. column pass, SSIM terms, weighted partials
     for (int idx = tid; idx < GST * GST; idx += 256) {
         const int v = idx / GST, u = idx - v * GST;
-        const int px = x0 - 5 + u, py = y0 - 5 + v;
+        const int px = x0 - R + u, py = y0 - R + v;
         float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (px >= 0 && px < W && py >= 0 && py < H) {
+            float k = k_uniform;
+            if (per_pixel) k = pk[(int64_t)px * go.g_step + (int64_t)py * go.g_stride];     // in flight during the column pass
             const f2* cab = Hab + v * GST + u;
             const f2* cq = Hq + v * GST + u;
-            f2 m = cab[0] * f2{gf[5], gf[5]}, e = cq[0] * f2{gf[5], gf[5]};
+            f2 m = cab[0] * f2{gf[R], gf[R]}, e = cq[0] * f2{gf[R], gf[R]};
 #pragma unroll
-            for (int t = 1; t < 11; ++t) {
-                const float w = gf[t < 5 ? 5 - t : t - 5];
+            for (int t = 1; t < N; ++t) {
+                const float w = gf[t < R ? R - t : t - R];
                 m = fma_(cab[t * GST], f2{w, w}, m);
                 e = fma_(cq[t * GST], f2{w, w}, e);
             }
@@ -621,9 +620,9 @@ void ssimf_grad_kernel(const KGArgs args)
     // 4. adjoint row pass: Q[pl][v][x], x = tid % 32 for every position of this lane
     {
         const int x = tid & (GT - 1), qx = x0 + x;
-        float wx[11];
+        float wx[N];
 #pragma unroll
-        for (int j = -5; j <= 5; ++j) wx[j + 5] = adjoint_weight(qx, W, j, gf, tail, args.total);
+        for (int j = -R; j <= R; ++j) wx[j + R] = adjoint_weight<R>(qx, W, j, gf, tail, args.total);
         for (int idx = tid; idx < GST * GT; idx += 256) {
             const int v = idx / GT;
 #pragma unroll
@@ -631,7 +630,7 @@ void ssimf_grad_kernel(const KGArgs args)
                 const float* src = P + pl * GST * GST + v * GST + x;
                 float acc = src[0] * wx[0];
 #pragma unroll
-                for (int t = 1; t < 11; ++t) acc = __builtin_fmaf(src[t], wx[t], acc);
+                for (int t = 1; t < N; ++t) acc = __builtin_fmaf(src[t], wx[t], acc);
                 Q[pl * GST * GT + idx] = acc;
             }
         }
@@ -643,16 +642,16 @@ void ssimf_grad_kernel(const KGArgs args)
         const int y = idx / GT, x = idx - y * GT;
         const int qx = x0 + x, qy = y0 + y;
         if (qx >= W || qy >= H) continue;
-        float wy[11];
+        float wy[N];
 #pragma unroll
-        for (int j = -5; j <= 5; ++j) wy[j + 5] = adjoint_weight(qy, H, j, gf, tail, args.total);
+        for (int j = -R; j <= R; ++j) wy[j + R] = adjoint_weight<R>(qy, H, j, gf, tail, args.total);
         float r[NP];
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) {
             const float* src = Q + pl * GST * GT + y * GT + x;
             float acc = src[0] * wy[0];
 #pragma unroll
-            for (int t = 1; t < 11; ++t) acc = __builtin_fmaf(src[t * GT], wy[t], acc);
+            for (int t = 1; t < N; ++t) acc = __builtin_fmaf(src[t * GT], wy[t], acc);
             r[pl] = acc;
         }
         const float a = pa[(int64_t)qx * pd.a_step + (int64_t)qy * pd.a_stride] - cen.x;
@@ -668,26 +667,58 @@ void ssimf_grad_kernel(const KGArgs args)
     }
 }
 
+template <int R>
+hipError_t launch_strip(const KKArgs& ka, bool map, bool wide, const dim3& grid, hipStream_t stream)
+{
+    const dim3 block(64);
+    if (wide) {
+        if (map) hipLaunchKernelGGL((ssimk_strip_kernel<R, 1, true>), grid, block, 0, stream, ka);
+        else     hipLaunchKernelGGL((ssimk_strip_kernel<R, 0, true>), grid, block, 0, stream, ka);
+    } else if (map) hipLaunchKernelGGL((ssimk_strip_kernel<R, 1, false>), grid, block, 0, stream, ka);
+    else            hipLaunchKernelGGL((ssimk_strip_kernel<R, 0, false>), grid, block, 0, stream, ka);
+    return hipGetLastError();
+}
+
+template <int R>
+hipError_t launch_grad(const KKGArgs& ka, int which, const dim3& grid, hipStream_t stream)
+{
+    const dim3 block(256);
+    if (which == 1)      hipLaunchKernelGGL((ssimk_grad_kernel<R, 1>), grid, block, 0, stream, ka);
+    else if (which == 2) hipLaunchKernelGGL((ssimk_grad_kernel<R, 2>), grid, block, 0, stream, ka);
+    else                 hipLaunchKernelGGL((ssimk_grad_kernel<R, 3>), grid, block, 0, stream, ka);
+    return hipGetLastError();
+}
+
 } // namespace
 
-void ssimf_constants(float data_range, float& c1, float& c2)
+bool window_taps(uint32_t radius, uint32_t kind, float sigma, float (&gf)[kSKMaxRadius + 1])
 {
-    const double R = (double)data_range;
-    c1 = (float)((0.01 * R) * (0.01 * R));
-    c2 = (float)((0.03 * R) * (0.03 * R));
+    if (radius < 1 || radius > kSKMaxRadius) return false;
+    for (int i = 0; i <= kSKMaxRadius; ++i) gf[i] = 0.0f;
+    if (kind == kSKUniform) {
+        for (uint32_t i = 0; i <= radius; ++i) gf[i] = (float)(1.0 / (double)(2 * radius + 1));
+        return true;
+    }
+    if (kind != kSKGaussian || !(sigma > 0.0f) || !std::isfinite(sigma)) return false;
+    const double s = (double)sigma;
+    double g[kSKMaxRadius + 1], norm = 0.0;
+    for (int i = 0; i <= (int)radius; ++i) {
+        g[i] = exp(-(double)(i * i) / (2.0 * s * s));
+        norm += (i == 0) ? g[i] : 2.0 * g[i];
+    }
+    for (int i = 0; i <= (int)radius; ++i) gf[i] = (float)(g[i] / norm);
+    return true;
 }
 
-uint32_t ssimf_max_count(uint32_t width, uint32_t height)
+void window_tails(uint32_t radius, const float (&gf)[kSKMaxRadius + 1], float (&tail)[kSKMaxRadius + 1], float& total)
 {
-    if (width == 0 || height == 0 || width > kSFMaxDim || height > kSFMaxDim) return 0;
-    // the worst case: strips of the smallest height
-    const uint64_t cr = cell_rows_of(height);
-    const uint64_t per = (uint64_t)((width + kSFStripW - 1) / kSFStripW) * ((height + cr - 1) / cr);
-    const uint64_t tiles = (uint64_t)((width + kSFTile - 1) / kSFTile) * ((height + kSFTile - 1) / kSFTile);
-    return (uint32_t)std::min<uint64_t>(std::min(kMaxBlocks / per, kMaxGradBlocks / tiles), 65535);
+    for (int i = 0; i <= kSKMaxRadius; ++i) tail[i] = 0.0f;
+    double t = 0.0;
+    for (int i = (int)radius; i >= 0; --i) { t += (double)gf[i]; tail[i] = (float)t; }
+    total = (float)(2.0 * t - (double)gf[0]);
 }
 
-GeometryF planf(uint32_t width, uint32_t height, uint32_t count, int cu_count)
+GeometryF plank(uint32_t radius, uint32_t width, uint32_t height, uint32_t count, int cu_count)
 {
     GeometryF g;
     g.width = width; g.height = height; g.count = count;
@@ -695,8 +726,7 @@ GeometryF planf(uint32_t width, uint32_t height, uint32_t count, int cu_count)
     g.cells_x = (width + 63) / 64;
     g.cells_y = (height + g.cell_rows - 1) / g.cell_rows;
     g.strips_x = (width + kSFStripW - 1) / kSFStripW;
-    // three waves per SIMD, four SIMDs per CU: a round of strips; pick the strip height (whole cells, at most 2048 rows) that
-    // finishes the launch's strips in the fewest row-times, 10 warm-up rows included
+    // planf()'s choice of the strip height with 2 * radius warm-up rows
     const uint64_t slots = (uint64_t)(cu_count > 0 ? cu_count : 256) * 4 * 3;
     const uint64_t cols = (uint64_t)g.strips_x * count;
     uint64_t best = ~uint64_t(0);
@@ -704,7 +734,7 @@ GeometryF planf(uint32_t width, uint32_t height, uint32_t count, int cu_count)
     for (uint32_t rows = g.cell_rows; rows <= std::max<uint32_t>(g.cell_rows, 2048); rows += g.cell_rows) {
         const uint64_t per_col = (height + rows - 1) / rows;
         const uint64_t rounds = (cols * per_col + slots - 1) / slots;
-        const uint64_t cost = rounds * (std::min<uint64_t>(rows, height) + 10);
+        const uint64_t cost = rounds * (std::min<uint64_t>(rows, height) + 2 * radius);
         if (cost <= best) { best = cost; best_rows = rows; }
         if (rows >= height) break;
     }
@@ -713,12 +743,13 @@ GeometryF planf(uint32_t width, uint32_t height, uint32_t count, int cu_count)
     return g;
 }
 
-hipError_t launch_ssimf(const GeometryF& geo, const PairFDesc* descs_dev, bool map, bool map_unit, bool wide, float data_range,
-                        const float (&taps)[6], int xcd_count, double* partials, double* sums, hipStream_t stream)
+hipError_t launch_ssimk(uint32_t radius, const float (&gf)[kSKMaxRadius + 1], const GeometryF& geo, const PairFDesc* descs_dev, bool map, bool wide,
+                        float data_range, int xcd_count, double* partials, double* sums, hipStream_t stream)
 {
     if (geo.count == 0) return hipSuccess;
-    if (!(data_range > 0.0f) || !std::isfinite(data_range) || geo.count > ssimf_max_count(geo.width, geo.height)) return hipErrorInvalidValue;
-    KFArgs ka;
+    if (radius < 1 || radius > MAXR || !(data_range > 0.0f) || !std::isfinite(data_range) || geo.count > ssimf_max_count(geo.width, geo.height))
+        return hipErrorInvalidValue;
+    KKArgs ka;
     ka.descs = descs_dev;
     ka.width = geo.width; ka.height = geo.height;
     ka.strip_rows = geo.strip_rows; ka.strips_x = geo.strips_x; ka.strips_y = geo.strips_y;
@@ -729,41 +760,44 @@ hipError_t launch_ssimf(const GeometryF& geo, const PairFDesc* descs_dev, bool m
     ka.partials = partials;
     ka.range = data_range;
     ssimf_constants(data_range, ka.c1, ka.c2);
-    for (int i = 0; i < 6; ++i) ka.gf[i] = taps[i];
-    const dim3 grid((uint32_t)((uint64_t)geo.strips_x * geo.strips_y * geo.count)), block(64);
-    if (wide) {
-        if (map) hipLaunchKernelGGL((ssimf_strip_kernel<1, true>), grid, block, 0, stream, ka);
-        else     hipLaunchKernelGGL((ssimf_strip_kernel<0, true>), grid, block, 0, stream, ka);
-    } else if (!map)   hipLaunchKernelGGL((ssimf_strip_kernel<0, false>), grid, block, 0, stream, ka);
-    else if (map_unit) hipLaunchKernelGGL((ssimf_strip_kernel<2, false>), grid, block, 0, stream, ka);
-    else               hipLaunchKernelGGL((ssimf_strip_kernel<1, false>), grid, block, 0, stream, ka);
-    hipError_t e = hipGetLastError();
+    for (int i = 0; i <= MAXR; ++i) ka.gf[i] = gf[i];
+    const dim3 grid((uint32_t)((uint64_t)geo.strips_x * geo.strips_y * geo.count));
+    hipError_t e;
+    switch (radius) {
+    case 1:  e = launch_strip<1>(ka, map, wide, grid, stream); break;
+    case 2:  e = launch_strip<2>(ka, map, wide, grid, stream); break;
+    case 3:  e = launch_strip<3>(ka, map, wide, grid, stream); break;
+    default: e = launch_strip<4>(ka, map, wide, grid, stream); break;
+    }
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ssimf_reduce_kernel, dim3(geo.count), dim3(kReduceThreads), 0, stream, partials, geo.cells_per_image(), sums);
+    hipLaunchKernelGGL(ssimk_reduce_kernel, dim3(geo.count), dim3(kReduceThreads), 0, stream, partials, geo.cells_per_image(), sums);
     return hipGetLastError();
 }
 
-hipError_t launch_ssimf_grad(uint32_t width, uint32_t height, uint32_t count, const PairFDesc* descs_dev, const GradFDesc* grads_dev,
-                             const float* g_out, float data_range, const float (&taps)[6], int which, hipStream_t stream)
+hipError_t launch_ssimk_grad(uint32_t radius, const float (&gf)[kSKMaxRadius + 1], uint32_t width, uint32_t height, uint32_t count,
+                             const PairFDesc* descs_dev, const GradFDesc* grads_dev, const float* g_out, const GradOutFDesc* gouts_dev,
+                             float data_range, int which, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!(data_range > 0.0f) || !std::isfinite(data_range) || which < 1 || which > 3 || count > ssimf_max_count(width, height)) return hipErrorInvalidValue;
-    KGArgs ka;
-    ka.descs = descs_dev; ka.grads = grads_dev; ka.g_out = g_out;
+    if (radius < 1 || radius > MAXR || !(data_range > 0.0f) || !std::isfinite(data_range) || which < 1 || which > 3 ||
+        (g_out == NULL) == (gouts_dev == NULL) || count > ssimf_max_count(width, height))
+        return hipErrorInvalidValue;
+    KKGArgs ka;
+    ka.descs = descs_dev; ka.grads = grads_dev; ka.g_out = g_out; ka.gouts = g_out ? NULL : gouts_dev;
     ka.width = width; ka.height = height;
     ka.tiles_x = (width + kSFTile - 1) / kSFTile; ka.tiles_y = (height + kSFTile - 1) / kSFTile;
     ka.range = data_range;
     ssimf_constants(data_range, ka.c1, ka.c2);
-    for (int i = 0; i < 6; ++i) ka.gf[i] = taps[i];
-    // tail[d] = g_d + ... + g_5 and the sum of all eleven taps: sums of the float taps in double, rounded once
-    double t = 0.0;
-    for (int i = 5; i >= 0; --i) { t += (double)ka.gf[i]; ka.tail[i] = (float)t; }
-    ka.total = (float)(2.0 * t - (double)ka.gf[0]);
-    const dim3 grid((uint32_t)((uint64_t)ka.tiles_x * ka.tiles_y * count)), block(256);
-    if (which == 1)      hipLaunchKernelGGL((ssimf_grad_kernel<1>), grid, block, 0, stream, ka);
-    else if (which == 2) hipLaunchKernelGGL((ssimf_grad_kernel<2>), grid, block, 0, stream, ka);
-    else                 hipLaunchKernelGGL((ssimf_grad_kernel<3>), grid, block, 0, stream, ka);
-    return hipGetLastError();
+    float tail[kSKMaxRadius + 1];
+    window_tails(radius, gf, tail, ka.total);
+    for (int i = 0; i <= MAXR; ++i) { ka.gf[i] = gf[i]; ka.tail[i] = tail[i]; }
+    const dim3 grid((uint32_t)((uint64_t)ka.tiles_x * ka.tiles_y * count));
+    switch (radius) {
+    case 1:  return launch_grad<1>(ka, which, grid, stream);
+    case 2:  return launch_grad<2>(ka, which, grid, stream);
+    case 3:  return launch_grad<3>(ka, which, grid, stream);
+    default: return launch_grad<4>(ka, which, grid, stream);
+    }
 }
 
 } // namespace ssim_hip

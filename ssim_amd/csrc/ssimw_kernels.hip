@@ -261,7 +261,8 @@ void ssimw_grad_kernel(const KWArgs<TYPE> args)
     }
 }
 
-// the true 1-D Gaussian, sigma 1.5, normalised over the 11 taps, rounded to float: the engine's taps, centre first
+// the true 1-D Gaussian, sigma 1.5, normalised over the 11 taps, rounded to float: the engine's taps, centre first (16-bit samples: the
+// fixed window)
 void gaussian_taps(float (&gf)[6])
 {
     double g[6], norm = 0.0;
@@ -274,7 +275,8 @@ void gaussian_taps(float (&gf)[6])
 
 template <int TYPE>
 hipError_t launch(uint32_t width, uint32_t height, uint32_t count, const typename Sample<TYPE>::Pair* descs_dev,
-                  const typename Sample<TYPE>::Grad* grads_dev, const GradOutFDesc* gouts_dev, float data_range, int which, hipStream_t stream)
+                  const typename Sample<TYPE>::Grad* grads_dev, const GradOutFDesc* gouts_dev, float data_range, const float* taps, int which,
+                  hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
     if (!(data_range > 0.0f) || !std::isfinite(data_range) || which < 1 || which > 3 || count > ssimf_max_count(width, height)) return hipErrorInvalidValue;
@@ -284,7 +286,8 @@ hipError_t launch(uint32_t width, uint32_t height, uint32_t count, const typenam
     ka.tiles_x = (width + kSFTile - 1) / kSFTile; ka.tiles_y = (height + kSFTile - 1) / kSFTile;
     ka.range = data_range;
     ssimf_constants(data_range, ka.c1, ka.c2);
-    gaussian_taps(ka.gf);
+    if (taps) { for (int i = 0; i < 6; ++i) ka.gf[i] = taps[i]; }      // the caller's window (float32 samples)
+    else      gaussian_taps(ka.gf);
     // tail[d] = g_d + ... + g_5 and the sum of all eleven taps: sums of the float taps in double, rounded once
     double t = 0.0;
     for (int i = 5; i >= 0; --i) { t += (double)ka.gf[i]; ka.tail[i] = (float)t; }
@@ -299,16 +302,16 @@ hipError_t launch(uint32_t width, uint32_t height, uint32_t count, const typenam
 } // namespace
 
 hipError_t launch_ssimw_grad_f(uint32_t width, uint32_t height, uint32_t count, const PairFDesc* descs_dev, const GradFDesc* grads_dev,
-                               const GradOutFDesc* gouts_dev, float data_range, int which, hipStream_t stream)
+                               const GradOutFDesc* gouts_dev, float data_range, const float (&taps)[6], int which, hipStream_t stream)
 {
-    return launch<kSWTypeF32>(width, height, count, descs_dev, grads_dev, gouts_dev, data_range, which, stream);
+    return launch<kSWTypeF32>(width, height, count, descs_dev, grads_dev, gouts_dev, data_range, taps, which, stream);
 }
 
 hipError_t launch_ssimw_grad_h(uint32_t width, uint32_t height, uint32_t count, const PairHDesc* descs_dev, const GradHDesc* grads_dev,
                                int type, const GradOutFDesc* gouts_dev, float data_range, int which, hipStream_t stream)
 {
-    if (type == kSHTypeBF16) return launch<kSWTypeBF16>(width, height, count, descs_dev, grads_dev, gouts_dev, data_range, which, stream);
-    if (type == kSHTypeF16)  return launch<kSWTypeF16>(width, height, count, descs_dev, grads_dev, gouts_dev, data_range, which, stream);
+    if (type == kSHTypeBF16) return launch<kSWTypeBF16>(width, height, count, descs_dev, grads_dev, gouts_dev, data_range, NULL, which, stream);
+    if (type == kSHTypeF16)  return launch<kSWTypeF16>(width, height, count, descs_dev, grads_dev, gouts_dev, data_range, NULL, which, stream);
     return hipErrorInvalidValue;
 }
 

@@ -35,6 +35,16 @@ hands back is one float, not a plane).  It saves x and y only.
 A zero weight does not hide a NaN: 0 * NaN is NaN, and the gradient of the pixels around it is NaN too.  Replace invalid samples in x and
 y, not only in the weights.
 
+The window.  ssim, ssim_map and SSIMLoss take win_size (3, 5, 7, 9 or 11), win_sigma and window ("gaussian" or "uniform", a box that
+ignores win_sigma): pytorch-msssim's win_size / win_sigma, torchmetrics' and piq's kernel_size / sigma, TensorFlow's filter_size /
+filter_sigma, kornia's window_size, skimage's 7 x 7 box, the 3 x 3 box of monodepth-style losses.  The defaults (11, 1.5, "gaussian") take
+exactly the path above; anything else runs the _win entries of the float32 family (rmgr_ssim_hip_enqueue_ssimf_win, _ssimf_win_grad,
+_ssimf_win_map_grad), the small windows on kernels of their own radius.  Edges are clamped for every window: where monodepth-style code
+reflects, the interior is identical and the outermost (win_size - 1) / 2 pixels differ.  float16 / bfloat16 tensors and ms_ssim keep the
+fixed window for now: a non-default window with 16-bit tensors is a TypeError.
+
+    photo = 0.85 * (1 - ssim_map(warped, target, win_size=3, window="uniform")) / 2 + 0.15 * (warped - target).abs()
+
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
 import ctypes
@@ -100,6 +110,25 @@ def _check(x, y, data_range, half=False):
     return r
 
 
+def _window(x, y, win_size, win_sigma, window):
+    """The documented errors of the window arguments, before any GPU call.  Returns None for the defaults (today's path) or an api.Window."""
+    if not isinstance(window, str):
+        raise TypeError("ssim: window must be 'gaussian' or 'uniform', got %s" % type(window).__name__)
+    win = api.make_window(win_size, 1.5 if window == "uniform" else win_sigma, window)      # TypeError / ValueError
+    if win.size == 11 and win.kind == api.WINDOW_GAUSSIAN and win.sigma == 1.5:
+        return None
+    for t in (x, y):
+        if str(getattr(t, "dtype", "")) in ("torch.float16", "torch.bfloat16"):
+            raise TypeError("ssim: float16 / bfloat16 tensors keep the fixed window (win_size=11, win_sigma=1.5, window='gaussian'); "
+                            "a configurable window needs float32 tensors")
+    return win
+
+
+def _win_kw(win):
+    """The keyword that selects a _win entry; none at all for the default window: exactly the call made before windows existed."""
+    return {} if win is None else {"window": win}
+
+
 def _plane_offsets(t):
     """Element offset of every (H, W) plane of t from t.data_ptr(), in the order of t.reshape(-1, H, W)."""
     offs = [0]
@@ -137,7 +166,7 @@ def _make_function():
 
     class _SSIM(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, y, data_range):
+        def forward(ctx, x, y, data_range, win):
             lead, h, w = x.shape[:-2], x.shape[-2], x.shape[-1]
             params, n = _params(x, y)
             sums = torch.empty(n, dtype=torch.float64, device=x.device)
@@ -147,13 +176,13 @@ def _make_function():
                     work.wait_stream(cur)
                 st = _sample_type(torch, x.dtype)
                 if st is None:
-                    _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr())
+                    _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr(), **_win_kw(win))
                 else:
                     _context(x.device, work).enqueue_ssimh(params, n, data_range, st, sums.data_ptr())
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
-            ctx.data_range = data_range
+            ctx.data_range, ctx.win = data_range, win
             return (sums / (float(w) * float(h))).to(torch.float32).reshape(lead)
 
         @staticmethod
@@ -163,7 +192,7 @@ def _make_function():
             h, w = x.shape[-2], x.shape[-1]
             want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             if not (want_x or want_y):
-                return None, None, None
+                return None, None, None, None
             params, n = _params(x, y)
             g = grad_out.to(torch.float32).reshape(-1).contiguous()
             gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
@@ -176,28 +205,33 @@ def _make_function():
                 ga = _grad_planes(gx, n, h, w) if want_x else None
                 gb = _grad_planes(gy, n, h, w) if want_y else None
                 if st is None:
-                    _context(x.device, work).enqueue_ssimf_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb)
+                    _context(x.device, work).enqueue_ssimf_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb, **_win_kw(ctx.win))
                 else:
                     _context(x.device, work).enqueue_ssimh_grad(params, n, ctx.data_range, st, g.data_ptr(), ga, gb)
                 if work is not cur:
                     cur.wait_stream(work)
-            return gx, gy, None
+            return gx, gy, None, None
 
     return _SSIM
 
 
-def ssim(x, y, data_range=1.0):
+def ssim(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
     """Per-plane SSIM of two GPU tensors of identical shape (..., H, W), both float32, both float16 or both bfloat16, any strides (each
     plane is addressed in place, no copy): a float32 tensor of shape x.shape[:-2] at every input dtype.  Differentiable with respect to
     x, y or both; the gradient is computed only for the inputs that need it and has the inputs' dtype (float16 and bfloat16: the
     float32 value rounded once; see the top of this file for autocast and loss scaling).  TypeError: not tensors, mixed dtypes, any
     other dtype.  ValueError: CPU tensors, differing shapes or devices, fewer than 2 dimensions, empty planes, a data_range that is not
-    finite and > 0."""
+    finite and > 0.
+    The window: win_size taps per axis (3, 5, 7, 9 or 11), window "gaussian" with win_sigma or "uniform" (a box; win_sigma ignored); the
+    defaults are the engine's window and take exactly the path without these arguments.  TypeError: a win_size that is not an int, a
+    window that is not a str, a non-default window with float16 / bfloat16 tensors (they keep the fixed window).  ValueError: any other
+    win_size, an unknown window name, a win_sigma that is not finite and > 0."""
     global _function
+    win = _window(x, y, win_size, win_sigma, window)
     r = _check(x, y, data_range, half=True)
     if _function is None:
         _function = _make_function()
-    return _function.apply(x, y, r)
+    return _function.apply(x, y, r, win)
 
 
 def _with_maps(params, n, m, h, w):
@@ -222,7 +256,7 @@ def _make_map_function():
 
     class _SSIMMap(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, y, data_range):
+        def forward(ctx, x, y, data_range, win):
             h, w = x.shape[-2], x.shape[-1]
             params, n = _params(x, y)
             out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
@@ -235,13 +269,13 @@ def _make_map_function():
                     work.wait_stream(cur)
                 st = _sample_type(torch, x.dtype)
                 if st is None:
-                    _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr())
+                    _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr(), **_win_kw(win))
                 else:
                     _context(x.device, work).enqueue_ssimh(params, n, data_range, st, sums.data_ptr())
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
-            ctx.data_range = data_range
+            ctx.data_range, ctx.win = data_range, win
             return out
 
         @staticmethod
@@ -251,7 +285,7 @@ def _make_map_function():
             h, w = x.shape[-2], x.shape[-1]
             want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             if not (want_x or want_y):
-                return None, None, None
+                return None, None, None, None
             params, n = _params(x, y)
             g = grad_out if grad_out.dtype == torch.float32 else grad_out.to(torch.float32)      # read in place, through its own strides
             gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
@@ -265,41 +299,45 @@ def _make_map_function():
                 ga = _grad_planes(gx, n, h, w) if want_x else None
                 gb = _grad_planes(gy, n, h, w) if want_y else None
                 if st is None:
-                    _context(x.device, work).enqueue_ssimf_map_grad(params, n, ctx.data_range, maps, ga, gb)
+                    _context(x.device, work).enqueue_ssimf_map_grad(params, n, ctx.data_range, maps, ga, gb, **_win_kw(ctx.win))
                 else:
                     _context(x.device, work).enqueue_ssimh_map_grad(params, n, ctx.data_range, st, maps, ga, gb)
                 if work is not cur:
                     cur.wait_stream(work)
-            return gx, gy, None
+            return gx, gy, None, None
 
     return _SSIMMap
 
 
-def ssim_map(x, y, data_range=1.0):
+def ssim_map(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
     """Per-pixel SSIM of two GPU tensors of identical shape (..., H, W), both float32, both float16 or both bfloat16, any strides (each
     plane is addressed in place, no copy): a float32 tensor of shape x.shape at every input dtype, the map rmgr_ssim_hip_enqueue_ssimf /
     _ssimh write.  Differentiable with respect to x, y or both for ANY upstream gradient: the backward reads grad_out per pixel, in place
     (expanded and non-contiguous tensors included; another dtype is cast to float32 once), computes the gradient only for the inputs
     that need it and returns it in the inputs' dtype (float16 and bfloat16: the float32 value rounded once).  It keeps x and y, not the
-    map.  A zero in grad_out does not hide a NaN in the images.  Errors: as ssim()."""
+    map.  A zero in grad_out does not hide a NaN in the images.  win_size, win_sigma, window: as ssim().  Errors: as ssim()."""
     global _map_function
+    win = _window(x, y, win_size, win_sigma, window)
     r = _check(x, y, data_range, half=True)
     if _map_function is None:
         _map_function = _make_map_function()
-    return _map_function.apply(x, y, r)
+    return _map_function.apply(x, y, r, win)
 
 
 class SSIMLoss(object):
     """1 - ssim(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per plane), float32 whatever the inputs' dtype (float32,
-    float16 or bfloat16, as ssim()).  A plain callable: it has no parameters."""
+    float16 or bfloat16, as ssim()).  win_size, win_sigma, window: the window, as ssim(), checked here.  A plain callable: it has no
+    parameters."""
 
-    def __init__(self, data_range=1.0, reduction="mean"):
+    def __init__(self, data_range=1.0, reduction="mean", win_size=11, win_sigma=1.5, window="gaussian"):
         if reduction not in ("mean", "none"):
             raise ValueError("SSIMLoss: reduction must be 'mean' or 'none', got %r" % (reduction,))
+        _window(None, None, win_size, win_sigma, window)
         self.data_range, self.reduction = data_range, reduction
+        self.win_size, self.win_sigma, self.window = win_size, win_sigma, window
 
     def __call__(self, x, y):
-        loss = 1.0 - ssim(x, y, self.data_range)
+        loss = 1.0 - ssim(x, y, self.data_range, self.win_size, self.win_sigma, self.window)
         return loss.mean() if self.reduction == "mean" else loss
 
 
