@@ -35,6 +35,10 @@ inline uint64_t msf_partials(uint32_t W, uint32_t H, uint32_t count, uint32_t sc
     return t;
 }
 
+// Strip height launch_msssimf gives the strips of one scale of `count` pairs, `width` x `height` that scale's size: chosen as
+// ssimf_kernels.h's planf chooses it.  Results do not depend on the strip height.
+uint32_t strip_rows_of(uint32_t width, uint32_t height, uint32_t count, int cu_count);
+
 // Most pairs of this size one call to the launchers below may take (every grid stays below 2^32 work-items); 0 when one pair is
 // already too large.
 uint32_t msssimf_max_count(uint32_t width, uint32_t height);

@@ -759,25 +759,6 @@ void gaussian_taps(float (&gf)[6])
     for (int i = 0; i <= 5; ++i) gf[i] = (float)(g[i] / norm);
 }
 
-// Strip height of one scale's launch (whole cells, at most 2048 rows): the one that finishes the launch's strips in the fewest
-// row-times at three waves per SIMD, 10 warm-up rows included -- planf() of ssimf_kernels.hip.  Results do not depend on it.
-uint32_t strip_rows_of(uint32_t width, uint32_t height, uint32_t count, int cu_count)
-{
-    const uint32_t cell_rows = cell_rows_of(height);
-    const uint64_t slots = (uint64_t)(cu_count > 0 ? cu_count : 256) * 4 * 3;
-    const uint64_t cols = (uint64_t)((width + kSFStripW - 1) / kSFStripW) * count;
-    uint64_t best = ~uint64_t(0);
-    uint32_t best_rows = cell_rows;
-    for (uint32_t rows = cell_rows; rows <= std::max<uint32_t>(cell_rows, 2048); rows += cell_rows) {
-        const uint64_t per_col = (height + rows - 1) / rows;
-        const uint64_t rounds = (cols * per_col + slots - 1) / slots;
-        const uint64_t cost = rounds * (std::min<uint64_t>(rows, height) + 10);
-        if (cost <= best) { best = cost; best_rows = rows; }
-        if (rows >= height) break;
-    }
-    return best_rows;
-}
-
 bool valid_call(uint32_t count, uint32_t width, uint32_t height, uint32_t scales, float data_range, const double* weights)
 {
     if (!(data_range > 0.0f) || !std::isfinite(data_range) || scales < 1 || scales > kMSFMaxScales || weights == nullptr) return false;
@@ -812,6 +793,25 @@ hipError_t launch_pyramid(const PairFDesc* descs_dev, uint32_t count, uint32_t w
 }
 
 } // namespace
+
+// Strip height of one scale's launch (whole cells, at most 2048 rows): the one that finishes the launch's strips in the fewest
+// row-times at three waves per SIMD, 10 warm-up rows included -- planf() of ssimf_kernels.hip.  Results do not depend on it.
+uint32_t strip_rows_of(uint32_t width, uint32_t height, uint32_t count, int cu_count)
+{
+    const uint32_t cell_rows = cell_rows_of(height);
+    const uint64_t slots = (uint64_t)(cu_count > 0 ? cu_count : 256) * 4 * 3;
+    const uint64_t cols = (uint64_t)((width + kSFStripW - 1) / kSFStripW) * count;
+    uint64_t best = ~uint64_t(0);
+    uint32_t best_rows = cell_rows;
+    for (uint32_t rows = cell_rows; rows <= std::max<uint32_t>(cell_rows, 2048); rows += cell_rows) {
+        const uint64_t per_col = (height + rows - 1) / rows;
+        const uint64_t rounds = (cols * per_col + slots - 1) / slots;
+        const uint64_t cost = rounds * (std::min<uint64_t>(rows, height) + 10);
+        if (cost <= best) { best = cost; best_rows = rows; }
+        if (rows >= height) break;
+    }
+    return best_rows;
+}
 
 uint64_t msf_cells(uint32_t W, uint32_t H, uint32_t s)
 {

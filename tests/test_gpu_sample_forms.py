@@ -38,7 +38,9 @@ each on the host), and the host entry points stage 2 x 1 GiB while they run: the
 
 Shapes (W x H): 130 x 19 -- two 128-column strip columns, the second two pixels wide (x0 != 0, x_hi and refM clamped to W - 1, 63 lanes
 with col_ok false), strips with y0 != 0 at 8-row cells, a last cell of 3 rows (ROW_LAST) -- and 3 x 300: one strip column narrower
-than the halo, 38 cells, so the batch of eight cells is flushed more than once.
+than the halo, 38 strips of one 8-row cell each (a launch this small fits one round of wave slots, for which the planners choose
+single-cell strips: every flush here carries one parked cell).  Strips of several cells, full batches of eight and the short last cell
+of a tall strip are what tests/test_gpu_tall_strips.py runs.
 
 Bounds.  None is new: ssimf_model.PX_TOL / G_TOL / GRAD_TOL, test_gpu_ssim16.PX_TOL / G_TOL, msssimf_model.VALUE_TOL / MEAN_TOL /
 GRAD_TOL, ssimw_model.WGRAD_TOL; the half family is held to ssimf on the widened planes and to halfmodel's single rounding, bit for

@@ -8,7 +8,8 @@ float64 model over five golden pairs in two forms (tests/test_ssimk_cpu.py pins 
 
 Sizes are W x H.  1 x 1, 2 x 1, 1 x 2: the axis-of-one rule; 5 x 3, 4 x 4, 9 x 9: axes shorter than and equal to the window, both tails
 overlapping; 33 x 33: a second gradient tile of one pixel and more than four 8-row strips; 129 x 17: a second strip column of one pixel;
-7 x 300: many strips and tiles of a narrow column.
+7 x 300: many strips and tiles of a narrow column.  Every strip here holds one 8-row cell and no launch more than 3 pairs: strips of many
+cells (9 x 603 and 9 x 2115 in 1000 pairs, 260 x 601 in 350) and gradient launches of 300 pairs are in tests/test_gpu_tall_strips.py.
 """
 import ctypes
 import json
