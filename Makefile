@@ -21,8 +21,8 @@ lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr
 
 # The objects both flavours share: kernels, the C ABI's host layer apart from ssim_context (the only one that reads
 # RMGR_SSIM_USE_DOUBLE: $(OBJ)/ssim_context.o / ssim_context_double.o), the drop-in layer.
-ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
-HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/msssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
+HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/msssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
 
 # Static flavour under the reference's archive name (CMakeLists.txt:205): the same objects, linked into ONE relocatable
 # object whose only global symbols are the API (the shared libraries' export list has no counterpart for archives: the
@@ -85,6 +85,12 @@ $(OBJ)/msssimf_kernels.o: $(SRC)/msssimf_kernels.hip $(SRC)/msssimf_kernels.h $(
 # SSIM of float16 / bfloat16 samples and its gradient (rmgr_ssim_hip_*_ssimh*): its own file for the same reason, and the same flags as
 # ssimf_kernels.o -- its results are held to that object's, bit for bit.
 $(OBJ)/ssimh_kernels.o: $(SRC)/ssimh_kernels.hip $(SRC)/ssimh_kernels.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# Multi-scale SSIM of float16 / bfloat16 samples and its gradient (rmgr_ssim_hip_*_msssimh*): scale 0's kernels; its own file for the same
+# reason, and the rule and flags of msssimf_kernels.o -- its results are held to that object's, bit for bit.
+$(OBJ)/msssimh_kernels.o: $(SRC)/msssimh_kernels.hip $(SRC)/msssimh_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -28,6 +28,8 @@
  *                                      samples and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssimh, rmgr_ssim_hip_compute_ssimh_device / _host, rmgr_ssim_hip_enqueue_ssimh_grad   SSIM of float16 /
  *                                      bfloat16 samples and its gradient: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_msssimh, rmgr_ssim_hip_compute_msssimh_device / _host, rmgr_ssim_hip_enqueue_msssimh_grad   multi-scale SSIM
+ *       of float16 / bfloat16 images and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssimf_map_grad, rmgr_ssim_hip_enqueue_ssimh_map_grad   gradient of the SSIM MAP for a per-pixel upstream
  *                                      gradient: no reference counterpart (definition below)
  *
@@ -617,6 +619,54 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* ctx, rmgr_u
                                               const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
 
 /*
+ * Multi-scale SSIM of `count` pairs of float16 or bfloat16 images of one size, and its gradient (1 - MS-SSIM as a training loss under
+ * mixed precision, without a float32 copy of the images or of the gradient).  No reference counterpart: msssimh is msssimf applied to the
+ * samples widened to float32, so tests/msssimf_model.py restates it as well; tests/halfmodel.py restates the two encodings.  Additions
+ * only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ *   Samples  as rmgr_ssim_hip_enqueue_ssimh: 16-bit, ONE encoding per call (sampleType RMGR_SSIM_HIP_SAMPLE_F16 or _BF16), each widened
+ *            to float32 EXACTLY (float16 subnormals are kept; NaN and Inf stay NaN and Inf).  Only scale 0 holds 16-bit samples: the
+ *            pyramid is float32 from scale 1 on.
+ *   Inputs   params[0 .. count-1] (rmgr_ssim_hip_Params16): width, height (the same for every pair), imgA / imgB with any step / stride
+ *            in SAMPLES, negative and interleaved views included; params[i].ssimMap must be NULL.  Alignment: 2 bytes.
+ *   Data range, scales, weights, pyramid, per scale, value, arithmetic  as rmgr_ssim_hip_enqueue_msssimf, word for word, on the widened
+ *            planes.
+ *   Forward  the value and every per-scale mean {mcs_s, mssim_s} have the BITS rmgr_ssim_hip_enqueue_msssimf gives on the widened planes,
+ *            at every `scales` 1 .. 8 and with any weights.
+ *   Gradient  the float32 value rmgr_ssim_hip_enqueue_msssimf_grad would store at scale 0 for the widened planes -- fp32(local_0 +
+ *            fp32(0.25 c g_1)) when a coarser scale exists, local_0 when scales == 1 --, rounded ONCE, to nearest-even, into the inputs'
+ *            encoding.  float16 keeps subnormals and overflows to +-Inf; a NaN stays a (quiet) NaN.  gradOutDevice, the per-scale means,
+ *            the coefficients k_s and the gradient planes of scales >= 1 stay float32 / float64 as they are; a loss scale that arrives
+ *            in gOut is applied before the single rounding.
+ *   Determinism  every promise of msssimf: the same bits -- value, means, gradient -- alone or anywhere in a batch, after any sub-batch
+ *            split, through every entry point, on every call, with one gradient or both, and as a view with negative step or stride, or
+ *            interleaved samples, compared with the same pixels stored contiguously.  One writer per gradient pixel, no floating-point
+ *            atomics.
+ *
+ * _enqueue_msssimh, _compute_msssimh_device, _compute_msssimh_host: as the msssimf entries of the same names (valuesDevice,
+ *            scaleMeansDevice, msssim, scaleMeans as there); the _host form stages 2 bytes per pixel.
+ * _enqueue_msssimh_grad: as _enqueue_msssimf_grad; gradA / gradB: arrays of count rmgr_ssim_hip_GradH as for _enqueue_ssimh_grad (16-bit
+ *            device planes in the inputs' encoding, step / stride in samples; either may be NULL, not both; written, not accumulated).
+ * Scratch  msssimf's: the pyramids and the coarse gradient planes are the same float32 planes; the same sub-batches under about 1 GB.
+ * EINVAL: every EINVAL of the msssimf entries -- count == 0, a NULL pointer, a zero, differing or too large size, a bad dataRange, scales
+ *         or weights, a non-NULL ssimMap, a NULL ctx for anything but _host --, a sampleType that is neither of the two constants, an
+ *         image or gradient pointer that is not 2-byte aligned -- all checked before any device is touched.  ENODEV: no device.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                           rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                           double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssimh_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                  float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssimh_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                const double* scaleMeansDevice, const float* gradOutDevice,
+                                                const rmgr_ssim_hip_GradH* gradA, const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
+
+/*
  * Gradient of the SSIM map: dLoss/da and dLoss/db of `count` pairs for an upstream gradient given PER PIXEL (a weighted or masked mean,
  * a per-pixel combination with L1 and a minimum over views, sums over boxes -- any loss that is a function of the map
  * rmgr_ssim_hip_enqueue_ssimf / _ssimh write through params[i].ssimMap, not of its plain mean).  No reference counterpart:
@@ -693,8 +743,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* ctx, rm
  * Arguments, EINVAL / ENODEV rules, sub-batches, scratch and stream behaviour are those of the entry without _win.  Additional EINVAL,
  * checked before any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
  *
- * Follow-up, not in this interface: float16 / bfloat16 samples (the ssimh entries) and multi-scale SSIM (the msssim and msssimf entries)
- * keep the fixed window {11, GAUSSIAN, 1.5f}.
+ * Follow-up, not in this interface: float16 / bfloat16 samples (the ssimh entries) and multi-scale SSIM (the msssim, msssimf and msssimh
+ * entries) keep the fixed window {11, GAUSSIAN, 1.5f}.
  */
 enum { RMGR_SSIM_HIP_WINDOW_GAUSSIAN = 0, RMGR_SSIM_HIP_WINDOW_UNIFORM = 1 };
 typedef struct rmgr_ssim_hip_Window {

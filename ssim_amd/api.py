@@ -183,6 +183,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssimf_map_grad", "rmgr_ssim_hip_enqueue_ssimh_map_grad",
     "rmgr_ssim_hip_enqueue_ssimf_win", "rmgr_ssim_hip_compute_ssimf_win_device", "rmgr_ssim_hip_compute_ssimf_win_host",
     "rmgr_ssim_hip_enqueue_ssimf_win_grad", "rmgr_ssim_hip_enqueue_ssimf_win_map_grad",
+    "rmgr_ssim_hip_enqueue_msssimh", "rmgr_ssim_hip_compute_msssimh_device", "rmgr_ssim_hip_compute_msssimh_host", "rmgr_ssim_hip_enqueue_msssimh_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -279,6 +280,10 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_msssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_enqueue_msssimf_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
+        "rmgr_ssim_hip_enqueue_msssimh": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
+        "rmgr_ssim_hip_compute_msssimh_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssimh_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_msssimh_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
     }
     for name, args in sig.items():
         if path is None and os.environ.get("RMGR_SSIM_LIB") and not hasattr(lib, name):
@@ -733,6 +738,43 @@ def compute_msssimf_batch(pairs, data_range, scales=5, weights=None, per_scale=F
     return _msssimf_call("rmgr_ssim_hip_compute_msssimf_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale)
 
 
+def _msssimh_call(fn_name, handle, params, count, code, data_range, scales, weights, per_scale):
+    out = (ctypes.c_float * max(count, 1))()
+    means = (ctypes.c_double * max(count * scales * 2, 1))() if per_scale else None
+    _check(fn_name, getattr(load_library(), fn_name)(handle, count, params, code, data_range, scales, _weights_array(weights), out, means))
+    vals = np.array(out[:count], np.float32)
+    if not per_scale:
+        return vals
+    return vals, np.array(means[:count * scales * 2], np.float64).reshape(count, scales, 2)
+
+
+def compute_msssimh(a, b, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
+    """Multi-scale SSIM of two H x W host arrays of float16 or bfloat16 samples at `data_range` (any strides numpy can express, negative
+    ones included) through rmgr_ssim_hip_compute_msssimh_host.  Arrays and sample_type: as compute_ssimh (np.float16 arrays select
+    float16; np.uint16 arrays carry bit patterns and need sample_type), with its errors.  weights None: Wang's five (scales must be 5).
+    Returns a float32, and with per_scale=True also a (scales, 2) float64 array of [scale]{mcs, mssim}."""
+    a, b, code = _h_pair(a, b, sample_type)
+    params = (Params16 * 1)()
+    params[0] = _params16_of(a, b)
+    r = _msssimh_call("rmgr_ssim_hip_compute_msssimh_host", ctx.handle if ctx is not None else None, params, 1, code, data_range, scales, weights, per_scale)
+    return (r[0][0], r[1][0]) if per_scale else r[0]
+
+
+def compute_msssimh_batch(pairs, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
+    """compute_msssimh() of many host pairs of one size and one sample type in one call: a float32 array (and a (count, scales, 2) array
+    with per_scale)."""
+    pairs = [_h_pair(a, b, sample_type) for a, b in pairs]
+    n = len(pairs)
+    codes = set(t for _, _, t in pairs)
+    if len(codes) > 1:
+        raise TypeError("the pairs differ in sample type")
+    code = codes.pop() if codes else sample_type_code("float16" if sample_type is None else sample_type)
+    params = (Params16 * max(n, 1))()
+    for i, (a, b, _) in enumerate(pairs):
+        params[i] = _params16_of(a, b)
+    return _msssimh_call("rmgr_ssim_hip_compute_msssimh_host", ctx.handle if ctx is not None else None, params, n, code, data_range, scales, weights, per_scale)
+
+
 class DeviceBuffer(object):
     def __init__(self, ctx, nbytes):
         self.ctx, self.nbytes = ctx, nbytes
@@ -946,6 +988,27 @@ class Context(object):
         (device memory), into the planes the GradF arrays describe; asynchronous on the context's stream, no host synchronisation."""
         _check("rmgr_ssim_hip_enqueue_msssimf_grad", self.lib.rmgr_ssim_hip_enqueue_msssimf_grad(
             self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
+
+    def msssimh_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False):
+        """MS-SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_msssimh_device: a
+        float32 array, and with per_scale=True also a (count, scales, 2) float64 array of [pair][scale]{mcs, mssim}."""
+        return _msssimh_call("rmgr_ssim_hip_compute_msssimh_device", self.handle, params_array, count, sample_type_code(sample_type), data_range,
+                             scales, weights, per_scale)
+
+    def enqueue_msssimh(self, params_array, count, data_range, sample_type, values_dev_ptr, means_dev_ptr, scales=5, weights=None):
+        """rmgr_ssim_hip_enqueue_msssimh: per-pair fp64 values and count x scales x 2 fp64 means into device memory, asynchronously on the
+        context's stream."""
+        _check("rmgr_ssim_hip_enqueue_msssimh", self.lib.rmgr_ssim_hip_enqueue_msssimh(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+
+    def enqueue_msssimh_grad(self, params_array, count, data_range, sample_type, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5,
+                             weights=None):
+        """rmgr_ssim_hip_enqueue_msssimh_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs, from the forward's means (device
+        memory), into the 16-bit planes the GradH arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values;
+        asynchronous on the context's stream, no host synchronisation."""
+        _check("rmgr_ssim_hip_enqueue_msssimh_grad", self.lib.rmgr_ssim_hip_enqueue_msssimh_grad(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), means_dev_ptr,
+            grad_out_dev_ptr, grad_a, grad_b))
 
     def enqueue_batch(self, params_array, count, sums_dev_ptr):
         _check("rmgr_ssim_hip_enqueue_batch", self.lib.rmgr_ssim_hip_enqueue_batch(self.handle, count, params_array, sums_dev_ptr))

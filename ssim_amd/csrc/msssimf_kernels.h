@@ -68,6 +68,18 @@ hipError_t launch_msssimf_grad(const PairFDesc* descs_dev, const GradFDesc* grad
                                uint32_t scales, float data_range, const double* weights, const double* means, const float* g_out,
                                float* coef, int which, hipStream_t stream);
 
+// The two launchers above from scale `first` (0 or 1) on, for a caller whose scale 0 is not float32 (msssimh_kernels.hip) and who has
+// launched, on the same stream, the pyramid step from its scale 0 into row 1 of descs_dev and -- forward -- its own strip kernel over
+// scale 0's share of `partials`, which comes first and has msf_cells(width, height, 0) x 2 x count doubles.  first == 0 is the launcher
+// above.  first == 1 skips the pyramid step, the strip kernel and the gradient kernel of scale 0 and reads nothing of row 0 of descs_dev
+// and grads_dev; the reduction, the product and the coefficients cover every scale.  `wide` is scale 0's and ignored when first == 1.
+hipError_t launch_msssimf_from(uint32_t first, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales,
+                               bool wide, float data_range, const double* weights, int cu_count, int xcd_count, double* partials,
+                               double* means, double* values, hipStream_t stream);
+hipError_t launch_msssimf_grad_from(uint32_t first, const PairFDesc* descs_dev, const GradFDesc* grads_dev, uint32_t count, uint32_t width,
+                                    uint32_t height, uint32_t scales, float data_range, const double* weights, const double* means,
+                                    const float* g_out, float* coef, int which, hipStream_t stream);
+
 } // namespace ssim_hip
 
 #endif

@@ -1,31 +1,22 @@
-// msssimf_kernels.hip -- gfx950 kernels of multi-scale SSIM on float32 samples and of its gradient, behind
-// rmgr_ssim_hip_enqueue_msssimf, rmgr_ssim_hip_compute_msssimf_device / _host and rmgr_ssim_hip_enqueue_msssimf_grad.  The definition
-// they implement is in include/rmgr/ssim-hip.h; tests/msssimf_model.py restates it in float64 and restates the arithmetic below in fp32.
+// msssimh_kernels.hip -- gfx950 kernels of multi-scale SSIM on float16 / bfloat16 samples and of its gradient, behind
+// rmgr_ssim_hip_enqueue_msssimh, rmgr_ssim_hip_compute_msssimh_device / _host and rmgr_ssim_hip_enqueue_msssimh_grad.  The definition
+// they implement is in include/rmgr/ssim-hip.h: msssimf's, applied to the samples widened to float32, with the gradient rounded once into
+// the samples' encoding.
 //
-// Kept apart from ssimf_kernels.hip and msssim_kernels.hip on purpose: tests count and budget the kernels of those files, and the
-// uint8 multi-scale path's bits are pinned.  The strip and gradient choreographies are those of ssimf_kernels.hip, copied here, not
-// included.
+// Only scale 0 touches 16-bit memory -- the pyramid is float32 from scale 1 on -- so only scale 0 has kernels here: its strip kernel, its
+// pyramid step and its gradient kernel.  They are those of msssimf_kernels.hip, copied, not included (DESIGN.md sections 12 to 14 and 17),
+// with the loads and stores of ssimh_kernels.hip:
+//  * a sample gets into a register through a 2-byte load and the exact widen<TYPE>; byte offsets scale by 2.  From stage_from on (strip),
+//    from the four widened samples on (pyramid step) and from the `in` plane on (gradient) every instruction is msssimf's, built with the
+//    same flags (-ffp-contract=off): the cell sums, the scale-1 plane and the float32 gradient have the bits of msssimf on the widened
+//    planes;
+//  * a gradient pixel leaves through narrow<TYPE>: the float32 value, the coarser scale's gradient included, rounded once to nearest-even,
+//    one 2-byte store.
+// Scales >= 1, the reduction, the product and the coefficients run on msssimf_kernels.hip's kernels (launch_msssimf_from,
+// launch_msssimf_grad_from) over the same partials layout, pyramid and coarse gradient planes.
 //
-//  * msssimf_down_kernel: one step of the pyramid, a launch of its own: scale s + 1 = ((P(2x,2y) + P(2x+1,2y)) + (P(2x,2y+1) +
-//    P(2x+1,2y+1))) * 0.25f of scale s, coordinates clamped, every operation rounded to fp32 in that order; A and B of a pair in one
-//    work-item.  Scale 0 is read at the caller's steps and strides, every coarser scale is a dense plane of the context's scratch.
-//  * msssimf_strip_kernel: the strip flow of ssimf_strip_kernel (one 64-lane wavefront = one strip of 128 output columns, LDS ring for
-//    the row pass, register rings for the column pass, n * rcp(d)) without a map and with TWO fp64 sums per cell: cs = A2 / B2 and
-//    ssim = A1 A2 / (B1 B2).  One launch per scale over that scale's descriptors.
-//  * msssimf_reduce_kernel: every (pair, scale, kind) sum of cell partials in a fixed order, divided by double(W_s) * double(H_s).
-//  * msssimf_finalise_kernel: the ReLU'd weighted product of a pair's means, in double.
-//  * msssimf_coef_kernel: k_s = gOut w_s MS / m_s / (double(W_s) * double(H_s)) per pair and scale, all 0 when MS = 0.
-//  * msssimf_grad_kernel: the fused recomputing gradient kernel of ssimf_kernels.hip (32 x 32 tiles at absolute positions) in a cs form
-//    and an ssim form, whose epilogue adds the coarser scale's gradient through the adjoint of the clamped box filter.
-//
-// Centring, at every scale as in ssimf_kernels.hip ON THAT SCALE'S PLANES: the centre of the 128 columns from x0 = 128 k on is A's and
-// B's sample of scale s at (min(x0 + 64, W_s - 1), (H_s - 1) / 2) when its magnitude is at most dataRange, else 0.  The position is
-// fixed by the image and the pyramid is a fixed function of the image, so every strip height, tile, batch, split and entry point
-// sees the same centre.
-//
-// Per-pixel values and cells are formed exactly as in ssimf_kernels.hip (source-row order, fixed trees), so the sums are bit-identical
-// for any strip height, batch or split.
-#include "msssimf_kernels.h"
+// Centring, per-pixel values and cells: see the top of msssimf_kernels.hip; the rules are the same, on the widened samples.
+#include "msssimh_kernels.h"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -39,12 +30,34 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 typedef const uint8_t __attribute__((address_space(1)))*    gptr_u8;
 typedef const float __attribute__((address_space(1)))*      gptr_cf32;
+typedef const uint16_t __attribute__((address_space(1)))*   gptr_cu16;
+typedef uint16_t __attribute__((address_space(1)))*         gptr_u16;
 typedef float __attribute__((address_space(1)))*            gptr_f32;
 typedef double __attribute__((address_space(1)))*           gptr_f64;
-typedef const PairFDesc __attribute__((address_space(1)))* gptr_descf;
+typedef const PairHDesc __attribute__((address_space(1)))* gptr_desch;
 
 __device__ __forceinline__ f2 fma_(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ float opaque(float v) { asm("" : "+v"(v)); return v; }
+
+// A stored sample -> float32, exactly (ssimh_kernels.hip).
+template <int TYPE>
+__device__ __forceinline__ float widen(uint16_t s)
+{
+    if constexpr (TYPE == kSHTypeBF16) return __builtin_bit_cast(float, (uint32_t)s << 16);
+    else                               return (float)__builtin_bit_cast(_Float16, s);
+}
+// float32 -> the samples' encoding, one rounding to nearest-even (ssimh_kernels.hip).
+template <int TYPE>
+__device__ __forceinline__ uint16_t narrow(float v)
+{
+    if constexpr (TYPE == kSHTypeBF16) {
+        const uint32_t u = __builtin_bit_cast(uint32_t, v);
+        const uint32_t r = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;               // no carry out of a finite or infinite value
+        return (uint16_t)((u & 0x7FFFFFFFu) > 0x7F800000u ? (u >> 16) | 0x0040u : r);   // NaN: quiet, never rounded into Inf
+    } else {
+        return __builtin_bit_cast(uint16_t, (_Float16)v);
+    }
+}
 
 __device__ __forceinline__ int64_t uniform64(int64_t v)
 {
@@ -88,7 +101,7 @@ __device__ __forceinline__ void blur_pair(f2 (&accA)[11], f2 (&accB)[11], const 
     columns_pair<KMIN>(accA, accB, hA, hB, g);
 }
 
-// cs and SSIM of the lane's two columns from the centred moments (ssim_px2 of ssimf_kernels.hip, plus cs = A2 * rcp(B2)): m0, m1 =
+// cs and SSIM of the lane's two columns from the centred moments (msssim_px2 of msssimf_kernels.hip): m0, m1 =
 // (mu_a', mu_b') of each column, e0, e1 = (E[a'^2 + b'^2], E[a'b']); cen = (cA, cB).
 __device__ __forceinline__ f2 msssim_px2(f2 m0, f2 m1, f2 e0, f2 e1, f2 cen, float c1, float c2, f2& cs)
 {
@@ -111,9 +124,9 @@ __device__ __forceinline__ f2 msssim_px2(f2 m0, f2 m1, f2 e0, f2 e1, f2 cen, flo
     return n * r;
 }
 
-// One scale of one launch: that scale's descriptors, size and cell partials.
-struct KMArgs {
-    const PairFDesc* descs;
+// Scale 0 of one launch: the caller's descriptors, the size and the cell partials (KMArgs of msssimf_kernels.hip).
+struct KMHArgs {
+    const PairHDesc* descs;
     uint32_t width, height, strip_rows, strips_x, strips_y;
     uint32_t cells_x, cells_y, cell_shift;
     uint32_t count, xcds;
@@ -144,7 +157,7 @@ __device__ __forceinline__ uint32_t xcd_order(uint32_t g, uint32_t total, uint32
 enum { CELL_BATCH = 8 };
 struct CellBatch { double leaf[CELL_BATCH][64]; };
 
-#define MSF_DPP_ADD(t, CTRL) do {                                                                             \
+#define MSH_DPP_ADD(t, CTRL) do {                                                                             \
         const int lo_ = __builtin_amdgcn_update_dpp(0, __double2loint(t), (CTRL), 0xF, 0xF, false);           \
         const int hi_ = __builtin_amdgcn_update_dpp(0, __double2hiint(t), (CTRL), 0xF, 0xF, false);           \
         (t) += __hiloint2double(hi_, lo_);                                                                    \
@@ -170,13 +183,13 @@ __device__ __forceinline__ double cell_batch_local(const CellBatch& cb, int lane
 
 // A leaf is the lane's column pair; leaves 0-31 of a batch row are cell 2 sx, leaves 32-63 cell 2 sx + 1.  which: 0 the cs sum, 1 the
 // ssim sum of the cell (adjacent doubles).
-__device__ __forceinline__ void cell_batch_flush(const KMArgs& args, uint32_t img, uint32_t sx, const CellBatch& cb, uint32_t cell_y_first, uint32_t n, uint32_t which)
+__device__ __forceinline__ void cell_batch_flush(const KMHArgs& args, uint32_t img, uint32_t sx, const CellBatch& cb, uint32_t cell_y_first, uint32_t n, uint32_t which)
 {
     int lane = threadIdx.x;
     asm volatile("" : "+v"(lane));
     double t = cell_batch_local(cb, lane);
-    MSF_DPP_ADD(t, DPP_QUAD_XOR1);
-    MSF_DPP_ADD(t, DPP_QUAD_XOR2);
+    MSH_DPP_ADD(t, DPP_QUAD_XOR1);
+    MSH_DPP_ADD(t, DPP_QUAD_XOR2);
     const uint32_t c = (uint32_t)lane >> 3, cx = 2u * sx + (((uint32_t)lane >> 2) & 1u);
     if ((lane & 3) == 0 && c < n && cx < args.cells_x)
         ((gptr_f64)args.partials)[(((size_t)img * args.cells_y + cell_y_first + c) * args.cells_x + cx) * 2 + which] = t;
@@ -192,10 +205,11 @@ struct Slot {
 
 enum { ROW_WARMUP = 0, ROW_MAIN = 1, ROW_LAST = 2 };
 
-// WIDE: 64-bit lane offsets for the samples (scale-0 pairs that fail fitsf_narrow()).
-template <bool WIDE>
+// WIDE: 64-bit lane offsets for the samples (pairs that fail fitsh_narrow()).
+// TYPE: kSHTypeF16 or kSHTypeBF16, the encoding of the samples.
+template <int TYPE, bool WIDE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
-void msssimf_strip_kernel(const KMArgs args)
+void msssimh_strip_kernel(const KMHArgs args)
 {
     constexpr int PAD = Slot::PAD, ROW_PX = Slot::ROW_PX;
     constexpr int NLOAD = 3;                         // samples each lane stages per row and image
@@ -212,11 +226,11 @@ void msssimf_strip_kernel(const KMArgs args)
     const uint32_t id = xcd_order(blockIdx.x, per_img * args.count, args.xcds);
     const uint32_t img = id / per_img, lin = id - img * per_img;
     const uint32_t sy = lin / args.strips_x, sx = lin - sy * args.strips_x;
-    PairFDesc pd;
+    PairHDesc pd;
     {
-        const gptr_descf gd = (gptr_descf)args.descs + img;
-        pd.a = (const float*)uniform64((int64_t)gd->a); pd.a_step = uniform64(gd->a_step); pd.a_stride = uniform64(gd->a_stride);
-        pd.b = (const float*)uniform64((int64_t)gd->b); pd.b_step = uniform64(gd->b_step); pd.b_stride = uniform64(gd->b_stride);
+        const gptr_desch gd = (gptr_desch)args.descs + img;
+        pd.a = (const uint16_t*)uniform64((int64_t)gd->a); pd.a_step = uniform64(gd->a_step); pd.a_stride = uniform64(gd->a_stride);
+        pd.b = (const uint16_t*)uniform64((int64_t)gd->b); pd.b_step = uniform64(gd->b_step); pd.b_stride = uniform64(gd->b_stride);
     }
     const int W = (int)args.width, H = (int)args.height;
     const int x0 = (int)(sx * Slot::STRIP_W), y0 = (int)(sy * args.strip_rows);
@@ -226,8 +240,8 @@ void msssimf_strip_kernel(const KMArgs args)
     f2 cen;
     {
         const int64_t cx = x0 + 64 < W ? x0 + 64 : W - 1, cy = (H - 1) / 2;
-        const float sa = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, ((gptr_cf32)pd.a)[cx * pd.a_step + cy * pd.a_stride])));
-        const float sb = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, ((gptr_cf32)pd.b)[cx * pd.b_step + cy * pd.b_stride])));
+        const float sa = widen<TYPE>((uint16_t)__builtin_amdgcn_readfirstlane((uint32_t)((gptr_cu16)pd.a)[cx * pd.a_step + cy * pd.a_stride]));
+        const float sb = widen<TYPE>((uint16_t)__builtin_amdgcn_readfirstlane((uint32_t)((gptr_cu16)pd.b)[cx * pd.b_step + cy * pd.b_stride]));
         cen = f2{__builtin_fabsf(sa) <= args.range ? sa : 0.0f, __builtin_fabsf(sb) <= args.range ? sb : 0.0f};
     }
 
@@ -246,20 +260,20 @@ void msssimf_strip_kernel(const KMArgs args)
         p = p < ROW_PX ? p : ROW_PX - 1;
         const int xg = clampx(x0 - PAD + p);
         sp[t] = p;
-        offA[t] = (Off)((int64_t)(xg - refA) * pd.a_step * 4);
-        offB[t] = (Off)((int64_t)(xg - refB) * pd.b_step * 4);
+        offA[t] = (Off)((int64_t)(xg - refA) * pd.a_step * 2);
+        offB[t] = (Off)((int64_t)(xg - refB) * pd.b_step * 2);
     }
 
     float va[NLOAD], vb[NLOAD];
     auto fetch_to = [&](int r, float (&oa)[NLOAD], float (&ob)[NLOAD]) {     // row r (clamped) -> registers
         const int ry = r < 0 ? 0 : (r > H - 1 ? H - 1 : r);
-        const gptr_u8 ra = baseA + (int64_t)ry * pd.a_stride * 4;
-        const gptr_u8 rb = baseB + (int64_t)ry * pd.b_stride * 4;
+        const gptr_u8 ra = baseA + (int64_t)ry * pd.a_stride * 2;
+        const gptr_u8 rb = baseB + (int64_t)ry * pd.b_stride * 2;
 #pragma unroll
         for (int t = 0; t < NLOAD; ++t) {
             if constexpr (!WIDE) asm volatile("" : "+v"(offA[t]), "+v"(offB[t]));   // keeps the zero-extension foldable into the load
-            oa[t] = *(gptr_cf32)(ra + offA[t]);
-            ob[t] = *(gptr_cf32)(rb + offB[t]);
+            oa[t] = widen<TYPE>(*(gptr_cu16)(ra + offA[t]));
+            ob[t] = widen<TYPE>(*(gptr_cu16)(rb + offB[t]));
         }
     };
     auto fetch = [&](int r) { fetch_to(r, va, vb); };
@@ -407,135 +421,50 @@ void msssimf_strip_kernel(const KMArgs args)
         cell_batch_flush(args, img, sx, cells[1], cell_y, parked, 1);
     }
 }
+// ---- the pyramid step ----------------------------------------------------------------------------------------------------------------
 
-// ---- pyramid, reduction, product, coefficients ---------------------------------------------------------------------------------
-
-// One step of the pyramid: work-item = one pixel of scale s + 1 of one pair, A and B.  dst planes are dense (step 1, stride dst_w).
+// The pyramid step from scale 0 to scale 1 (msssimf_down_kernel with widened loads): work-item = one pixel of scale 1 of one pair, A
+// and B; four widened samples per image at the caller's steps and strides, (top + bot) * 0.25f in that order; dst planes are dense float32
+// (step 1, stride dst_w).
+template <int TYPE>
 __global__ __launch_bounds__(256)
-void msssimf_down_kernel(const PairFDesc* __restrict__ src, const PairFDesc* __restrict__ dst, uint32_t src_w, uint32_t src_h,
+void msssimh_down_kernel(const PairHDesc* __restrict__ src, const PairFDesc* __restrict__ dst, uint32_t src_w, uint32_t src_h,
                          uint32_t dst_w, uint32_t dst_h, uint32_t blocks_per_image)
 {
     const uint32_t img = blockIdx.x / blocks_per_image, blk = blockIdx.x - img * blocks_per_image;
     const uint64_t idx = (uint64_t)blk * 256 + threadIdx.x;
     if (idx >= (uint64_t)dst_w * dst_h) return;
     const uint32_t y = (uint32_t)(idx / dst_w), x = (uint32_t)(idx - (uint64_t)y * dst_w);
-    const PairFDesc s = src[img];
+    const PairHDesc s = src[img];
     const PairFDesc d = dst[img];
     const int64_t x0 = 2 * (int64_t)x, x1 = x0 + 1 < (int64_t)src_w ? x0 + 1 : (int64_t)src_w - 1;
     const int64_t y0 = 2 * (int64_t)y, y1 = y0 + 1 < (int64_t)src_h ? y0 + 1 : (int64_t)src_h - 1;
     {
-        const gptr_cf32 p = (gptr_cf32)s.a;
-        const float top = p[x0 * s.a_step + y0 * s.a_stride] + p[x1 * s.a_step + y0 * s.a_stride];
-        const float bot = p[x0 * s.a_step + y1 * s.a_stride] + p[x1 * s.a_step + y1 * s.a_stride];
+        const gptr_cu16 p = (gptr_cu16)s.a;
+        const float top = widen<TYPE>(p[x0 * s.a_step + y0 * s.a_stride]) + widen<TYPE>(p[x1 * s.a_step + y0 * s.a_stride]);
+        const float bot = widen<TYPE>(p[x0 * s.a_step + y1 * s.a_stride]) + widen<TYPE>(p[x1 * s.a_step + y1 * s.a_stride]);
         ((gptr_f32)const_cast<float*>(d.a))[idx] = (top + bot) * 0.25f;
     }
     {
-        const gptr_cf32 p = (gptr_cf32)s.b;
-        const float top = p[x0 * s.b_step + y0 * s.b_stride] + p[x1 * s.b_step + y0 * s.b_stride];
-        const float bot = p[x0 * s.b_step + y1 * s.b_stride] + p[x1 * s.b_step + y1 * s.b_stride];
+        const gptr_cu16 p = (gptr_cu16)s.b;
+        const float top = widen<TYPE>(p[x0 * s.b_step + y0 * s.b_stride]) + widen<TYPE>(p[x1 * s.b_step + y0 * s.b_stride]);
+        const float bot = widen<TYPE>(p[x0 * s.b_step + y1 * s.b_stride]) + widen<TYPE>(p[x1 * s.b_step + y1 * s.b_stride]);
         ((gptr_f32)const_cast<float*>(d.b))[idx] = (top + bot) * 0.25f;
     }
 }
-
-struct KRArgs {
-    const double* partials;
-    double*       means;                      // [pair][scale]{mcs, mssim}
-    uint32_t      count, scales;
-    uint64_t      offset[kMSFMaxScales];      // of a scale's partials, in doubles
-    uint64_t      cells[kMSFMaxScales];       // per image
-    double        pixels[kMSFMaxScales];      // double(W_s) * double(H_s)
-};
-
-// Workgroup (pair, scale, kind): thread t of 256 adds cells t, t + 256, ... in that order, each wave runs a fixed xor butterfly, and
-// the four wave totals are added in wave order.
-constexpr int kReduceThreads = 256;
-
-__global__ __launch_bounds__(kReduceThreads) void msssimf_reduce_kernel(const KRArgs args)
-{
-    __shared__ double sh[kReduceThreads / 64];
-    const uint32_t kind = blockIdx.x & 1u, rest = blockIdx.x >> 1;
-    const uint32_t s = rest % args.scales, img = rest / args.scales;
-    const uint64_t cells = args.cells[s];
-    const double* p = args.partials + args.offset[s] + (uint64_t)img * cells * 2 + kind;
-    double acc = 0.0;
-    for (uint64_t i = threadIdx.x; i < cells; i += kReduceThreads)
-        acc += p[2 * i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63u) == 0)
-        sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = sh[0];
-#pragma unroll
-        for (int w = 1; w < kReduceThreads / 64; ++w)
-            t += sh[w];
-        args.means[((size_t)img * args.scales + s) * 2 + kind] = t / args.pixels[s];
-    }
-}
-
-struct KWArgs {
-    uint32_t count, scales;
-    double   weights[kMSFMaxScales];
-    double   pixels[kMSFMaxScales];
-};
-
-// The mean scale s contributes: mcs_s, or mssim_s for the last scale.
-__device__ __forceinline__ double scale_mean(const double* means, uint32_t s, uint32_t scales) { return means[2 * s + (s + 1 == scales ? 1 : 0)]; }
-
-// prod max(m_s, 0)^w_s with x^0 = 1; a NaN mean stays a NaN.
-__device__ __forceinline__ double ms_product(const double* means, const KWArgs& a)
-{
-    double r = 1.0;
-    for (uint32_t s = 0; s < a.scales; ++s) {
-        if (a.weights[s] == 0.0) continue;
-        const double m = scale_mean(means, s, a.scales);
-        r *= pow(m <= 0.0 ? 0.0 : m, a.weights[s]);
-    }
-    return r;
-}
-
-__global__ __launch_bounds__(64) void msssimf_finalise_kernel(const KWArgs args, const double* __restrict__ means, double* __restrict__ values)
-{
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= args.count) return;
-    values[i] = ms_product(means + (size_t)i * args.scales * 2, args);
-}
-
-// k_s of every pair and scale, rounded to float once; all 0 when MS = 0 (the ReLU's subgradient) and where w_s = 0.
-__global__ __launch_bounds__(64) void msssimf_coef_kernel(const KWArgs args, const double* __restrict__ means, const float* __restrict__ g_out,
-                                                          float* __restrict__ coef)
-{
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= args.count) return;
-    const double* m = means + (size_t)i * args.scales * 2;
-    const double ms = ms_product(m, args);
-    const double g = (double)g_out[i];
-    for (uint32_t s = 0; s < args.scales; ++s) {
-        double k = 0.0;
-        if (ms != 0.0 && args.weights[s] != 0.0)
-            k = g * args.weights[s] * ms / scale_mean(m, s, args.scales) / args.pixels[s];
-        coef[(size_t)i * args.scales + s] = (float)k;
-    }
-}
-
-const uint64_t kMaxBlocks = (uint64_t(1) << 26) - 1;      // x 64 work-items stays below 2^32
-const uint64_t kMaxGradBlocks = (uint64_t(1) << 24) - 1;  // x 256 work-items stays below 2^32
-
 uint32_t cell_rows_of(uint32_t height) { return height >= 2048 ? 32u : 8u; }
 
 // ---- the gradient ------------------------------------------------------------------------------------------------------------
-// msssimf_grad_kernel: ssimf_grad_kernel (its steps 1 to 6 are described there and repeated in the comments below) with the
-// coefficient k_s read from device memory, a cs form for every scale but the coarsest, and the coarser scale's gradient added in
-// the epilogue.  One 256-lane workgroup = one 32 x 32 tile of gradient pixels of one scale at an absolute position; every gradient
-// pixel is written by one work-item in a fixed order: no atomics, the same bits in any batch.
+// msssimh_grad_kernel: msssimf_grad_kernel at scale 0 (its steps are repeated in the comments below).  The samples come in through
+// widen<TYPE> (step 1, the centre, the re-read of step 6); the float32 result, the coarser scale's gradient included, leaves through
+// narrow<TYPE> as one 2-byte store.  One 256-lane workgroup = one 32 x 32 tile of gradient pixels at an absolute position; every
+// gradient pixel is written by one work-item in a fixed order: no atomics, the same bits in any batch.
 enum { GT = kSFTile, GIN = GT + 20, GST = GT + 10 };
 
-struct KGArgs {
-    const PairFDesc* descs;       // this scale's planes
-    const GradFDesc* grads;       // this scale's gradient planes
-    const GradFDesc* up;          // the next coarser scale's gradient planes (dense); unused by the LAST form
+struct KGHArgs {
+    const PairHDesc* descs;       // scale 0: the caller's planes
+    const GradHDesc* grads;       // scale 0: the caller's gradient planes, in the samples' encoding
+    const GradFDesc* up;          // scale 1's gradient planes (dense float32); unused by the LAST form
     const float*     coef;        // k_s of pair i at coef[i * coef_stride]
     uint32_t coef_stride;
     uint32_t width, height, tiles_x, tiles_y;
@@ -556,11 +485,12 @@ __device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float
 
 // WHICH: 1 dLoss/dA, 2 dLoss/dB, 3 both.  The statistics are computed in the same (a, b) order in all three, so a gradient has
 // the same bits alone and together with the other.
-// LAST: the coarsest scale (the ssim form, no coarser gradient to add); otherwise the cs form, whose epilogue adds the adjoint of
+// TYPE: kSHTypeF16 or kSHTypeBF16, the encoding of the samples and of the gradient.
+// LAST: scales == 1, scale 0 is the coarsest (the ssim form, no coarser gradient to add); otherwise the cs form, whose epilogue adds the adjoint of
 // the clamped 2 x 2 box filter applied to the next coarser scale's gradient: 0.25 c g_{s+1}(x >> 1, y >> 1).
-template <int WHICH, bool LAST>
+template <int TYPE, int WHICH, bool LAST>
 __global__ __launch_bounds__(256)
-void msssimf_grad_kernel(const KGArgs args)
+void msssimh_grad_kernel(const KGHArgs args)
 {
     constexpr int NP = WHICH == 3 ? 4 : 3;                       // partial planes: d_mu (of A, or of the one wanted), d_aa, d_ab, d_mu of B
     constexpr int XN = 2 * GIN * GIN > NP * GST * GST ? 2 * GIN * GIN : NP * GST * GST;
@@ -578,9 +508,9 @@ void msssimf_grad_kernel(const KGArgs args)
     const uint32_t img = blockIdx.x / per_img, lin = blockIdx.x - img * per_img;
     const uint32_t ty = lin / args.tiles_x, tx = lin - ty * args.tiles_x;
     const int x0 = (int)(tx * GT), y0 = (int)(ty * GT);
-    const PairFDesc pd = args.descs[img];
-    const GradFDesc gd = args.grads[img];
-    const gptr_cf32 pa = (gptr_cf32)pd.a, pb = (gptr_cf32)pd.b;
+    const PairHDesc pd = args.descs[img];
+    const GradHDesc gd = args.grads[img];
+    const gptr_cu16 pa = (gptr_cu16)pd.a, pb = (gptr_cu16)pd.b;
     const float gf[6] = {args.gf[0], args.gf[1], args.gf[2], args.gf[3], args.gf[4], args.gf[5]};
     const float tail[6] = {args.tail[0], args.tail[1], args.tail[2], args.tail[3], args.tail[4], args.tail[5]};
     const float k = ((gptr_cf32)args.coef)[(size_t)img * args.coef_stride];
@@ -602,9 +532,9 @@ void msssimf_grad_kernel(const KGArgs args)
             const int qx = x0 + x, qy = y0 + y;
             if (qx >= W || qy >= H) continue;
             if constexpr (WHICH != 2)
-                ((gptr_f32)gd.ga)[(int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride] = 0.0f + upstream(ud.ga, ud.ga_step, ud.ga_stride, qx, qy);
+                ((gptr_u16)gd.ga)[(int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride] = narrow<TYPE>(0.0f + upstream(ud.ga, ud.ga_step, ud.ga_stride, qx, qy));
             if constexpr (WHICH != 1)
-                ((gptr_f32)gd.gb)[(int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride] = 0.0f + upstream(ud.gb, ud.gb_step, ud.gb_stride, qx, qy);
+                ((gptr_u16)gd.gb)[(int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride] = narrow<TYPE>(0.0f + upstream(ud.gb, ud.gb_step, ud.gb_stride, qx, qy));
         }
         return;
     }
@@ -613,7 +543,7 @@ void msssimf_grad_kernel(const KGArgs args)
     {
         const int xs = x0 & ~(kSFStripW - 1);
         const int64_t cx = xs + 64 < W ? xs + 64 : W - 1, cy = (H - 1) / 2;
-        const float sa = pa[cx * pd.a_step + cy * pd.a_stride], sb = pb[cx * pd.b_step + cy * pd.b_stride];
+        const float sa = widen<TYPE>(pa[cx * pd.a_step + cy * pd.a_stride]), sb = widen<TYPE>(pb[cx * pd.b_step + cy * pd.b_stride]);
         cen = f2{__builtin_fabsf(sa) <= args.range ? sa : 0.0f, __builtin_fabsf(sb) <= args.range ? sb : 0.0f};
     }
 
@@ -623,7 +553,7 @@ void msssimf_grad_kernel(const KGArgs args)
         int x = x0 - 10 + i, y = y0 - 10 + j;
         x = x < 0 ? 0 : (x > W - 1 ? W - 1 : x);
         y = y < 0 ? 0 : (y > H - 1 ? H - 1 : y);
-        const f2 v = {pa[(int64_t)x * pd.a_step + (int64_t)y * pd.a_stride], pb[(int64_t)x * pd.b_step + (int64_t)y * pd.b_stride]};
+        const f2 v = {widen<TYPE>(pa[(int64_t)x * pd.a_step + (int64_t)y * pd.a_stride]), widen<TYPE>(pb[(int64_t)x * pd.b_step + (int64_t)y * pd.b_stride])};
         in[idx] = v - cen;
     }
     __syncthreads();
@@ -735,19 +665,18 @@ void msssimf_grad_kernel(const KGArgs args)
             for (int t = 1; t < 11; ++t) acc = __builtin_fmaf(src[t * GT], wy[t], acc);
             r[pl] = acc;
         }
-        const float a = pa[(int64_t)qx * pd.a_step + (int64_t)qy * pd.a_stride] - cen.x;
-        const float b = pb[(int64_t)qx * pd.b_step + (int64_t)qy * pd.b_stride] - cen.y;
+        const float a = widen<TYPE>(pa[(int64_t)qx * pd.a_step + (int64_t)qy * pd.a_stride]) - cen.x;
+        const float b = widen<TYPE>(pb[(int64_t)qx * pd.b_step + (int64_t)qy * pd.b_stride]) - cen.y;
         if constexpr (WHICH != 2) {
             const float g = opaque(r[0] + opaque(opaque(2.0f * a) * r[1])) + opaque(b * r[2]);
-            ((gptr_f32)gd.ga)[(int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride] = LAST ? g : opaque(g) + upstream(ud.ga, ud.ga_step, ud.ga_stride, qx, qy);
+            ((gptr_u16)gd.ga)[(int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride] = narrow<TYPE>(LAST ? g : opaque(g) + upstream(ud.ga, ud.ga_step, ud.ga_stride, qx, qy));
         }
         if constexpr (WHICH != 1) {
             const float g = opaque(r[WHICH == 3 ? 3 : 0] + opaque(opaque(2.0f * b) * r[1])) + opaque(a * r[2]);
-            ((gptr_f32)gd.gb)[(int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride] = LAST ? g : opaque(g) + upstream(ud.gb, ud.gb_step, ud.gb_stride, qx, qy);
+            ((gptr_u16)gd.gb)[(int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride] = narrow<TYPE>(LAST ? g : opaque(g) + upstream(ud.gb, ud.gb_step, ud.gb_stride, qx, qy));
         }
     }
 }
-
 // the true 1-D Gaussian, sigma 1.5, normalised over the 11 taps, rounded to float: the engine's taps, centre first
 void gaussian_taps(float (&gf)[6])
 {
@@ -759,146 +688,97 @@ void gaussian_taps(float (&gf)[6])
     for (int i = 0; i <= 5; ++i) gf[i] = (float)(g[i] / norm);
 }
 
-bool valid_call(uint32_t count, uint32_t width, uint32_t height, uint32_t scales, float data_range, const double* weights)
+bool valid_type(int type) { return type == kSHTypeF16 || type == kSHTypeBF16; }
+
+// The pyramid step from the caller's planes into row 1 of descs_dev.
+template <int TYPE>
+void launch_down(const PairHDesc* descs0_dev, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, hipStream_t stream)
 {
-    if (!(data_range > 0.0f) || !std::isfinite(data_range) || scales < 1 || scales > kMSFMaxScales || weights == nullptr) return false;
-    for (uint32_t s = 0; s < scales; ++s)
-        if (!std::isfinite(weights[s]) || weights[s] < 0.0) return false;
-    return count <= msssimf_max_count(width, height);
+    const uint32_t dw = msf_dim(width, 1), dh = msf_dim(height, 1);
+    const uint32_t per = (uint32_t)(((uint64_t)dw * dh + 255) / 256);
+    hipLaunchKernelGGL((msssimh_down_kernel<TYPE>), dim3(per * count), dim3(256), 0, stream, descs0_dev, descs_dev + (size_t)count, width, height, dw, dh, per);
 }
 
-KWArgs weight_args(uint32_t count, uint32_t width, uint32_t height, uint32_t scales, const double* weights)
+template <int TYPE>
+void launch_strip(const KMHArgs& ka, dim3 grid, dim3 block, bool wide, hipStream_t stream)
 {
-    KWArgs a;
-    a.count = count; a.scales = scales;
-    for (uint32_t s = 0; s < kMSFMaxScales; ++s) {
-        a.weights[s] = s < scales ? weights[s] : 0.0;
-        a.pixels[s] = (double)msf_dim(width, s) * (double)msf_dim(height, s);
-    }
-    return a;
+    if (wide) hipLaunchKernelGGL((msssimh_strip_kernel<TYPE, true>), grid, block, 0, stream, ka);
+    else      hipLaunchKernelGGL((msssimh_strip_kernel<TYPE, false>), grid, block, 0, stream, ka);
 }
 
-// The pyramid of `count` pairs from scale `first` on: one launch per step, finest first.
-hipError_t launch_pyramid(uint32_t first, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales, hipStream_t stream)
+template <int TYPE>
+void launch_grad(const KGHArgs& ka, dim3 grid, dim3 block, int which, bool last, hipStream_t stream)
 {
-    for (uint32_t s = first; s + 1 < scales; ++s) {
-        const uint32_t sw = msf_dim(width, s), sh = msf_dim(height, s), dw = msf_dim(width, s + 1), dh = msf_dim(height, s + 1);
-        const uint32_t per = (uint32_t)(((uint64_t)dw * dh + 255) / 256);
-        hipLaunchKernelGGL(msssimf_down_kernel, dim3(per * count), dim3(256), 0, stream, descs_dev + (size_t)s * count,
-                           descs_dev + (size_t)(s + 1) * count, sw, sh, dw, dh, per);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
+    if (last) {
+        if (which == 1)      hipLaunchKernelGGL((msssimh_grad_kernel<TYPE, 1, true>), grid, block, 0, stream, ka);
+        else if (which == 2) hipLaunchKernelGGL((msssimh_grad_kernel<TYPE, 2, true>), grid, block, 0, stream, ka);
+        else                 hipLaunchKernelGGL((msssimh_grad_kernel<TYPE, 3, true>), grid, block, 0, stream, ka);
+    } else {
+        if (which == 1)      hipLaunchKernelGGL((msssimh_grad_kernel<TYPE, 1, false>), grid, block, 0, stream, ka);
+        else if (which == 2) hipLaunchKernelGGL((msssimh_grad_kernel<TYPE, 2, false>), grid, block, 0, stream, ka);
+        else                 hipLaunchKernelGGL((msssimh_grad_kernel<TYPE, 3, false>), grid, block, 0, stream, ka);
     }
-    return hipSuccess;
 }
 
 } // namespace
 
-// Strip height of one scale's launch (whole cells, at most 2048 rows): the one that finishes the launch's strips in the fewest
-// row-times at three waves per SIMD, 10 warm-up rows included -- planf() of ssimf_kernels.hip.  Results do not depend on it.
-uint32_t strip_rows_of(uint32_t width, uint32_t height, uint32_t count, int cu_count)
-{
-    const uint32_t cell_rows = cell_rows_of(height);
-    const uint64_t slots = (uint64_t)(cu_count > 0 ? cu_count : 256) * 4 * 3;
-    const uint64_t cols = (uint64_t)((width + kSFStripW - 1) / kSFStripW) * count;
-    uint64_t best = ~uint64_t(0);
-    uint32_t best_rows = cell_rows;
-    for (uint32_t rows = cell_rows; rows <= std::max<uint32_t>(cell_rows, 2048); rows += cell_rows) {
-        const uint64_t per_col = (height + rows - 1) / rows;
-        const uint64_t rounds = (cols * per_col + slots - 1) / slots;
-        const uint64_t cost = rounds * (std::min<uint64_t>(rows, height) + 10);
-        if (cost <= best) { best = cost; best_rows = rows; }
-        if (rows >= height) break;
-    }
-    return best_rows;
-}
-
-uint64_t msf_cells(uint32_t W, uint32_t H, uint32_t s)
-{
-    const uint32_t w = msf_dim(W, s), h = msf_dim(H, s), cr = cell_rows_of(h);
-    return (uint64_t)((w + 63) / 64) * ((h + cr - 1) / cr);
-}
-
-uint32_t msssimf_max_count(uint32_t width, uint32_t height)
-{
-    if (width == 0 || height == 0 || width > kSFMaxDim || height > kSFMaxDim) return 0;
-    // scale 0 has the largest grids: strips of the smallest height, gradient tiles; a pyramid step has a quarter of the tiles' lanes
-    const uint64_t cr = cell_rows_of(height);
-    const uint64_t per = (uint64_t)((width + kSFStripW - 1) / kSFStripW) * ((height + cr - 1) / cr);
-    const uint64_t tiles = (uint64_t)((width + kSFTile - 1) / kSFTile) * ((height + kSFTile - 1) / kSFTile);
-    return (uint32_t)std::min<uint64_t>(std::min(kMaxBlocks / per, kMaxGradBlocks / tiles), 65535);
-}
-
-hipError_t launch_msssimf(const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales, bool wide,
-                          float data_range, const double* weights, int cu_count, int xcd_count, double* partials, double* means,
-                          double* values, hipStream_t stream)
-{
-    return launch_msssimf_from(0, descs_dev, count, width, height, scales, wide, data_range, weights, cu_count, xcd_count, partials, means, values, stream);
-}
-
-hipError_t launch_msssimf_from(uint32_t first, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales,
-                               bool wide, float data_range, const double* weights, int cu_count, int xcd_count, double* partials,
-                               double* means, double* values, hipStream_t stream)
+hipError_t launch_msssimh(const PairHDesc* descs0_dev, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height,
+                          uint32_t scales, int type, bool wide, float data_range, const double* weights, int cu_count, int xcd_count,
+                          double* partials, double* means, double* values, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_call(count, width, height, scales, data_range, weights) || first > 1) return hipErrorInvalidValue;
-    hipError_t e = launch_pyramid(first, descs_dev, count, width, height, scales, stream);
-    if (e != hipSuccess) return e;
-    KRArgs kr;
-    kr.partials = partials; kr.means = means; kr.count = count; kr.scales = scales;
-    uint64_t offset = 0;
-    for (uint32_t s = 0; s < kMSFMaxScales; ++s) { kr.offset[s] = 0; kr.cells[s] = 0; kr.pixels[s] = 1.0; }
-    for (uint32_t s = 0; s < scales; ++s) {
-        const uint32_t w = msf_dim(width, s), h = msf_dim(height, s);
-        KMArgs ka;
-        ka.descs = descs_dev + (size_t)s * count;
-        ka.width = w; ka.height = h;
-        ka.strip_rows = strip_rows_of(w, h, count, cu_count);
-        ka.strips_x = (w + kSFStripW - 1) / kSFStripW;
-        ka.strips_y = (h + ka.strip_rows - 1) / ka.strip_rows;
-        const uint32_t cr = cell_rows_of(h);
-        ka.cells_x = (w + 63) / 64; ka.cells_y = (h + cr - 1) / cr;
-        ka.cell_shift = cr == 32 ? 5 : 3;
-        ka.count = count;
-        ka.xcds = xcd_count >= 1 ? (uint32_t)xcd_count : 8u;
-        ka.partials = partials + offset;
-        ka.range = data_range;
-        ssimf_constants(data_range, ka.c1, ka.c2);
-        gaussian_taps(ka.gf);
-        kr.offset[s] = offset; kr.cells[s] = (uint64_t)ka.cells_x * ka.cells_y; kr.pixels[s] = (double)w * (double)h;
-        offset += kr.cells[s] * 2 * count;
-        if (s < first) continue;                  // the caller's own strip kernel fills this scale's partials
-        const dim3 grid((uint32_t)((uint64_t)ka.strips_x * ka.strips_y * count)), block(64);
-        if (wide && s == 0) hipLaunchKernelGGL((msssimf_strip_kernel<true>), grid, block, 0, stream, ka);
-        else                hipLaunchKernelGGL((msssimf_strip_kernel<false>), grid, block, 0, stream, ka);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+    if (!valid_type(type) || !(data_range > 0.0f) || !std::isfinite(data_range) || scales < 1 || scales > kMSFMaxScales ||
+        count > msssimf_max_count(width, height))
+        return hipErrorInvalidValue;
+    hipError_t e;
+    if (scales > 1) {
+        if (type == kSHTypeBF16) launch_down<kSHTypeBF16>(descs0_dev, descs_dev, count, width, height, stream);
+        else                     launch_down<kSHTypeF16>(descs0_dev, descs_dev, count, width, height, stream);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(msssimf_reduce_kernel, dim3(count * scales * 2), dim3(kReduceThreads), 0, stream, kr);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(msssimf_finalise_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, scales, weights), means, values);
-    return hipGetLastError();
+    // scale 0's strips and cells, as launch_msssimf_from lays them out: its partials come first
+    KMHArgs ka;
+    ka.descs = descs0_dev;
+    ka.width = width; ka.height = height;
+    ka.strip_rows = strip_rows_of(width, height, count, cu_count);
+    ka.strips_x = (width + kSFStripW - 1) / kSFStripW;
+    ka.strips_y = (height + ka.strip_rows - 1) / ka.strip_rows;
+    const uint32_t cr = cell_rows_of(height);
+    ka.cells_x = (width + 63) / 64; ka.cells_y = (height + cr - 1) / cr;
+    ka.cell_shift = cr == 32 ? 5 : 3;
+    ka.count = count;
+    ka.xcds = xcd_count >= 1 ? (uint32_t)xcd_count : 8u;
+    ka.partials = partials;
+    ka.range = data_range;
+    ssimf_constants(data_range, ka.c1, ka.c2);
+    gaussian_taps(ka.gf);
+    const dim3 grid((uint32_t)((uint64_t)ka.strips_x * ka.strips_y * count)), block(64);
+    if (type == kSHTypeBF16) launch_strip<kSHTypeBF16>(ka, grid, block, wide, stream);
+    else                     launch_strip<kSHTypeF16>(ka, grid, block, wide, stream);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return launch_msssimf_from(1, descs_dev, count, width, height, scales, false, data_range, weights, cu_count, xcd_count, partials, means,
+                               values, stream);
 }
 
-hipError_t launch_msssimf_grad(const PairFDesc* descs_dev, const GradFDesc* grads_dev, uint32_t count, uint32_t width, uint32_t height,
-                               uint32_t scales, float data_range, const double* weights, const double* means, const float* g_out,
-                               float* coef, int which, hipStream_t stream)
-{
-    return launch_msssimf_grad_from(0, descs_dev, grads_dev, count, width, height, scales, data_range, weights, means, g_out, coef, which, stream);
-}
-
-hipError_t launch_msssimf_grad_from(uint32_t first, const PairFDesc* descs_dev, const GradFDesc* grads_dev, uint32_t count, uint32_t width,
-                                    uint32_t height, uint32_t scales, float data_range, const double* weights, const double* means,
-                                    const float* g_out, float* coef, int which, hipStream_t stream)
+hipError_t launch_msssimh_grad(const PairHDesc* descs0_dev, const PairFDesc* descs_dev, const GradHDesc* grads0_dev, const GradFDesc* grads_dev,
+                               uint32_t count, uint32_t width, uint32_t height, uint32_t scales, int type, float data_range,
+                               const double* weights, const double* means, const float* g_out, float* coef, int which, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_call(count, width, height, scales, data_range, weights) || which < 1 || which > 3 || first > 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(msssimf_coef_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, scales, weights), means, g_out, coef);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = launch_pyramid(first, descs_dev, count, width, height, scales, stream)) != hipSuccess) return e;
-    KGArgs ka;
+    if (!valid_type(type) || !(data_range > 0.0f) || !std::isfinite(data_range) || scales < 1 || scales > kMSFMaxScales || which < 1 ||
+        which > 3 || count > msssimf_max_count(width, height))
+        return hipErrorInvalidValue;
+    hipError_t e;
+    if (scales > 1) {
+        if (type == kSHTypeBF16) launch_down<kSHTypeBF16>(descs0_dev, descs_dev, count, width, height, stream);
+        else                     launch_down<kSHTypeF16>(descs0_dev, descs_dev, count, width, height, stream);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    // the coefficients of every scale, the rest of the pyramid, the float32 gradients from the coarsest scale down to scale 1
+    if ((e = launch_msssimf_grad_from(1, descs_dev, grads_dev, count, width, height, scales, data_range, weights, means, g_out, coef, which,
+                                      stream)) != hipSuccess)
+        return e;
+    KGHArgs ka;
     ka.range = data_range;
     ssimf_constants(data_range, ka.c1, ka.c2);
     gaussian_taps(ka.gf);
@@ -907,27 +787,17 @@ hipError_t launch_msssimf_grad_from(uint32_t first, const PairFDesc* descs_dev, 
     for (int i = 5; i >= 0; --i) { t += (double)ka.gf[i]; ka.tail[i] = (float)t; }
     ka.total = (float)(2.0 * t - (double)ka.gf[0]);
     ka.coef_stride = scales;
-    for (uint32_t s = scales; s-- > first;) {
-        const bool last = s + 1 == scales;
-        ka.descs = descs_dev + (size_t)s * count;
-        ka.grads = grads_dev + (size_t)s * count;
-        ka.up = last ? nullptr : grads_dev + (size_t)(s + 1) * count;
-        ka.coef = coef + s;
-        ka.width = msf_dim(width, s); ka.height = msf_dim(height, s);
-        ka.tiles_x = (ka.width + kSFTile - 1) / kSFTile; ka.tiles_y = (ka.height + kSFTile - 1) / kSFTile;
-        const dim3 grid((uint32_t)((uint64_t)ka.tiles_x * ka.tiles_y * count)), block(256);
-        if (last) {
-            if (which == 1)      hipLaunchKernelGGL((msssimf_grad_kernel<1, true>), grid, block, 0, stream, ka);
-            else if (which == 2) hipLaunchKernelGGL((msssimf_grad_kernel<2, true>), grid, block, 0, stream, ka);
-            else                 hipLaunchKernelGGL((msssimf_grad_kernel<3, true>), grid, block, 0, stream, ka);
-        } else {
-            if (which == 1)      hipLaunchKernelGGL((msssimf_grad_kernel<1, false>), grid, block, 0, stream, ka);
-            else if (which == 2) hipLaunchKernelGGL((msssimf_grad_kernel<2, false>), grid, block, 0, stream, ka);
-            else                 hipLaunchKernelGGL((msssimf_grad_kernel<3, false>), grid, block, 0, stream, ka);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    const bool last = scales == 1;
+    ka.descs = descs0_dev;
+    ka.grads = grads0_dev;
+    ka.up = last ? nullptr : grads_dev + (size_t)count;
+    ka.coef = coef;
+    ka.width = width; ka.height = height;
+    ka.tiles_x = (width + kSFTile - 1) / kSFTile; ka.tiles_y = (height + kSFTile - 1) / kSFTile;
+    const dim3 grid((uint32_t)((uint64_t)ka.tiles_x * ka.tiles_y * count)), block(256);
+    if (type == kSHTypeBF16) launch_grad<kSHTypeBF16>(ka, grid, block, which, last, stream);
+    else                     launch_grad<kSHTypeF16>(ka, grid, block, which, last, stream);
+    return hipGetLastError();
 }
 
 } // namespace ssim_hip

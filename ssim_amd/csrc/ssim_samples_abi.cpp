@@ -1,7 +1,8 @@
 // ssim_samples_abi.cpp -- the entry points of the C ABI for samples other than 8-bit ones (the 8-bit path: ssim_hip_abi.cpp): SSIM of
 // 9- to 16-bit integers (ssim16), of float32 (ssimf) and of float16 / bfloat16 samples (ssimh), the gradients of the latter two for a
-// scalar and for a per-pixel upstream gradient (ssimw), and multi-scale SSIM of float32 samples with its gradient (msssimf).  The
-// definitions are in include/rmgr/ssim-hip.h, the kernels in ssim16_ / ssimf_ / ssimh_ / ssimw_ / ssimk_ / msssimf_kernels.hip.
+// scalar and for a per-pixel upstream gradient (ssimw), and multi-scale SSIM of float32 (msssimf) and of float16 / bfloat16 samples
+// (msssimh) with its gradient.  The definitions are in include/rmgr/ssim-hip.h, the kernels in ssim16_ / ssimf_ / ssimh_ / ssimw_ /
+// ssimk_ / msssimf_ / msssimh_kernels.hip.
 //
 // The three single-scale families differ in their sample type and in what a launch is told (bit depth; data range; encoding and data
 // range); each is described once by a small struct (Family16 / FamilyF / FamilyH) and the host flow -- validation, sub-batches, staging
@@ -16,6 +17,7 @@
 // the launch that read its ring slot kSfSlots enqueues ago.
 #include "ssim_context.h"
 #include "ssimh_kernels.h"
+#include "msssimh_kernels.h"
 #include "ssimw_kernels.h"
 #include "ssimk_kernels.h"
 
@@ -458,14 +460,79 @@ int enqueue_grads(rmgr_ssim_hip_Context* c, uint32_t count, const typename F::Pa
     return 0;
 }
 
-// ---- multi-scale SSIM of float32 samples ---------------------------------------------------------------------------------------------------
-// Scale 0 is read where the caller has it; the planes of scales >= 1 (and, in the backward, their gradient planes) are dense planes of
-// the context's scratch, one set per pair, rewritten by every sub-batch in stream order.
+// ---- multi-scale SSIM of float32 and of float16 / bfloat16 samples ---------------------------------------------------------------------------
+// Scale 0 is read where the caller has it; the planes of scales >= 1 (and, in the backward, their gradient planes) are dense float32
+// planes of the context's scratch, one set per pair, rewritten by every sub-batch in stream order.  The two families differ in scale 0
+// alone -- its samples, its descriptors and the kernels that read and write them -- and each is described by a small struct (MultiF /
+// MultiH) over which the flow is written once.
+//
+// A launch reads one table of pair descriptors, scales x n PairFDesc as [scale][pair] (rows >= 1: the pyramid), and -- backward -- one of
+// gradient descriptors, scales x n GradFDesc.  MultiF: row 0 holds the caller's planes.  MultiH: row 0 is not read (zeroed), and the
+// caller's n PairHDesc / GradHDesc follow the table.
+
+struct MultiF {
+    typedef FamilyF Single;
+    float range;
+    int validate(uint32_t count, const rmgr_ssim_hip_ParamsF* params, const void* out) const { return ssimf_validate(count, params, range, out); }
+    static size_t pair_bytes(uint32_t scales, uint32_t n) { return (size_t)scales * n * sizeof(PairFDesc); }
+    static size_t grad_bytes(uint32_t scales, uint32_t n) { return (size_t)scales * n * sizeof(GradFDesc); }
+    // Where the n scale-0 descriptors of a table go.
+    static PairFDesc* pairs0(uint8_t* table, uint32_t, uint32_t) { return reinterpret_cast<PairFDesc*>(table); }
+    static GradFDesc* grads0(uint8_t* table, uint32_t, uint32_t) { return reinterpret_cast<GradFDesc*>(table); }
+    hipError_t forward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, uint32_t n, uint32_t W, uint32_t H, uint32_t scales, bool wide, const double* w,
+                       double* means, double* values) const
+    {
+        return ssim_hip::launch_msssimf(reinterpret_cast<const PairFDesc*>(pairs), n, W, H, scales, wide, range, w, c->cu_count, c->xcd_count,
+                                        c->msf_partials, means, values, c->stream);
+    }
+    hipError_t backward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, const uint8_t* grads, uint32_t n, uint32_t W, uint32_t H, uint32_t scales,
+                        const double* w, const double* means, const float* g_out, int which) const
+    {
+        return ssim_hip::launch_msssimf_grad(reinterpret_cast<const PairFDesc*>(pairs), reinterpret_cast<const GradFDesc*>(grads), n, W, H, scales,
+                                             range, w, means, g_out, c->msf_coef, which, c->stream);
+    }
+};
+
+struct MultiH {
+    typedef FamilyH Single;
+    uint32_t sampleType;
+    float range;
+    int validate(uint32_t count, const rmgr_ssim_hip_Params16* params, const void* out) const { return ssimh_validate(count, params, sampleType, range, out); }
+    static size_t pair_bytes(uint32_t scales, uint32_t n) { return (size_t)scales * n * sizeof(PairFDesc) + n * sizeof(PairHDesc); }
+    static size_t grad_bytes(uint32_t scales, uint32_t n) { return (size_t)scales * n * sizeof(GradFDesc) + n * sizeof(GradHDesc); }
+    static PairHDesc* pairs0(uint8_t* table, uint32_t scales, uint32_t n)
+    {
+        memset(table, 0, n * sizeof(PairFDesc));
+        return reinterpret_cast<PairHDesc*>(table + (size_t)scales * n * sizeof(PairFDesc));
+    }
+    static GradHDesc* grads0(uint8_t* table, uint32_t scales, uint32_t n)
+    {
+        memset(table, 0, n * sizeof(GradFDesc));
+        return reinterpret_cast<GradHDesc*>(table + (size_t)scales * n * sizeof(GradFDesc));
+    }
+    hipError_t forward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, uint32_t n, uint32_t W, uint32_t H, uint32_t scales, bool wide, const double* w,
+                       double* means, double* values) const
+    {
+        return ssim_hip::launch_msssimh(reinterpret_cast<const PairHDesc*>(pairs + (size_t)scales * n * sizeof(PairFDesc)),
+                                        reinterpret_cast<const PairFDesc*>(pairs), n, W, H, scales, ssimh_type(sampleType), wide, range, w, c->cu_count,
+                                        c->xcd_count, c->msf_partials, means, values, c->stream);
+    }
+    hipError_t backward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, const uint8_t* grads, uint32_t n, uint32_t W, uint32_t H, uint32_t scales,
+                        const double* w, const double* means, const float* g_out, int which) const
+    {
+        return ssim_hip::launch_msssimh_grad(reinterpret_cast<const PairHDesc*>(pairs + (size_t)scales * n * sizeof(PairFDesc)),
+                                             reinterpret_cast<const PairFDesc*>(pairs),
+                                             reinterpret_cast<const GradHDesc*>(grads + (size_t)scales * n * sizeof(GradFDesc)),
+                                             reinterpret_cast<const GradFDesc*>(grads), n, W, H, scales, ssimh_type(sampleType), range, w, means, g_out,
+                                             c->msf_coef, which, c->stream);
+    }
+};
 
 // Every check the entry points share.
-int msssimf_validate(uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, uint32_t scales, const double* weights, const void* out)
+template <typename M>
+int ms_validate(const M& fam, uint32_t count, const typename M::Single::Params* params, uint32_t scales, const double* weights, const void* out)
 {
-    int rc = ssimf_validate(count, params, dataRange, out);
+    int rc = fam.validate(count, params, out);
     if (rc) return rc;
     if (scales < 1 || scales > RMGR_SSIM_HIP_MSSSIM_MAX_SCALES) return EINVAL;
     if (weights == NULL) {
@@ -481,7 +548,7 @@ int msssimf_validate(uint32_t count, const rmgr_ssim_hip_ParamsF* params, float 
 }
 
 // Device scratch one pair needs: the pyramid of both images, grad_planes (0 forward, 1 or 2 backward) coarse gradient pyramids, its
-// cell partials (forward) or coefficients (backward).
+// cell partials (forward) or coefficients (backward).  The same for both families: all of it is float32 / float64.
 uint64_t msf_pair_bytes(uint32_t W, uint32_t H, uint32_t scales, int grad_planes)
 {
     const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
@@ -490,15 +557,16 @@ uint64_t msf_pair_bytes(uint32_t W, uint32_t H, uint32_t scales, int grad_planes
 }
 
 // Pairs of params[i0 ..] one sub-batch takes (take() with a pair's multi-scale scratch; staged images count against the same cap).
-uint32_t msf_take(const rmgr_ssim_hip_ParamsF* params, uint32_t i0, uint32_t count, uint32_t scales, int grad_planes, bool stage, uint64_t& staged)
+template <typename M>
+uint32_t msf_take(const typename M::Single::Params* params, uint32_t i0, uint32_t count, uint32_t scales, int grad_planes, bool stage, uint64_t& staged)
 {
     const uint32_t W = params[0].width, H = params[0].height;
-    return take<FamilyF>(params, i0, count, ssim_hip::msssimf_max_count(W, H), msf_pair_bytes(W, H, scales, grad_planes), stage, false, staged);
+    return take<typename M::Single>(params, i0, count, ssim_hip::msssimf_max_count(W, H), msf_pair_bytes(W, H, scales, grad_planes), stage, false, staged);
 }
 
 
-// Fills rows 1 .. scales-1 of table[scale][pair] (scales x n; row 0, the caller's scale-0 descriptors without maps, is the caller's to
-// write): dense planes of `pyramid`, scale by scale, A then B of each pair.
+// Fills rows 1 .. scales-1 of table[scale][pair] (scales x n; row 0 is the caller's to write): dense planes of `pyramid`, scale by
+// scale, A then B of each pair.
 void msf_fill_coarse(PairFDesc* table, uint32_t n, uint32_t W, uint32_t H, uint32_t scales, float* pyramid)
 {
     float* at = pyramid;
@@ -516,44 +584,44 @@ void msf_fill_coarse(PairFDesc* table, uint32_t n, uint32_t W, uint32_t H, uint3
 
 // Enqueues the forward of n pairs (scale-0 descriptors without maps in host memory, images on the device) on the context's stream:
 // n x scales x 2 means and n values into device memory.
-int msssimf_enqueue(rmgr_ssim_hip_Context* c, uint32_t n, const PairFDesc* d, uint32_t W, uint32_t H, float range, uint32_t scales,
-                    const double* w, double* means, double* values)
+template <typename M>
+int ms_enqueue(rmgr_ssim_hip_Context* c, const M& fam, uint32_t n, const typename M::Single::Desc* d, uint32_t W, uint32_t H, uint32_t scales,
+               const double* w, double* means, double* values)
 {
     int rc;
     if ((rc = c->msf_pyramid.grow((size_t)(2 * ssim_hip::msf_pyramid_floats(W, H, scales) * n)))) return rc;
     if ((rc = c->msf_partials.grow((size_t)ssim_hip::msf_partials(W, H, n, scales)))) return rc;
     bool wide = false;
-    for (uint32_t i = 0; i < n; ++i) wide = wide || !ssim_hip::fitsf_narrow(d[i]);
-    return ring_launch(c, (size_t)scales * n * sizeof(PairFDesc),
+    for (uint32_t i = 0; i < n; ++i) wide = wide || !M::Single::fits_narrow(d[i]);
+    return ring_launch(c, M::pair_bytes(scales, n),
         [&](uint8_t* pin) {
-            memcpy(pin, d, n * sizeof(PairFDesc));
+            memcpy(M::pairs0(pin, scales, n), d, n * sizeof(*d));
             msf_fill_coarse(reinterpret_cast<PairFDesc*>(pin), n, W, H, scales, c->msf_pyramid);
         },
-        [&](const uint8_t* dev) {
-            return ssim_hip::launch_msssimf(reinterpret_cast<const PairFDesc*>(dev), n, W, H, scales, wide, range, w, c->cu_count, c->xcd_count,
-                                            c->msf_partials, means, values, c->stream);
-        });
+        [&](const uint8_t* dev) { return fam.forward(c, dev, n, W, H, scales, wide, w, means, values); });
 }
 
 // Every sub-batch of the forward into values[0 .. count-1] and means[count x scales x 2] (device).  stage: host pointers -- each
 // sub-batch's images are copied (each image's sample range) into c->stage_a first.
-int msssimf_forward(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float range, uint32_t scales, const double* w,
-                    double* means, double* values, bool stage)
+template <typename M>
+int ms_forward(rmgr_ssim_hip_Context* c, const M& fam, uint32_t count, const typename M::Single::Params* params, uint32_t scales, const double* w,
+               double* means, double* values, bool stage)
 {
+    typedef typename M::Single F;
     const uint32_t W = params[0].width, H = params[0].height;
     int rc;
     try {
-        std::vector<PairFDesc> d;
+        std::vector<typename F::Desc> d;
         for (uint32_t i0 = 0; i0 < count;) {
             uint64_t staged, off = 0;
-            const uint32_t n = msf_take(params, i0, count, scales, 0, stage, staged);
+            const uint32_t n = msf_take<M>(params, i0, count, scales, 0, stage, staged);
             if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
             d.resize(n);
             for (uint32_t i = 0; i < n; ++i) {
-                d[i] = make_desc<FamilyF>(params[i0 + i], false);
-                if (stage && (rc = stage_images<FamilyF>(c, params[i0 + i], W, H, d[i], off))) return rc;
+                d[i] = make_desc<F>(params[i0 + i], false);
+                if (stage && (rc = stage_images<F>(c, params[i0 + i], W, H, d[i], off))) return rc;
             }
-            if ((rc = msssimf_enqueue(c, n, &d[0], W, H, range, scales, w, means + (size_t)i0 * scales * 2, values + i0))) return rc;
+            if ((rc = ms_enqueue(c, fam, n, &d[0], W, H, scales, w, means + (size_t)i0 * scales * 2, values + i0))) return rc;
             i0 += n;
         }
     } catch (...) {
@@ -563,18 +631,103 @@ int msssimf_forward(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hi
 }
 
 // The blocking entry points: every sub-batch into c->msf_out (count values, then count x scales x 2 means), one copy back, one wait.
-int msssimf_blocking(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float range, uint32_t scales, const double* w,
-                     float* msssim, double* scaleMeans, bool stage)
+template <typename M>
+int ms_blocking(rmgr_ssim_hip_Context* c, const M& fam, uint32_t count, const typename M::Single::Params* params, uint32_t scales, const double* w,
+                float* msssim, double* scaleMeans, bool stage)
 {
     const size_t total = (1 + 2 * (size_t)scales) * count;
     int rc;
     if ((rc = c->msf_out.grow(total))) return rc;
     if ((rc = c->msf_out_pin.grow(total))) return rc;
-    if ((rc = msssimf_forward(c, count, params, range, scales, w, c->msf_out + count, c->msf_out, stage))) return rc;
+    if ((rc = ms_forward(c, fam, count, params, scales, w, c->msf_out + count, c->msf_out, stage))) return rc;
     HIP_TRY(hipMemcpyAsync(c->msf_out_pin, c->msf_out, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < count; ++i) msssim[i] = (float)c->msf_out_pin[i];
     if (scaleMeans) memcpy(scaleMeans, c->msf_out_pin + count, (size_t)count * scales * 2 * sizeof(double));
+    return 0;
+}
+
+// What the three forward entries do once ms_validate has passed.
+template <typename M>
+int ms_enqueue_entry(rmgr_ssim_hip_Context* c, const M& fam, uint32_t count, const typename M::Single::Params* params, uint32_t scales,
+                     const double* weights, double* valuesDevice, double* scaleMeansDevice)
+{
+    if (scaleMeansDevice == NULL || !c) return EINVAL;
+    USE_DEVICE(c);
+    return ms_forward(c, fam, count, params, scales, weights ? weights : kWangWeights, scaleMeansDevice, valuesDevice, false);
+}
+
+template <typename M>
+int ms_device_entry(rmgr_ssim_hip_Context* c, const M& fam, uint32_t count, const typename M::Single::Params* params, uint32_t scales,
+                    const double* weights, float* msssim, double* scaleMeans)
+{
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return ms_blocking(c, fam, count, params, scales, weights ? weights : kWangWeights, msssim, scaleMeans, false);
+}
+
+template <typename M>
+int ms_host_entry(rmgr_ssim_hip_Context* c, const M& fam, uint32_t count, const typename M::Single::Params* params, uint32_t scales,
+                  const double* weights, float* msssim, double* scaleMeans)
+{
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    int rc = lease.take(c);
+    if (rc) return rc;
+    USE_DEVICE(lease.c);
+    return ms_blocking(lease.c, fam, count, params, scales, weights ? weights : kWangWeights, msssim, scaleMeans, true);
+}
+
+// The gradient entry, arguments valid: per sub-batch the coefficients, the pyramid again and the gradient kernels from the coarsest scale
+// down, the caller's planes (float32, or the samples' encoding) at scale 0 and dense float32 scratch planes below.
+template <typename M>
+int ms_grad_entry(rmgr_ssim_hip_Context* c, const M& fam, uint32_t count, const typename M::Single::Params* params, uint32_t scales,
+                  const double* weights, const double* scaleMeansDevice, const float* gradOutDevice, const typename M::Single::Grad* gradA,
+                  const typename M::Single::Grad* gradB)
+{
+    typedef typename M::Single F;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    int rc;
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = grad_which(gradA, gradB), planes = (gradA ? 1 : 0) + (gradB ? 1 : 0);
+    const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
+    const double* w = weights ? weights : kWangWeights;
+    for (uint32_t i0 = 0; i0 < count;) {
+        uint64_t staged;
+        const uint32_t n = msf_take<M>(params, i0, count, scales, planes, false, staged);
+        if ((rc = c->msf_pyramid.grow((size_t)(2 * pyr * n)))) return rc;
+        if ((rc = c->msf_grads.grow((size_t)((uint64_t)planes * pyr * n)))) return rc;
+        if ((rc = c->msf_coef.grow((size_t)n * scales))) return rc;
+        const size_t pair_bytes = M::pair_bytes(scales, n);
+        rc = ring_launch(c, pair_bytes + M::grad_bytes(scales, n),
+            [&](uint8_t* pin) {
+                typename F::Desc* pd = M::pairs0(pin, scales, n);
+                typename F::GradDesc* gd = M::grads0(pin + pair_bytes, scales, n);
+                for (uint32_t i = 0; i < n; ++i) {
+                    pd[i] = make_desc<F>(params[i0 + i], false);
+                    gd[i] = make_grad_desc<F>(gradA, gradB, i0 + i);
+                }
+                msf_fill_coarse(reinterpret_cast<PairFDesc*>(pin), n, W, H, scales, c->msf_pyramid);
+                // gradient planes of scales >= 1: dense scratch, scale by scale, dA then dB of each pair
+                GradFDesc* coarse = reinterpret_cast<GradFDesc*>(pin + pair_bytes);
+                float* at = c->msf_grads;
+                for (uint32_t sc = 1; sc < scales; ++sc) {
+                    const uint64_t plane = ssim_hip::msf_plane(W, H, sc);
+                    const int64_t stride = ssim_hip::msf_dim(W, sc);
+                    for (uint32_t i = 0; i < n; ++i) {
+                        GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
+                        if (gradA) { g.ga = at; g.ga_step = 1; g.ga_stride = stride; at += plane; }
+                        if (gradB) { g.gb = at; g.gb_step = 1; g.gb_stride = stride; at += plane; }
+                        coarse[(size_t)sc * n + i] = g;
+                    }
+                }
+            },
+            [&](const uint8_t* dev) {
+                return fam.backward(c, dev, dev + pair_bytes, n, W, H, scales, w, scaleMeansDevice + (size_t)i0 * scales * 2, gradOutDevice + i0, which);
+            });
+        if (rc) return rc;
+        i0 += n;
+    }
     return 0;
 }
 
@@ -813,86 +966,79 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* c, rmgr
 rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
                                            rmgr_uint32_t scales, const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
 {
-    const int rc = msssimf_validate(count, params, dataRange, scales, weights, valuesDevice);
-    if (rc) return rc;
-    if (scaleMeansDevice == NULL || !c) return EINVAL;
-    USE_DEVICE(c);
-    return msssimf_forward(c, count, params, dataRange, scales, weights ? weights : kWangWeights, scaleMeansDevice, valuesDevice, false);
+    const MultiF fam = {dataRange};
+    const int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
+    return rc ? rc : ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_msssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
                                                   rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const int rc = msssimf_validate(count, params, dataRange, scales, weights, msssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return msssimf_blocking(c, count, params, dataRange, scales, weights ? weights : kWangWeights, msssim, scaleMeans, false);
+    const MultiF fam = {dataRange};
+    const int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    return rc ? rc : ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_msssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
                                                 rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    int rc = msssimf_validate(count, params, dataRange, scales, weights, msssim);
-    if (rc) return rc;
-    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
-    if ((rc = lease.take(c))) return rc;
-    USE_DEVICE(lease.c);
-    return msssimf_blocking(lease.c, count, params, dataRange, scales, weights ? weights : kWangWeights, msssim, scaleMeans, true);
+    const MultiF fam = {dataRange};
+    const int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    return rc ? rc : ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
                                                 rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
                                                 const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
 {
-    int rc = msssimf_validate(count, params, dataRange, scales, weights, gradOutDevice);
+    const MultiF fam = {dataRange};
+    int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
     if (rc) return rc;
     if (scaleMeansDevice == NULL) return EINVAL;
     if ((rc = validate_grads(count, gradA, gradB))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = grad_which(gradA, gradB), planes = (gradA ? 1 : 0) + (gradB ? 1 : 0);
-    const uint64_t pyr = ssim_hip::msf_pyramid_floats(W, H, scales);
-    const double* w = weights ? weights : kWangWeights;
-    for (uint32_t i0 = 0; i0 < count;) {
-        uint64_t staged;
-        const uint32_t n = msf_take(params, i0, count, scales, planes, false, staged);
-        if ((rc = c->msf_pyramid.grow((size_t)(2 * pyr * n)))) return rc;
-        if ((rc = c->msf_grads.grow((size_t)((uint64_t)planes * pyr * n)))) return rc;
-        if ((rc = c->msf_coef.grow((size_t)n * scales))) return rc;
-        const size_t pair_bytes = (size_t)scales * n * sizeof(PairFDesc);
-        rc = ring_launch(c, pair_bytes + (size_t)scales * n * sizeof(GradFDesc),
-            [&](uint8_t* pin) {
-                PairFDesc* pd = reinterpret_cast<PairFDesc*>(pin);
-                GradFDesc* gd = reinterpret_cast<GradFDesc*>(pin + pair_bytes);
-                for (uint32_t i = 0; i < n; ++i) {
-                    pd[i] = make_desc<FamilyF>(params[i0 + i], false);
-                    gd[i] = make_grad_desc<FamilyF>(gradA, gradB, i0 + i);
-                }
-                msf_fill_coarse(pd, n, W, H, scales, c->msf_pyramid);
-                // gradient planes of scales >= 1: dense scratch, scale by scale, dA then dB of each pair
-                float* at = c->msf_grads;
-                for (uint32_t sc = 1; sc < scales; ++sc) {
-                    const uint64_t plane = ssim_hip::msf_plane(W, H, sc);
-                    const int64_t stride = ssim_hip::msf_dim(W, sc);
-                    for (uint32_t i = 0; i < n; ++i) {
-                        GradFDesc g = {NULL, 0, 0, NULL, 0, 0};
-                        if (gradA) { g.ga = at; g.ga_step = 1; g.ga_stride = stride; at += plane; }
-                        if (gradB) { g.gb = at; g.gb_step = 1; g.gb_stride = stride; at += plane; }
-                        gd[(size_t)sc * n + i] = g;
-                    }
-                }
-            },
-            [&](const uint8_t* dev) {
-                return ssim_hip::launch_msssimf_grad(reinterpret_cast<const PairFDesc*>(dev), reinterpret_cast<const GradFDesc*>(dev + pair_bytes),
-                                                     n, W, H, scales, dataRange, w, scaleMeansDevice + (size_t)i0 * scales * 2, gradOutDevice + i0,
-                                                     c->msf_coef, which, c->stream);
-            });
-        if (rc) return rc;
-        i0 += n;
-    }
-    return 0;
+    return ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);
+}
+
+// ---- multi-scale SSIM of float16 / bfloat16 samples and its gradient: the msssimf flow with 2-byte samples at scale 0 -------------------------
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                           rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                           double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
+{
+    const MultiH fam = {sampleType, dataRange};
+    const int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
+    return rc ? rc : ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimh_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                  float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    const MultiH fam = {sampleType, dataRange};
+    const int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    return rc ? rc : ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimh_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    const MultiH fam = {sampleType, dataRange};
+    const int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    return rc ? rc : ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                const double* scaleMeansDevice, const float* gradOutDevice, const rmgr_ssim_hip_GradH* gradA,
+                                                const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
+{
+    const MultiH fam = {sampleType, dataRange};
+    int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
+    if (rc) return rc;
+    if (scaleMeansDevice == NULL) return EINVAL;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    return ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);
 }
 
 } // extern "C"

@@ -1,7 +1,7 @@
-"""SSIM of float32, float16 and bfloat16 tensors and multi-scale SSIM of float32 tensors as differentiable PyTorch operations, on the
-library's fused gfx950 kernels.
+"""SSIM and multi-scale SSIM of float32, float16 and bfloat16 tensors as differentiable PyTorch operations, on the library's fused gfx950
+kernels.
 
-    from ssim_amd.torch_ops import ssim, ssim_map, SSIMLoss, ms_ssim, MSSSIMLoss
+    from ssim_amd.torch_ops import ssim, ssim_map, SSIMLoss, ms_ssim, ms_ssim_amp, MSSSIMLoss
     loss = 0.8 * (x - y).abs().mean() + 0.2 * SSIMLoss()(x, y)      # x, y: (N, C, H, W) float32 on the GPU
     loss = 0.16 * (x - y).abs().mean() + 0.84 * MSSSIMLoss()(x, y)
     loss.backward()
@@ -11,16 +11,20 @@ rmgr_ssim_hip_enqueue_ssimf_grad; ms_ssim(x, y, data_range, scales, weights) is 
 rmgr_ssim_hip_enqueue_msssimf_grad.  Everything is enqueued on torch.cuda.current_stream() of the tensors' device through a Context cached
 per (device, stream); neither forward nor backward waits for the host.  There is no eager fall-back: without the library this raises.
 
-float16 and bfloat16 (ssim and SSIMLoss only).  x and y both float16 or both bfloat16 run rmgr_ssim_hip_enqueue_ssimh and its backward
-rmgr_ssim_hip_enqueue_ssimh_grad: the samples are read as they are (2 B/px), the result is float32 per plane at every input dtype (a loss
-of 1 - 0.98 has no business in 8 significant bits), and the gradient comes back in the inputs' dtype, written by the kernel into a 2 B/px
-tensor with one rounding and no float32 intermediate.  Two things to know:
+float16 and bfloat16.  x and y both float16 or both bfloat16 run rmgr_ssim_hip_enqueue_ssimh and its backward
+rmgr_ssim_hip_enqueue_ssimh_grad (ms_ssim_amp and MSSSIMLoss: rmgr_ssim_hip_enqueue_msssimh and _msssimh_grad): the samples are read as
+they are (2 B/px), the result is float32 per plane at every input dtype (a loss of 1 - 0.98 has no business in 8 significant bits), and
+the gradient comes back in the inputs' dtype, written by the kernel into a 2 B/px tensor with one rounding and no float32 intermediate.  Two things to know:
   * inside torch.autocast the function takes its tensors as they come and is not itself autocast: a conv's bfloat16 output is read as
     bfloat16, a float32 tensor as float32, and a mixed pair is a TypeError, not a silent cast;
   * with float16 the gradient of a mean SSIM is of order 1 / (W H) and underflows without torch.amp.GradScaler.  With a scaled loss
     the scale arrives in grad_out, which stays float32, and is applied before the single rounding: the result is round(scale * g), not
     scale * round(g).
-ms_ssim and MSSSIMLoss keep refusing 16-bit tensors (TypeError): that is the follow-up, and needs only scale 0's loads and stores.
+ms_ssim_amp and MSSSIMLoss take 16-bit tensors the same way: only scale 0 holds 16-bit samples (the pyramid is float32 from scale 1 on),
+the value has the bits of ms_ssim(x.float(), y.float()) and the gradient is that call's float32 gradient rounded once.  Two warts, both
+pinned by tests from the time there was no 16-bit multi-scale path: ms_ssim itself stays float32-only (16-bit tensors are a TypeError
+there; ms_ssim_amp is the same function without that refusal), and two 16-bit CPU tensors are a TypeError in ms_ssim_amp and MSSSIMLoss
+(ssim: a ValueError, like every CPU tensor).
 
 The map.  ssim_map(x, y, data_range) returns the per-pixel SSIM, float32 of shape x.shape, for losses that are not a plain mean per plane.
 The forward is the same kernel writing its map; the backward is rmgr_ssim_hip_enqueue_ssimf_map_grad / _ssimh_map_grad, the fused gradient
@@ -374,7 +378,11 @@ def _make_ms_function():
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
-                _context(x.device, work).enqueue_msssimf(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights)
+                st = _sample_type(torch, x.dtype)
+                if st is None:
+                    _context(x.device, work).enqueue_msssimf(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights)
+                else:
+                    _context(x.device, work).enqueue_msssimh(params, n, data_range, st, values.data_ptr(), means.data_ptr(), scales, weights)
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y, means)
@@ -391,20 +399,39 @@ def _make_ms_function():
                 return None, None, None, None, None
             params, n = _params(x, y)
             g = grad_out.to(torch.float32).reshape(-1).contiguous()
-            gx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_x else None
-            gy = torch.empty(y.shape, dtype=torch.float32, device=y.device) if want_y else None
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
+            gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
             if n:
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
-                _context(x.device, work).enqueue_msssimf_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(),
-                                                              _grad_planes(gx, n, h, w) if want_x else None,
-                                                              _grad_planes(gy, n, h, w) if want_y else None, ctx.scales, ctx.weights)
+                st = _sample_type(torch, x.dtype)
+                ga = _grad_planes(gx, n, h, w) if want_x else None
+                gb = _grad_planes(gy, n, h, w) if want_y else None
+                if st is None:
+                    _context(x.device, work).enqueue_msssimf_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales, ctx.weights)
+                else:
+                    _context(x.device, work).enqueue_msssimh_grad(params, n, ctx.data_range, st, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales,
+                                                                  ctx.weights)
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None, None, None
 
     return _MSSSIM
+
+
+def _is_half_pair(x, y):
+    """Two tensors, both float16 or both bfloat16."""
+    import torch
+    return isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.dtype == y.dtype and x.dtype in (torch.float16, torch.bfloat16)
+
+
+def _ms_ssim(x, y, r, scales, weights):
+    global _ms_function
+    scales, w = _check_scales(scales, weights)
+    if _ms_function is None:
+        _ms_function = _make_ms_function()
+    return _ms_function.apply(x, y, r, scales, w)
 
 
 def ms_ssim(x, y, data_range=1.0, scales=5, weights=None):
@@ -413,18 +440,29 @@ def ms_ssim(x, y, data_range=1.0, scales=5, weights=None):
     >= 0.  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that need it, from x, y and the
     (planes, scales, 2) float64 per-scale means the forward keeps.  TypeError / ValueError as ssim(), plus ValueError for scales outside
     1 .. 8, a wrong number of weights, a negative or non-finite weight (TypeError: scales is not an int).  float16 and bfloat16 tensors
-    are refused (TypeError) -- unlike ssim(); taking them needs only scale 0's loads and stores and is the follow-up."""
-    global _ms_function
-    r = _check(x, y, data_range)
-    scales, w = _check_scales(scales, weights)
-    if _ms_function is None:
-        _ms_function = _make_ms_function()
-    return _ms_function.apply(x, y, r, scales, w)
+    are a TypeError here, on any device: tests/tools/ssimh_torch_checks.py and tests/test_ssimh_cpu.py pin that refusal from the time
+    there was no 16-bit path.  ms_ssim_amp() and MSSSIMLoss take them."""
+    if _is_half_pair(x, y):
+        raise TypeError("ms_ssim: float32 tensors expected, got %s; ms_ssim_amp() and MSSSIMLoss take float16 / bfloat16 tensors" % (x.dtype,))
+    return _ms_ssim(x, y, _check(x, y, data_range), scales, weights)
+
+
+def ms_ssim_amp(x, y, data_range=1.0, scales=5, weights=None):
+    """ms_ssim() for tensors as they come under mixed precision: two GPU tensors of identical shape (..., H, W), both float32, both float16
+    or both bfloat16, any strides (each plane is addressed in place, no copy or widening): a float32 tensor of shape x.shape[:-2] at every
+    input dtype.  float32 tensors: exactly ms_ssim().  float16 and bfloat16: the value has the bits of ms_ssim(x.float(), y.float()),
+    the gradient has the inputs' dtype and is that call's float32 gradient rounded once (see the top of this file for autocast and loss
+    scaling); saved for the backward are x, y and the float64 means.  Errors: as ms_ssim(), and -- unlike ssim(), where every CPU tensor
+    is a ValueError -- two float16 or two bfloat16 CPU tensors are a TypeError: 16-bit tensors are taken on a GPU only (one of the two
+    on a GPU: the ValueError)."""
+    if _is_half_pair(x, y) and not x.is_cuda and not y.is_cuda:
+        raise TypeError("ms_ssim_amp: float16 / bfloat16 tensors are taken on a GPU only, got %s on %s and %s" % (x.dtype, x.device, y.device))
+    return _ms_ssim(x, y, _check(x, y, data_range, half=True), scales, weights)
 
 
 class MSSSIMLoss(object):
-    """1 - ms_ssim(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per plane).  A plain callable: it
-    has no parameters.  float32 tensors only, as ms_ssim()."""
+    """1 - ms_ssim_amp(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per plane).  A plain callable:
+    it has no parameters.  float32, float16 or bfloat16 tensors, as ms_ssim_amp(); the loss is float32 at every input dtype."""
 
     def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean"):
         if reduction not in ("mean", "none"):
@@ -433,5 +471,5 @@ class MSSSIMLoss(object):
         self.data_range, self.scales, self.weights, self.reduction = data_range, scales, weights, reduction
 
     def __call__(self, x, y):
-        loss = 1.0 - ms_ssim(x, y, self.data_range, self.scales, self.weights)
+        loss = 1.0 - ms_ssim_amp(x, y, self.data_range, self.scales, self.weights)
         return loss.mean() if self.reduction == "mean" else loss
