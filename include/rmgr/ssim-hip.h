@@ -32,6 +32,8 @@
  *       of float16 / bfloat16 images and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssimf_map_grad, rmgr_ssim_hip_enqueue_ssimh_map_grad   gradient of the SSIM MAP for a per-pixel upstream
  *                                      gradient: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssim3f, rmgr_ssim_hip_compute_ssim3f_device / _host, rmgr_ssim_hip_enqueue_ssim3f_grad   SSIM of float32
+ *                                      VOLUMES (three-dimensional window) and its gradient: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -763,6 +765,90 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_grad(rmgr_ssim_hip_Context* ctx, rm
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                                       float dataRange, const rmgr_ssim_hip_Window* window, const rmgr_ssim_hip_GradOutF* gradOutMaps,
                                                       const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
+
+/*
+ * SSIM of `count` pairs of float32 VOLUMES of one size under a THREE-DIMENSIONAL window, and its gradient (MRI / CT reconstruction,
+ * volumetric super-resolution, spatio-temporal video losses): what pytorch-msssim computes with spatial_dims = 3, torchmetrics on 5-D
+ * input, MONAI's SSIMLoss(spatial_dims = 3) and skimage on n-D arrays.  The 2-D entries on a stack of slices compute independent 2-D
+ * SSIMs with no window across slices; this family is not that.  No reference counterpart: the definition is pinned down here, and
+ * tests/ssim3f_model.py restates it in float64, the gradient included.  Additions only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ *   Samples  float32 volumes, used as stored.  Negative values and values above dataRange are not rejected; NaN and Inf propagate.
+ *   Data range  dataRange, one float per call, finite and > 0 (R): C1 and C2 exactly as for rmgr_ssim_hip_enqueue_ssimf.
+ *   Inputs   params[0 .. count-1]: width, height, depth (the same for every pair, each 1 .. 0x7FFF0000); voxel (x, y, z) of A is
+ *            imgA.topLeft[x * step + y * stride + z * sliceStride], in FLOATS, each a signed ptrdiff_t of any value, negatives and 0
+ *            included; ssimMap NULL (no map) or a float volume addressed the same way by ssimStep / ssimStride / ssimSliceStride -- per
+ *            pair.  Every offset is a 64-bit product: volumes whose slices lie more than 2^32 bytes apart work.
+ *   Window   the engine's 11-tap Gaussian (sigma 1.5, the fp32 taps of every other entry), separable over x, y and z, with CLAMPED edges
+ *            on every axis, same-size output: the linear operator G.
+ *   Per voxel  the formulas of rmgr_ssim_hip_enqueue_ssimf with this G: mu_a = G a, mu_b = G b, s_aa = G(a^2) - mu_a^2, s_bb = G(b^2) -
+ *            mu_b^2, s_ab = G(a b) - mu_a mu_b; A1 = 2 mu_a mu_b + C1, A2 = 2 s_ab + C2, B1 = mu_a^2 + mu_b^2 + C1, B2 = s_aa + s_bb + C2;
+ *            ssim = A1 A2 / (B1 B2).
+ *   Global   S_i: the fp64 sum of the per-voxel values divided by double(W) * double(H) * double(D).
+ *   Gradient  given gOut[i] = dLoss/dS_i, the exact derivative of the above, clamped edges included.  With k = float(double(gOut[i]) /
+ *            (double(W) * double(H) * double(D))) and ssimf's d_ab = 2 A1 / (B1 B2), d_aa = -ssim / B2,
+ *              d_mu = 2 mu_b A2 / (B1 B2) - 2 mu_a ssim / B1 - 2 mu_a d_aa - mu_b d_ab:
+ *              dLoss/da = Gt(k d_mu) + 2 a Gt(k d_aa) + b Gt(k d_ab),    dLoss/db: the same with a and b exchanged.
+ *            Gt is the ADJOINT of the clamped 3-D window.  It is separable; on each axis it is ssimf's rule: the plain blur of v
+ *            zero-extended by 5, with the 5 results beyond each end added onto the end voxel.  The rule holds down to 1 x 1 x 1.
+ *   Arithmetic  fp32 with centred samples, a' = a - cA, b' = b - cB.  ONE centre per volume (not one per 128 columns as in 2-D): A's and
+ *            B's sample at ((W - 1) / 2, (H - 1) / 2, (D - 1) / 2), used when its magnitude is at most dataRange, else 0.  It depends on
+ *            the volume alone.  (One centre for the whole volume lets the backward keep coefficients of the centred variables: a
+ *            coefficient and the voxel that collects it always share their centre.)  The x pass runs centre tap first on folded symmetric
+ *            sums, the y pass and the z pass in source order, the first product plain and the others fused; the gradient differentiates in
+ *            the centred variables, as ssimf's.  The context's mode does not change this path.
+ *   Determinism  each volume's sum runs over fixed cells of 16 x 16 x 8 voxels at absolute positions in a fixed order, and every map and
+ *            gradient voxel is written by exactly one work-item in a fixed summation order; the order does not depend on how a launch is cut
+ *            into tiles, z-chunks or sub-batches; no floating-point atomics.  A pair gives the same bits -- value, map, gradients -- alone or
+ *            anywhere in a batch, on every call, through every entry point, with one gradient or both, and as any view (negative or
+ *            permuted strides, interleaved samples) compared with the same voxels stored densely.
+ *   Reach    a NaN voxel makes NaN exactly the 11 x 11 x 11 map voxels and the 21 x 21 x 21 gradient voxels around it, clipped to the volume
+ *            (clamping taken into account); everything else stays finite (a NaN at the centre position makes the centre 0).
+ *
+ * _enqueue_ssim3f: device pointers; asynchronous on the context's stream, never waits for the host; writes each pair's fp64 SUM of
+ *            per-voxel values to sumsDevice[i] (device memory).
+ * _compute_ssim3f_device: device pointers; blocks; ssim: count floats in host memory.
+ * _compute_ssim3f_host: host pointers (ctx NULL: a default context).  The volumes are staged to the device and each map is copied back at
+ *            its own strides; a batch runs in sub-batches that keep the device scratch under about 1 GB, at least one volume each.
+ * _enqueue_ssim3f_grad: everything device-resident, asynchronous on the context's stream, no host synchronisation.  gradOutDevice: count
+ *            floats in DEVICE memory.  gradA / gradB: arrays of count rmgr_ssim_hip_Grad3F (host memory); either may be NULL, not both.
+ *            Gradients are WRITTEN, not accumulated.  A gradient volume must not overlap an input or another gradient volume: not checked.
+ *            params[i].ssimMap is ignored.
+ *            Scratch: a first walk writes the weighted partial derivatives k d_mu, k d_aa, k d_ab of every voxel -- 12 bytes per voxel for
+ *            one gradient, 16 for both (d_mu differs, d_aa and d_ab are shared) -- into the context's scratch, a second walk applies Gt.
+ *            The scratch belongs to the context and is reused in stream order; a batch runs in sub-batches of about 1 GB of it, at least one
+ *            volume each (a volume of 512^3 takes 2 GB for both gradients).
+ * EINVAL: count == 0; a NULL params, ssim, volume pointer, sumsDevice, gradOutDevice or gradient volume; both gradient arrays NULL; a zero
+ *         or differing width, height or depth, or one above 0x7FFF0000; a volume with more than 2^24 - 1 tiles of 16 x 16 columns; a
+ *         dataRange that is not finite or not > 0; a volume, map or gradient pointer that is not 4-byte aligned; a NULL ctx for anything
+ *         but _host -- all checked before any device is touched.  ENODEV: no device.
+ *
+ * Follow-ups, not in this interface: a caller-chosen window (the _win entries), float16 / bfloat16 volumes, multi-scale SSIM of volumes
+ * and a per-voxel upstream gradient.
+ */
+typedef struct rmgr_ssim_hip_Img3F {
+    const float* topLeft;
+    ptrdiff_t step, stride, sliceStride;        /* in floats */
+} rmgr_ssim_hip_Img3F;
+typedef struct rmgr_ssim_hip_Params3F {
+    rmgr_uint32_t       width, height, depth;
+    rmgr_ssim_hip_Img3F imgA, imgB;
+    float*              ssimMap;                /* NULL: no map */
+    ptrdiff_t           ssimStep, ssimStride, ssimSliceStride;    /* in floats */
+} rmgr_ssim_hip_Params3F;
+typedef struct rmgr_ssim_hip_Grad3F {
+    float*    topLeft;
+    ptrdiff_t step, stride, sliceStride;        /* in floats */
+} rmgr_ssim_hip_Grad3F;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                          float dataRange, double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                 float dataRange, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                               float dataRange, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                               float dataRange, const float* gradOutDevice,
+                                               const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

@@ -72,6 +72,23 @@ class GradF(ctypes.Structure):
     _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
 
 
+class Img3F(ctypes.Structure):
+    """rmgr_ssim_hip_Img3F: one float32 volume; step, stride and sliceStride count floats, not bytes."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd), ("sliceStride", c_pd)]
+
+
+class Params3F(ctypes.Structure):
+    """rmgr_ssim_hip_Params3F: ssimStep, ssimStride and ssimSliceStride count floats; ssimMap None = no map."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("depth", ctypes.c_uint32),
+                ("imgA", Img3F), ("imgB", Img3F),
+                ("ssimMap", ctypes.c_void_p), ("ssimStep", c_pd), ("ssimStride", c_pd), ("ssimSliceStride", c_pd)]
+
+
+class Grad3F(ctypes.Structure):
+    """rmgr_ssim_hip_Grad3F: one gradient volume in device memory; step, stride and sliceStride count floats."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd), ("sliceStride", c_pd)]
+
+
 class GradH(ctypes.Structure):
     """rmgr_ssim_hip_GradH: one float16 / bfloat16 gradient plane in device memory; step and stride count 16-bit samples."""
     _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
@@ -184,6 +201,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssimf_win", "rmgr_ssim_hip_compute_ssimf_win_device", "rmgr_ssim_hip_compute_ssimf_win_host",
     "rmgr_ssim_hip_enqueue_ssimf_win_grad", "rmgr_ssim_hip_enqueue_ssimf_win_map_grad",
     "rmgr_ssim_hip_enqueue_msssimh", "rmgr_ssim_hip_compute_msssimh_device", "rmgr_ssim_hip_compute_msssimh_host", "rmgr_ssim_hip_enqueue_msssimh_grad",
+    "rmgr_ssim_hip_enqueue_ssim3f", "rmgr_ssim_hip_compute_ssim3f_device", "rmgr_ssim_hip_compute_ssim3f_host", "rmgr_ssim_hip_enqueue_ssim3f_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -269,6 +287,10 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssimh_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_compute_ssimh_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssimh_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
+        "rmgr_ssim_hip_enqueue_ssim3f": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, vp],
+        "rmgr_ssim_hip_compute_ssim3f_device": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssim3f_host": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssim3f_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, vp, ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
         "rmgr_ssim_hip_enqueue_ssimf_map_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
         "rmgr_ssim_hip_enqueue_ssimh_map_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
         "rmgr_ssim_hip_enqueue_ssimf_win": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, vp],
@@ -629,6 +651,61 @@ def compute_ssimf_batch(pairs, data_range, ctx=None, window=None):
     return np.array(out[:n], np.float32)
 
 
+def make_params3f(width, height, depth, a_ptr, a_strides, b_ptr, b_strides, map_ptr=None, map_strides=None):
+    """rmgr_ssim_hip_Params3F; a_strides, b_strides, map_strides: (step, stride, sliceStride) in floats (map_strides None: a dense
+    depth x height x width map)."""
+    p = Params3F()
+    p.width, p.height, p.depth = width, height, depth
+    p.imgA = Img3F(a_ptr, *a_strides)
+    p.imgB = Img3F(b_ptr, *b_strides)
+    p.ssimMap = map_ptr
+    p.ssimStep, p.ssimStride, p.ssimSliceStride = (1, width, width * height) if map_strides is None else map_strides
+    return p
+
+
+def _f32_volume(x):
+    """A native float32 D x H x W array whose strides are whole floats: x itself when it already is one (negative strides kept)."""
+    assert x.ndim == 3 and x.dtype.kind == "f" and x.dtype.itemsize == 4, "D x H x W float32 expected"
+    if not x.dtype.isnative:
+        x = x.astype(np.float32)
+    if any(s % 4 for s in x.strides) or x.ctypes.data % 4:
+        x = np.ascontiguousarray(x)
+    return x
+
+
+def _params3f_of(a, b, map_ptr=None):
+    d, h, w = a.shape
+    return make_params3f(w, h, d, a.ctypes.data, (a.strides[2] // 4, a.strides[1] // 4, a.strides[0] // 4),
+                         b.ctypes.data, (b.strides[2] // 4, b.strides[1] // 4, b.strides[0] // 4), map_ptr)
+
+
+def compute_ssim3f(a, b, data_range, want_map=False, ctx=None):
+    """SSIM of two D x H x W float32 host volumes at `data_range` under the three-dimensional 11-tap window (any strides numpy can
+    express, negative ones included) through rmgr_ssim_hip_compute_ssim3f_host.  Returns (float32 value, D x H x W float32 map or None)."""
+    a, b = _f32_volume(a), _f32_volume(b)
+    assert a.shape == b.shape
+    m = np.empty(a.shape, np.float32) if want_map else None
+    params = (Params3F * 1)()
+    params[0] = _params3f_of(a, b, m.ctypes.data if want_map else None)
+    out = (ctypes.c_float * 1)()
+    _check("rmgr_ssim_hip_compute_ssim3f_host",
+           load_library().rmgr_ssim_hip_compute_ssim3f_host(ctx.handle if ctx is not None else None, 1, params, data_range, out))
+    return np.float32(out[0]), m
+
+
+def compute_ssim3f_batch(pairs, data_range, ctx=None):
+    """compute_ssim3f() of many host pairs of one size in one call (no maps): a float32 array."""
+    pairs = [(_f32_volume(a), _f32_volume(b)) for a, b in pairs]
+    n = len(pairs)
+    params = (Params3F * max(n, 1))()
+    for i, (a, b) in enumerate(pairs):
+        params[i] = _params3f_of(a, b)
+    out = (ctypes.c_float * max(n, 1))()
+    _check("rmgr_ssim_hip_compute_ssim3f_host",
+           load_library().rmgr_ssim_hip_compute_ssim3f_host(ctx.handle if ctx is not None else None, n, params, data_range, out))
+    return np.array(out[:n], np.float32)
+
+
 def sample_type_code(sample_type):
     """RMGR_SSIM_HIP_SAMPLE_F16 / _BF16 of "float16" / "bfloat16" (or of the code itself).  ValueError: anything else."""
     if isinstance(sample_type, str) and sample_type in _SAMPLE_TYPES:
@@ -935,6 +1012,23 @@ class Context(object):
         else:
             _check("rmgr_ssim_hip_enqueue_ssimf_win_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_win_grad(
                 self.handle, count, params_array, data_range, _window_ref(window), grad_out_dev_ptr, grad_a, grad_b))
+
+    def ssim3f_device(self, params_array, count, data_range):
+        """SSIM of `count` device-resident pairs of float32 volumes (a Params3F array) under the three-dimensional window through
+        rmgr_ssim_hip_compute_ssim3f_device: a float32 array."""
+        out = (ctypes.c_float * max(count, 1))()
+        _check("rmgr_ssim_hip_compute_ssim3f_device", self.lib.rmgr_ssim_hip_compute_ssim3f_device(self.handle, count, params_array, data_range, out))
+        return np.array(out[:count], np.float32)
+
+    def enqueue_ssim3f(self, params_array, count, data_range, sums_dev_ptr):
+        """rmgr_ssim_hip_enqueue_ssim3f: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        _check("rmgr_ssim_hip_enqueue_ssim3f", self.lib.rmgr_ssim_hip_enqueue_ssim3f(self.handle, count, params_array, data_range, sums_dev_ptr))
+
+    def enqueue_ssim3f_grad(self, params_array, count, data_range, grad_out_dev_ptr, grad_a=None, grad_b=None):
+        """rmgr_ssim_hip_enqueue_ssim3f_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes into the volumes the
+        Grad3F arrays grad_a / grad_b describe (None: not wanted), from `count` floats dLoss/dS_i in device memory; asynchronous, written
+        not accumulated."""
+        _check("rmgr_ssim_hip_enqueue_ssim3f_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_grad(self.handle, count, params_array, data_range, grad_out_dev_ptr, grad_a, grad_b))
 
     def ssimh_device(self, params_array, count, data_range, sample_type):
         """SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_ssimh_device: a

@@ -1,0 +1,322 @@
+// ssim3f_abi.cpp -- the entry points of the C ABI for float32 VOLUMES: SSIM under the three-dimensional window and its gradient
+// (rmgr_ssim_hip_*_ssim3f*).  The definition is in include/rmgr/ssim-hip.h, the kernels in ssim3f_kernels.hip.
+//
+// The flow is the one of ssim_samples_abi.cpp, written for three strides: validation before any device is touched, sub-batches under
+// kScratchCap of device scratch (cell partials, staged volumes and maps; the backward's coefficient volumes) with at least one volume
+// each, staging of host volumes, enqueue, strided map copy-back.  Every volume's sum runs over fixed cells in a fixed order and every
+// map and gradient voxel belongs to one fixed tile: neither the sub-batches nor the launch a volume lands in change a bit.
+//
+// It runs on the context's ring of descriptor tables, its cell partials and its pinned sums (sf_slots, sf_partials, sf_sums_pin), which
+// the 2-D families use as well, and on the coefficient scratch s3_coef: one stream, stream order.  An enqueue form never waits for the
+// host, except -- at most -- for the launch that read its ring slot kSfSlots enqueues ago.
+#include "ssim_context.h"
+#include "ssim3f_kernels.h"
+
+#include <cmath>
+
+using namespace ssim_host;
+
+namespace {
+
+using ssim_hip::Pair3FDesc;
+using ssim_hip::Grad3FDesc;
+using ssim_hip::Geometry3F;
+
+const uint64_t kScratchCap = uint64_t(1) << 30;     // device scratch of one sub-batch
+
+// ---- validation, before any device is touched -----------------------------------------------------------------------------------------------
+
+int validate3f(uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataRange, const void* out)
+{
+    if (!(dataRange > 0.0f) || !std::isfinite(dataRange)) return EINVAL;
+    if (count == 0 || params == NULL || out == NULL) return EINVAL;
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    if (W == 0 || H == 0 || D == 0 || W > ssim_hip::kS3MaxDim || H > ssim_hip::kS3MaxDim || D > ssim_hip::kS3MaxDim) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i) {
+        const rmgr_ssim_hip_Params3F& p = params[i];
+        if (p.width != W || p.height != H || p.depth != D) return EINVAL;
+        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
+        if (((uintptr_t)p.imgA.topLeft & 3u) || ((uintptr_t)p.imgB.topLeft & 3u) || ((uintptr_t)p.ssimMap & 3u)) return EINVAL;
+    }
+    if (ssim_hip::ssim3f_max_count(W, H, D) == 0) return EINVAL;
+    return 0;
+}
+
+int validate_grads3f(uint32_t count, const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)
+{
+    if (gradA == NULL && gradB == NULL) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const rmgr_ssim_hip_Grad3F* g = k ? gradB : gradA;
+            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 3u))) return EINVAL;
+        }
+    return 0;
+}
+
+// ---- descriptors, sub-batches and staging -----------------------------------------------------------------------------------------------------
+
+Pair3FDesc make_desc(const rmgr_ssim_hip_Params3F& p, bool with_map)
+{
+    Pair3FDesc d;
+    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride; d.a_slice = p.imgA.sliceStride;
+    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride; d.b_slice = p.imgB.sliceStride;
+    const bool m = with_map && p.ssimMap;
+    d.map = m ? p.ssimMap : NULL;
+    d.map_step = m ? p.ssimStep : 0;
+    d.map_stride = m ? p.ssimStride : 0;
+    d.map_slice = m ? p.ssimSliceStride : 0;
+    return d;
+}
+
+uint64_t round64(uint64_t bytes) { return (bytes + 63) & ~uint64_t(63); }
+
+// The bytes of the sample range of a volume; lo: where the range starts, in floats relative to topLeft (<= 0).
+size_t volume_bytes(const rmgr_ssim_hip_Img3F& im, uint32_t w, uint32_t h, uint32_t d, int64_t& lo)
+{
+    const int64_t ext[3] = {(int64_t)(w - 1) * (int64_t)im.step, (int64_t)(h - 1) * (int64_t)im.stride, (int64_t)(d - 1) * (int64_t)im.sliceStride};
+    int64_t hi = 0;
+    lo = 0;
+    for (int k = 0; k < 3; ++k) { if (ext[k] < 0) lo += ext[k]; else hi += ext[k]; }
+    return (size_t)(hi - lo + 1) * sizeof(float);
+}
+
+// Volumes of params[i0 ..] that one sub-batch takes: at least one; at most nmax (the launch limit) and, with `scratch` bytes per volume
+// and -- stage: host pointers -- the staged volumes and maps of each pair, kScratchCap of device scratch.  staged: the bytes its staged
+// volumes and maps take, each rounded up to 64.
+uint32_t take3f(const rmgr_ssim_hip_Params3F* params, uint32_t i0, uint32_t count, uint32_t nmax, uint64_t scratch, bool stage, uint64_t& staged)
+{
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    uint32_t n = 0;
+    staged = 0;
+    while (i0 + n < count && n < nmax) {
+        uint64_t bytes = 0;
+        if (stage) {
+            const rmgr_ssim_hip_Params3F& p = params[i0 + n];
+            int64_t lo;
+            bytes += round64(volume_bytes(p.imgA, W, H, D, lo)) + round64(volume_bytes(p.imgB, W, H, D, lo));
+            if (p.ssimMap) bytes += round64((uint64_t)W * H * D * 4);
+        }
+        if (n > 0 && scratch * (n + 1) + staged + bytes > kScratchCap) break;
+        staged += bytes;
+        ++n;
+    }
+    return n;
+}
+
+// One launch that reads a table of `bytes` from the next slot of the context's ring (ssim_samples_abi.cpp: ring_launch).
+template <typename Fill, typename Launch>
+int ring_launch(rmgr_ssim_hip_Context* c, size_t bytes, Fill fill, Launch launch)
+{
+    rmgr_ssim_hip_Context_::SfSlot& s = c->sf_slots[c->sf_next];
+    c->sf_next = (c->sf_next + 1) % rmgr_ssim_hip_Context_::kSfSlots;
+    if (s.pending) {
+        HIP_TRY(hipEventSynchronize(s.used));
+        s.pending = false;
+    }
+    HIP_TRY(s.used.ensure());
+    int rc;
+    if ((rc = s.pin.grow(bytes))) return rc;
+    if ((rc = s.dev.grow(bytes))) return rc;
+    fill(s.pin.get());
+    HIP_TRY(hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch(const_cast<const uint8_t*>(s.dev.get())));
+    HIP_TRY(hipEventRecord(s.used, c->stream));
+    s.pending = true;
+    return 0;
+}
+
+// ---- the forward flow -----------------------------------------------------------------------------------------------------------------------------
+
+uint64_t partials_per_volume(uint32_t W, uint32_t H, uint32_t D) { return ssim_hip::plan3f(W, H, D, 1, 0).cells_per_volume() * sizeof(double); }
+
+// Enqueues n pairs (descriptors in host memory, volumes on the device): descriptor upload, walk, reduction into sums[0 .. n-1].
+int enqueue_volumes(rmgr_ssim_hip_Context* c, float range, uint32_t n, const Pair3FDesc* d, uint32_t W, uint32_t H, uint32_t D, double* sums)
+{
+    const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+    int rc;
+    if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_volume() * n)))) return rc;
+    return ring_launch(c, n * sizeof(Pair3FDesc),
+        [&](uint8_t* pin) { memcpy(pin, d, n * sizeof(Pair3FDesc)); },
+        [&](const uint8_t* dev) { return ssim_hip::launch_ssim3f(geo, reinterpret_cast<const Pair3FDesc*>(dev), range, c->sf_partials, sums, c->stream); });
+}
+
+int enqueue_all(rmgr_ssim_hip_Context* c, float range, uint32_t count, const rmgr_ssim_hip_Params3F* params, double* sums)
+{
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    try {
+        std::vector<Pair3FDesc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), partials_per_volume(W, H, D), false, staged);
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) d[i] = make_desc(params[i0 + i], true);
+            const int rc = enqueue_volumes(c, range, n, &d[0], W, H, D, sums + i0);
+            if (rc) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+// Copies a dense W x H x D map in device memory to the caller's map at its own step, stride and sliceStride (blocking).
+int copy_map_back(const float* src, const rmgr_ssim_hip_Params3F& p, std::vector<float>& back)
+{
+    const uint32_t W = p.width, H = p.height, D = p.depth;
+    const size_t n = (size_t)W * H * D;
+    if (p.ssimStep == 1 && p.ssimStride == (ptrdiff_t)W && p.ssimSliceStride == (ptrdiff_t)W * (ptrdiff_t)H) {
+        HIP_TRY(hipMemcpy(p.ssimMap, src, n * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    back.resize(n);
+    HIP_TRY(hipMemcpy(&back[0], src, n * 4, hipMemcpyDeviceToHost));
+    for (uint32_t z = 0; z < D; ++z)
+        for (uint32_t y = 0; y < H; ++y) {
+            float* row = p.ssimMap + (ptrdiff_t)z * p.ssimSliceStride + (ptrdiff_t)y * p.ssimStride;
+            const float* s = &back[((size_t)z * H + y) * W];
+            for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = s[x];
+        }
+    return 0;
+}
+
+// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the volumes are copied (each
+// volume's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own strides.
+int blocking(rmgr_ssim_hip_Context* c, float range, uint32_t count, const rmgr_ssim_hip_Params3F* params, float* ssim, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    const double voxels = (double)W * (double)H * (double)D;
+    int rc;
+    if ((rc = c->sf_sums_pin.grow(count))) return rc;
+    try {
+        std::vector<Pair3FDesc> d;
+        std::vector<uint64_t> map_off;
+        std::vector<float> back;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), partials_per_volume(W, H, D), stage, staged);
+            d.resize(n);
+            map_off.assign(n, 0);
+            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
+            uint64_t off = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                const rmgr_ssim_hip_Params3F& p = params[i0 + i];
+                d[i] = make_desc(p, true);
+                if (!stage) continue;
+                for (int k = 0; k < 2; ++k) {
+                    const rmgr_ssim_hip_Img3F& im = k ? p.imgB : p.imgA;
+                    int64_t lo;
+                    const size_t bytes = volume_bytes(im, W, H, D, lo);
+                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
+                    (k ? d[i].b : d[i].a) = reinterpret_cast<const float*>(c->stage_a + off) - lo;
+                    off += round64(bytes);
+                }
+                if (p.ssimMap) {
+                    map_off[i] = off;
+                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
+                    d[i].map_step = 1; d[i].map_stride = W; d[i].map_slice = (int64_t)W * H;
+                    off += round64((uint64_t)W * H * D * 4);
+                }
+            }
+            if ((rc = enqueue_volumes(c, range, n, &d[0], W, H, D, c->sf_sums_pin + i0))) return rc;
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (uint32_t i = 0; i < n && stage; ++i) {
+                const rmgr_ssim_hip_Params3F& p = params[i0 + i];
+                if (!p.ssimMap) continue;
+                if ((rc = copy_map_back(reinterpret_cast<const float*>(c->stage_a + map_off[i]), p, back))) return rc;
+            }
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->sf_sums_pin[i] / voxels);
+    return 0;
+}
+
+// ---- the gradient ---------------------------------------------------------------------------------------------------------------------------------
+// Per sub-batch: the walk that writes the coefficient volumes (3 floats per voxel for one gradient, 4 for both) into c->s3_coef, then the
+// adjoint walk that reads them.  The next sub-batch rewrites the scratch in stream order.
+int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float range, const float* gradOutDevice,
+               const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)
+{
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
+    const uint64_t per_volume = (uint64_t)ssim_hip::ssim3f_coef_planes(which) * W * H * D;
+    for (uint32_t i0 = 0; i0 < count;) {
+        uint64_t staged;
+        const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), per_volume * sizeof(float), false, staged);
+        const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+        int rc;
+        if ((rc = c->s3_coef.grow((size_t)(per_volume * n)))) return rc;
+        const size_t pair_bytes = n * sizeof(Pair3FDesc);
+        rc = ring_launch(c, pair_bytes + n * sizeof(Grad3FDesc),
+            [&](uint8_t* pin) {
+                Pair3FDesc* pd = reinterpret_cast<Pair3FDesc*>(pin);
+                Grad3FDesc* gd = reinterpret_cast<Grad3FDesc*>(pin + pair_bytes);
+                for (uint32_t i = 0; i < n; ++i) {
+                    pd[i] = make_desc(params[i0 + i], false);
+                    Grad3FDesc g = {NULL, 0, 0, 0, NULL, 0, 0, 0};
+                    if (gradA) { const rmgr_ssim_hip_Grad3F& s = gradA[i0 + i]; g.ga = s.topLeft; g.ga_step = s.step; g.ga_stride = s.stride; g.ga_slice = s.sliceStride; }
+                    if (gradB) { const rmgr_ssim_hip_Grad3F& s = gradB[i0 + i]; g.gb = s.topLeft; g.gb_step = s.step; g.gb_stride = s.stride; g.gb_slice = s.sliceStride; }
+                    gd[i] = g;
+                }
+            },
+            [&](const uint8_t* dev) {
+                return ssim_hip::launch_ssim3f_grad(geo, reinterpret_cast<const Pair3FDesc*>(dev), reinterpret_cast<const Grad3FDesc*>(dev + pair_bytes),
+                                                    gradOutDevice + i0, range, which, c->s3_coef, c->stream);
+            });
+        if (rc) return rc;
+        i0 += n;
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                          float dataRange, double* sumsDevice) RMGR_NOEXCEPT
+{
+    const int rc = validate3f(count, params, dataRange, sumsDevice);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, dataRange, count, params, sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                 float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = validate3f(count, params, dataRange, ssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, dataRange, count, params, ssim, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                               float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    int rc = validate3f(count, params, dataRange, ssim);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    USE_DEVICE(lease.c);
+    return blocking(lease.c, dataRange, count, params, ssim, true);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                               float dataRange, const float* gradOutDevice,
+                                               const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT
+{
+    int rc = validate3f(count, params, dataRange, gradOutDevice);
+    if (rc) return rc;
+    if ((rc = validate_grads3f(count, gradA, gradB))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return grad_entry(c, count, params, dataRange, gradOutDevice, gradA, gradB);
+}
+
+} // extern "C"

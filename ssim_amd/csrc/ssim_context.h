@@ -1,6 +1,6 @@
 // ssim_context.h -- internal to the C ABI (include/rmgr/ssim-hip.h): the context, the resources it owns, and what the host-layer
 // files share.  ssim_context.cpp creates and destroys contexts and keeps the default pool; ssim_hip_abi.cpp holds the entry points
-// of 8-bit samples, ssim_samples_abi.cpp those of 16-bit, float32 and float16 / bfloat16 samples; ssim_comm.cpp the RCCL all-reduce;
+// of 8-bit samples, ssim_samples_abi.cpp those of 16-bit, float32 and float16 / bfloat16 samples, ssim3f_abi.cpp those of float32 volumes; ssim_comm.cpp the RCCL all-reduce;
 // ssim_tune.cpp profiling and tuning.  Not installed.
 #ifndef SSIM_AMD_CONTEXT_H
 #define SSIM_AMD_CONTEXT_H
@@ -200,6 +200,9 @@ struct rmgr_ssim_hip_Context_ {
     DeviceBuffer<float>    msf_pyramid, msf_grads, msf_coef;
     DeviceBuffer<double>   msf_partials, msf_out;
     PinnedBuffer<double>   msf_out_pin;
+    // SSIM of float32 volumes (rmgr_ssim_hip_*_ssim3f*, ssim3f_abi.cpp): the backward's coefficient volumes, rewritten by every sub-batch in
+    // stream order.  Descriptor tables, cell partials and pinned sums are sf_slots, sf_partials and sf_sums_pin.
+    DeviceBuffer<float>    s3_coef;
 
     // Every grow-only staging buffer above, once: what context_held counts and context_trim gives back.
     template <typename F> void for_each_staging(F f)
@@ -213,6 +216,7 @@ struct rmgr_ssim_hip_Context_ {
         for (SfSlot& s : sf_slots) { f(s.dev); f(s.pin); }
         f(sf_partials); f(sf_sums_pin);
         f(msf_pyramid); f(msf_grads); f(msf_coef); f(msf_partials); f(msf_out); f(msf_out_pin);
+        f(s3_coef);
     }
 
     bool profiling = false;

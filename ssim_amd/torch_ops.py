@@ -49,6 +49,12 @@ fixed window for now: a non-default window with 16-bit tensors is a TypeError.
 
     photo = 0.85 * (1 - ssim_map(warped, target, win_size=3, window="uniform")) / 2 + 0.15 * (warped - target).abs()
 
+Volumes.  ssim3d(x, y, data_range) and SSIM3DLoss take (..., D, H, W) float32 tensors and apply the window over x, y and z
+(rmgr_ssim_hip_enqueue_ssim3f, _ssim3f_grad): the 3-D SSIM of pytorch-msssim (spatial_dims=3), torchmetrics, MONAI and skimage.  ssim() on
+a 5-D tensor keeps its meaning -- one 2-D SSIM per slice --; the end of this file has the rest.
+
+    loss = SSIM3DLoss()(x, y)                                       # x, y: (N, C, D, H, W) float32 on the GPU
+
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
 import ctypes
@@ -472,4 +478,142 @@ class MSSSIMLoss(object):
 
     def __call__(self, x, y):
         loss = 1.0 - ms_ssim_amp(x, y, self.data_range, self.scales, self.weights)
+        return loss.mean() if self.reduction == "mean" else loss
+
+
+# ---- volumes: SSIM under the three-dimensional window -----------------------------------------------------------------------------------
+# ssim3d(x, y, data_range) is the per-volume mean of the definition in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssim3f): the 11-tap
+# Gaussian over x, y AND z, what pytorch-msssim (spatial_dims=3), torchmetrics (5-D input), MONAI (SSIMLoss(spatial_dims=3)) and skimage
+# (n-D arrays) compute for volumes.  It has a name of its own because ssim() on an (N, C, D, H, W) tensor already has a meaning: N * C * D
+# independent 2-D SSIMs with no window across slices.  The backward is rmgr_ssim_hip_enqueue_ssim3f_grad.  float32 only for now; the
+# configurable window, 16-bit tensors, a multi-scale form and a per-voxel map are follow-ups.
+
+_function3d = None
+
+
+def _check3d(x, y, data_range):
+    """The documented errors of ssim3d, before any GPU call.  Returns data_range as a float."""
+    import torch
+    if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
+        raise TypeError("ssim3d: x and y must be torch tensors")
+    if x.dtype in (torch.float16, torch.bfloat16) or y.dtype in (torch.float16, torch.bfloat16):
+        raise TypeError("ssim3d: the 3-D path is float32 for now, got %s and %s" % (x.dtype, y.dtype))
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise TypeError("ssim3d: float32 tensors expected, got %s and %s" % (x.dtype, y.dtype))
+    if x.dim() < 3:
+        raise ValueError("ssim3d: tensors of shape (..., D, H, W) expected, got %d dimension(s)" % x.dim())
+    if x.shape != y.shape:
+        raise ValueError("ssim3d: shapes differ: %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    if not x.is_cuda or not y.is_cuda:
+        raise ValueError("ssim3d: the tensors must be on a GPU (there is no CPU path)")
+    if x.device != y.device:
+        raise ValueError("ssim3d: the tensors are on different devices: %s and %s" % (x.device, y.device))
+    if x.shape[-1] == 0 or x.shape[-2] == 0 or x.shape[-3] == 0:
+        raise ValueError("ssim3d: empty volumes: %s" % (tuple(x.shape),))
+    r = float(data_range)
+    if not (r > 0.0) or math.isinf(r):
+        raise ValueError("ssim3d: data_range must be finite and > 0, got %r" % (data_range,))
+    return r
+
+
+def _volume_offsets(t):
+    """Element offset of every (D, H, W) volume of t from t.data_ptr(), in the order of t.reshape(-1, D, H, W)."""
+    offs = [0]
+    for size, stride in zip(t.shape[:-3], t.stride()[:-3]):
+        offs = [o + i * stride for o in offs for i in range(size)]
+    return offs
+
+
+def _params3d(x, y):
+    d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
+    ox, oy = _volume_offsets(x), _volume_offsets(y)
+    n = len(ox)
+    params = (api.Params3F * max(n, 1))()
+    px, py = x.data_ptr(), y.data_ptr()
+    sx, sy = (x.stride(-1), x.stride(-2), x.stride(-3)), (y.stride(-1), y.stride(-2), y.stride(-3))
+    for i in range(n):
+        params[i] = api.make_params3f(w, h, d, px + 4 * ox[i], sx, py + 4 * oy[i], sy)
+    return params, n
+
+
+def _grad_volumes(g, n, d, h, w):
+    """Grad3F array over the n contiguous volumes of the float32 tensor g."""
+    arr = (api.Grad3F * max(n, 1))()
+    base = g.data_ptr()
+    for i in range(n):
+        arr[i] = api.Grad3F(base + 4 * i * d * h * w, 1, w, w * h)
+    return arr
+
+
+def _make_function3d():
+    import torch
+
+    class _SSIM3D(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, data_range):
+            lead, d, h, w = x.shape[:-3], x.shape[-3], x.shape[-2], x.shape[-1]
+            params, n = _params3d(x, y)
+            sums = torch.empty(n, dtype=torch.float64, device=x.device)
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr())
+                if work is not cur:
+                    cur.wait_stream(work)
+            ctx.save_for_backward(x, y)
+            ctx.data_range = data_range
+            return (sums / (float(w) * float(h) * float(d))).to(torch.float32).reshape(lead)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            x, y = ctx.saved_tensors
+            d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
+            want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_x or want_y):
+                return None, None, None
+            params, n = _params3d(x, y)
+            g = grad_out.to(torch.float32).reshape(-1).contiguous()
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None
+            gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                ga = _grad_volumes(gx, n, d, h, w) if want_x else None
+                gb = _grad_volumes(gy, n, d, h, w) if want_y else None
+                _context(x.device, work).enqueue_ssim3f_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb)
+                if work is not cur:
+                    cur.wait_stream(work)
+            return gx, gy, None
+
+    return _SSIM3D
+
+
+def ssim3d(x, y, data_range=1.0):
+    """Per-volume SSIM of two float32 GPU tensors of identical shape (..., D, H, W) under the three-dimensional 11-tap Gaussian window
+    (sigma 1.5, clamped edges on every axis), any strides (each volume is addressed in place, no copy): a float32 tensor of shape
+    x.shape[:-3].  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that need it.  It runs on
+    torch's current stream through the cached context, as ssim() does.  TypeError: not tensors, float16 / bfloat16 tensors (the 3-D path
+    is float32 for now), any other dtype.  ValueError: CPU tensors, differing shapes or devices, fewer than 3 dimensions, empty volumes, a
+    data_range that is not finite and > 0.  Not ssim() on a 5-D tensor: that is one 2-D SSIM per slice."""
+    global _function3d
+    r = _check3d(x, y, data_range)
+    if _function3d is None:
+        _function3d = _make_function3d()
+    return _function3d.apply(x, y, r)
+
+
+class SSIM3DLoss(object):
+    """1 - ssim3d(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per volume).  A plain callable: it has no
+    parameters."""
+
+    def __init__(self, data_range=1.0, reduction="mean"):
+        if reduction not in ("mean", "none"):
+            raise ValueError("SSIM3DLoss: reduction must be 'mean' or 'none', got %r" % (reduction,))
+        self.data_range, self.reduction = data_range, reduction
+
+    def __call__(self, x, y):
+        loss = 1.0 - ssim3d(x, y, self.data_range)
         return loss.mean() if self.reduction == "mean" else loss
