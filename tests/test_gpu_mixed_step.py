@@ -1,10 +1,10 @@
 """GPU: one training step's mix of SSIM calls on ONE context, held to each call alone.
 
-Why.  Every sample family (ssim16, ssimf, the windowed ssimf, ssimh, msssimf, msssimh and their gradients) takes its descriptor tables from
+Why.  Every sample family (ssim16, ssimf, the windowed ssimf, ssimh, msssimf, msssimh, the volume family ssim3f and their gradients) takes its descriptor tables from
 one ring of 8 slots, writes its cell partials into one buffer and -- the two multi-scale families -- rebuilds its pyramid, its coarse
 gradient planes and its coefficients in one set of grow-only buffers whose grow() frees before it allocates (ssim_context.h: "Every family
 shares them: one stream, stream order").  The other modules drive one family at a time with a synchronise after every call or two.  Here a
-sequence of 54 enqueues of every asynchronous sample entry, forwards and backwards, of four shapes and 1 .. 8 pairs, goes onto one context
+sequence of 61 enqueues of every asynchronous sample entry, forwards and backwards, of four shapes and 1 .. 8 pairs and of two volume shapes, goes onto one context
 back to back without a host wait; one synchronise and one read-back follow.
 
 What is asserted.  Every byte of every output buffer of the sequence -- fp64 sums, maps, values, per-scale means, gradient planes, the
@@ -12,7 +12,7 @@ sentinel gaps of interleaved planes and the sentinel elements around every fp64 
 same pixels in the same layouts, leaves when it is issued ALONE on a second context that is synchronised after every op.  No tolerance:
 both sides run the same kernels on the same pixels.  So that "the same wrong bits on both sides" is excluded, the lone results of at least
 one pair per family are held to the float64 models at the bounds the families' own modules assert (ssim16_model, ssimf_model, ssimw_model,
-ssimk_model.tolerances, msssimf_model; the 16-bit encodings: the bits of the float32 entries on the planes widened by halfmodel, rounded
+ssimk_model.tolerances, msssimf_model, ssim3f_model.tolerances; the 16-bit encodings: the bits of the float32 entries on the planes widened by halfmodel, rounded
 once for the gradients).  No bound is new.
 
 The sequence (Sequence.build).  Sizes are W x H: 33 x 17 with 1 to 3 pairs, 130 x 19 (two strip columns, map rows of 520 bytes: no
@@ -21,7 +21,11 @@ regrow every shared buffer after smaller launches used it and keep the stream bu
 enqueue_batch of two golden fixtures shares only the stream.  Every multi-scale forward F whose means a backward consumes is followed,
 BEFORE that backward, by a forward of other pairs of the same shape and count, one of the same family at another shape and one of the
 other multi-scale family at F's shape and count: the backward must rebuild its own pyramid.  ssimf of one 33 x 17 pair is issued twice,
-first and last, into different outputs: the same bits.
+first and last, into different outputs: the same bits.  The volume family (W x H x D) shares the ring and the cell partials and adds a
+coefficient scratch of its own: enqueue_ssim3f with maps (dense, and two floats apart) and enqueue_ssim3f_grad for both gradients and for
+one, on 3 pairs and on 1 pair of 33 x 20 x 13 and on 2 pairs of 65 x 63 x 40, which regrow the cell partials and the coefficient scratch after
+smaller work; the backward of the 3 pairs follows a 2-D launch of more cells than its forward has (a gradient enqueue puts two tables in
+one ring slot).
 
 Orders: ascending size (every shared buffer is regrown while earlier work is queued), descending size (small launches run in scratch
 that holds a larger launch's partials, pyramid and gradient planes) and a seeded shuffle; all three keep every op after the ops it names
@@ -32,8 +36,8 @@ streams of their own.
 After a return code that is neither success nor EINVAL the module starts nothing more on the GPU (test_gpu_ssimk's _device_error, shared
 with that module).  Every test frees its own buffers.  The module prints its wall time and its peak device memory when it ends.
 
-Cost, measured on an MI355X: the 9 tests take 3.4 s together (2.9 s of it the torch child process), no test more than 0.1 s of its own;
-the device holds 84 MiB more than before the module at the peak.
+Cost, measured on an MI355X: the 9 tests take 4.3 s together (3.1 s of it the torch child process, 0.5 s the lone calls and their float64
+models), no test more than 0.1 s of its own; the device holds 96 MiB more than before the module at the peak.
 """
 import json
 import os
@@ -49,12 +53,14 @@ import halfmodel as HM
 import msssimf_model as MS
 import sample_forms_inputs as IN
 import ssim16_model as M16
+import ssim3f_model as S3
 import ssimf_model as MF
 import ssimk_model as K
 import ssimw_model as MW
 import ssim_amd
 from conftest import ROOT, load_pair
 from test_gpu_ssim16 import G_TOL as G16_TOL, PX_TOL as PX16_TOL
+from test_gpu_ssim3f import random_pair as random_volumes
 from test_gpu_ssimk import _device_error, mk
 from test_gpu_ssimw import FILL16, FILL32, Plane
 
@@ -67,6 +73,7 @@ GOLDEN = ("bbb257x65_q50_ch1", "bbb257x65_q00_ch1")
 WIN7U, WIN5G = (7, 0.0, "uniform"), (5, 0.8, "gaussian")                       # two of ssimk_model.WINDOWS
 MS5, MS3 = (5, None), (3, (0.2, 0.3, 0.5))                                      # Wang's five; three scales, weights of its own
 DENSE, WIDE3, BACK, BACK2 = (1, False), (3, False), (1, True), (2, True)       # (step, flip) of test_gpu_ssimw.Plane
+VOL, VOLBIG = (33, 20, 13), (65, 63, 40)                                       # W x H x D of the volume ops
 SHUFFLE_SEED = 20261019
 assert WIN7U in K.WINDOWS and WIN5G in K.WINDOWS
 
@@ -103,6 +110,14 @@ def pairs_h(shape, n, salt, enc):
         rng = _rng(shape, salt)
         got = [IN.random_pair_h(shape[0], shape[1], rng, enc) for _ in range(n)]
         _inputs[key] = ([u for u, _ in got], [f for _, f in got])
+    return _inputs[key]
+
+
+def pairs_3f(size, n, salt):
+    """n float32 pairs of volumes in [0, 1], (D, H, W) arrays (test_gpu_ssim3f.random_pair)."""
+    key = ("3f", size, n, salt)
+    if key not in _inputs:
+        _inputs[key] = [random_volumes(size, IN.SEED + 1000 * salt + i) for i in range(n)]
     return _inputs[key]
 
 
@@ -148,6 +163,19 @@ class PlaneOut(Out):
     def plane(self, host):
         p = host[:, :, self.lay[0] - 1]
         return np.ascontiguousarray(p[::-1, ::-1] if self.lay[1] else p)
+
+
+class VolOut(Out):
+    """A D x H x W output volume: samples `step` floats apart with sentinels between them."""
+
+    def __init__(self, mem, name, d, h, w, step=1):
+        owned = np.zeros((d, h, w, step), bool)
+        owned[..., step - 1] = True
+        Out.__init__(self, mem, name, np.full((d, h, w, step), FILL32, np.float32), owned, ptr_offset=4 * (step - 1))
+        self.strides = (step, step * w, step * w * h)            # step, stride, sliceStride
+
+    def plane(self, host):
+        return np.ascontiguousarray(host[..., -1])
 
 
 class VecOut(Out):
@@ -366,6 +394,50 @@ class Sequence(object):
             other_family = self.ms_forward(tag + ".family", pairs_h((h, w), n, 900 + len(self.ops), HM.BF16)[0], MS3, HM.BF16, after=[f])
         return f, self.ms_backward(tag + ".grad", f, which, [same_shape, at_other_shape, other_family], glay)
 
+    # -- the volume family: the ring, the cell partials and a coefficient scratch of its own --
+
+    def vol_forward(self, name, pairs, maps=None, step=1, after=()):
+        """enqueue_ssim3f of `pairs` ((D, H, W) arrays, dense in device memory); maps: the pairs that get a map (None: all), `step`
+        floats apart."""
+        mem, n, (d, h, w) = self.mem, len(pairs), pairs[0][0].shape
+        ps = (ssim_amd.Params3F * n)()
+        keep, outs = [], []
+        for i, (a, b) in enumerate(pairs):
+            da, db = mem.upload(a), mem.upload(b)
+            keep += [da, db]
+            m = None
+            if maps is None or i in maps:
+                m = VolOut(mem, "map%d" % i, d, h, w, step)
+                outs.append(m)
+            ps[i] = ssim_amd.make_params3f(w, h, d, da.ptr, (1, w, w * h), db.ptr, (1, w, w * h), m.ptr if m else None, m.strides if m else None)
+        sums = VecOut(mem, "sums", n)
+        outs.append(sums)
+        note = "depth %d, %d maps, step %d" % (d, len(outs) - 1, step)
+        op = self.add(Op(name, "enqueue_ssim3f", (h, w), n, note, lambda ctx: ctx.enqueue_ssim3f(ps, n, RANGE, sums.ptr), outs, keep, after))
+        op.kind, op.params, op.pairs, op.depth = "3f", ps, pairs, d
+        op.size *= d
+        return op
+
+    def vol_backward(self, name, f, which=3, step=1, after=()):
+        """enqueue_ssim3f_grad of the volume forward f's pairs, after f and the ops of `after`."""
+        mem, n, (h, w), d = self.mem, f.n, f.shape, f.depth
+        arrs, outs = [None, None], []
+        for k in range(2):
+            if which & (1 << k):
+                arrs[k] = (ssim_amd.Grad3F * n)()
+                for i in range(n):
+                    g = VolOut(mem, "d%s%d" % ("AB"[k], i), d, h, w, step)
+                    outs.append(g)
+                    arrs[k][i] = ssim_amd.Grad3F(g.ptr, *g.strides)
+        g_out = np.float32([IN.G_OUT * (1.0 + 0.5 * i) for i in range(n)])
+        go = mem.upload(g_out)
+        note = "of %s, %s, depth %d, step %d" % (f.name, ("dA", "dB", "dA dB")[which - 1], d, step)
+        op = self.add(Op(name, "enqueue_ssim3f_grad", (h, w), n, note,
+                         lambda ctx: ctx.enqueue_ssim3f_grad(f.params, n, RANGE, go.ptr, arrs[0], arrs[1]), outs, [go], [f] + list(after)))
+        op.of, op.which, op.up = f, which, g_out
+        op.size *= d
+        return op
+
     # -- the uint8 engine: shares only the stream --
 
     def batch8(self, name):
@@ -426,6 +498,15 @@ class Sequence(object):
         self.ms_group("msf.big", pairs_f(BIG, 4, 16), pairs_f(BIG, 4, 17), MS5, which=3)
         self.ms_group("msh.f16.twocol", pairs_h(TWOCOL, 2, 18, F16)[0], pairs_h(TWOCOL, 2, 19, F16)[0], MS3, which=2, enc=F16)
         self.ms_group("msh.bf16.small", pairs_h(SMALL, 3, 20, BF16)[0], pairs_h(SMALL, 3, 21, BF16)[0], MS3, which=3, enc=BF16, lay=WIDE3, glay=BACK)
+        # the volume family: 33 x 20 x 13 with 3 pairs and with 1, and 2 pairs of 65 x 63 x 40, which regrow the cell partials and the
+        # coefficient scratch after the smaller volumes; between vol.small and its backward a 2-D launch of more cells than vol.small has
+        v_small = self.vol_forward("vol.small", pairs_3f(VOL, 3, 22))
+        regrow = self.forward("ssimf.regrow", "f", pairs_f(GOLD, 1, 23), after=[v_small])
+        v_one = self.vol_forward("vol.one", pairs_3f(VOL, 1, 24), step=2)
+        v_big = self.vol_forward("vol.big", pairs_3f(VOLBIG, 2, 25), maps=(1,))
+        self.vol_backward("vol.small.g", v_small, after=[regrow])
+        self.vol_backward("vol.one.g", v_one, which=2, step=2)
+        self.vol_backward("vol.big.g", v_big, which=1)
         self.batch8("batch8")
         last = self.forward("ssimf.last", "f", pairs_f(SMALL, 1, 1), planes_of=first)
         self.twins = (first, last)
@@ -582,7 +663,7 @@ def _outs(seq, lone, name):
     op, res = seq.by_name[name], {}
     for o in op.outs:
         host = np.frombuffer(lone[name][o.name], o.init.dtype).reshape(o.init.shape)
-        res[o.name] = o.plane(host) if isinstance(o, PlaneOut) else o.vec(host)
+        res[o.name] = o.plane(host) if isinstance(o, (PlaneOut, VolOut)) else o.vec(host)
     return op, res
 
 
@@ -600,7 +681,7 @@ def _alone(ctx, seq, build):
         for op in seq.ops[n0:]:
             op.issue(ctx)
             _sync(ctx)
-            res.append(dict((o.name, o.plane(o.read()) if isinstance(o, PlaneOut) else o.vec(o.read())) for o in op.outs))
+            res.append(dict((o.name, o.plane(o.read()) if isinstance(o, (PlaneOut, VolOut)) else o.vec(o.read())) for o in op.outs))
         return res
     finally:
         for op in seq.ops[n0:]:
@@ -702,6 +783,22 @@ def hold_to_the_models(ctx, seq, lone):
         for key in rg:
             assert HM.same(rg[key], HM.round_to(wg[key], op.enc), op.enc) and (rg[key] & 0x7FFF).max() > 0, (fname, key)
         print("%s.grad alone: the bits of the float32 gradient on the widened planes, rounded once" % fname)
+    # the volumes: value, map and gradients of one pair per op against the float64 model (tests/ssim3f_model.py)
+    px_tol, g_tol, grad_tol, _ = S3.tolerances()
+    for fname, i in (("vol.small", 2), ("vol.one", 0), ("vol.big", 1)):
+        op, r = _outs(seq, lone, fname)
+        g, rg = _outs(seq, lone, fname + ".g")
+        a, b = op.pairs[i]
+        gv, gm = S3.ssim(a, b, RANGE)
+        e_px, e_g = float(np.abs(r["map%d" % i].astype(np.float64) - gm).max()), abs(float(r["sums"][i]) / S3.voxels(a.shape) - gv)
+        print("%s alone, pair %d: per voxel %.3g (bound %.3g), global %.3g (bound %.3g)" % (fname, i, e_px, px_tol, e_g, g_tol))
+        assert np.all(np.isfinite(r["map%d" % i])) and e_px <= px_tol and e_g <= g_tol, fname
+        want = S3.grad(a, b, RANGE, float(g.up[i]))
+        for k in range(2):
+            if g.which & (1 << k):
+                e = _rel(rg["d%s%d" % ("AB"[k], i)], want[k])
+                print("%s.g alone, pair %d, d%s: %.3g of max|grad| (bound %.3g)" % (fname, i, "AB"[k], e, grad_tol))
+                assert e <= grad_tol, (fname, k, e)
     # the uint8 batch: the committed golden values
     op, r = _outs(seq, lone, "batch8")
     for i, name in enumerate(GOLDEN):
