@@ -34,6 +34,8 @@
  *                                      gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim3f, rmgr_ssim_hip_compute_ssim3f_device / _host, rmgr_ssim_hip_enqueue_ssim3f_grad   SSIM of float32
  *                                      VOLUMES (three-dimensional window) and its gradient: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssim3f_map_grad      gradient of the 3-D SSIM MAP for a per-voxel upstream gradient: no reference
+ *                                      counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -823,8 +825,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* ctx
  *         dataRange that is not finite or not > 0; a volume, map or gradient pointer that is not 4-byte aligned; a NULL ctx for anything
  *         but _host -- all checked before any device is touched.  ENODEV: no device.
  *
- * Follow-ups, not in this interface: a caller-chosen window (the _win entries), float16 / bfloat16 volumes, multi-scale SSIM of volumes
- * and a per-voxel upstream gradient.
+ * Follow-ups, not in this interface: a caller-chosen window (the _win entries), float16 / bfloat16 volumes and multi-scale SSIM of
+ * volumes.
  */
 typedef struct rmgr_ssim_hip_Img3F {
     const float* topLeft;
@@ -849,6 +851,49 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_host(rmgr_ssim_hip_Context* ctx, rmgr_
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                                float dataRange, const float* gradOutDevice,
                                                const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
+
+/*
+ * Gradient of the 3-D SSIM map: dLoss/da and dLoss/db of `count` pairs of float32 volumes for an upstream gradient given PER VOXEL (SSIM
+ * inside a brain or body mask, validity or saliency weights of a spatio-temporal loss, a per-voxel combination with L1 -- any loss that
+ * is a function of the map rmgr_ssim_hip_enqueue_ssim3f writes through params[i].ssimMap, not of its plain mean).  No reference
+ * counterpart: tests/ssim3w_model.py restates it in float64.  Additions only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ * It is the definition of rmgr_ssim_hip_enqueue_ssim3f_grad with ONE change:
+ *   Input    per pair a float32 volume gMap_i(p) = dLoss/dssim_i(p) in place of the scalar gOut[i]: k(p) = gMap_i(p).  There is no
+ *            division by W H D.
+ *   Gradient  dLoss/da = Gt(k d_mu) + 2 a Gt(k d_aa) + b Gt(k d_ab) with k INSIDE Gt (it multiplies d_* at the voxel p of the map, before
+ *            the adjoint spreads them);  dLoss/db: the same with a and b exchanged.
+ *   Everything else is ssim3f's, word for word: samples, dataRange and the constants, the window G over x, y and z, the clamped edges on
+ *            all three axes and their adjoint Gt, ONE centre per volume, d_mu, d_aa, d_ab in the centred variables, the summation
+ *            orders, one writer per gradient voxel and no floating-point atomics, and the scratch: the first walk stores k d_mu, k d_aa,
+ *            k d_ab -- 12 bytes per voxel for one gradient, 16 for both -- into the context's scratch, which it shares with
+ *            _enqueue_ssim3f_grad in stream order, and a batch runs in sub-batches of about 1 GB of it, at least one volume each.
+ *   Products  k(p) d(p) is a plain fp32 product.  A zero weight does not hide a NaN or Inf in the images: 0 * NaN is NaN.  Mask such
+ *            samples out of the volumes, not only out of gMap.
+ *   Reach    a NaN in gMap at p makes NaN exactly the 11 x 11 x 11 gradient voxels around p, clipped to the volume; a NaN sample reaches
+ *            21 x 21 x 21 as before.
+ *   Identity  for a volume gMap_i whose every element is the float  float(double(gOut[i]) / (double(W) * double(H) * double(D)))  the
+ *            gradients have the BITS rmgr_ssim_hip_enqueue_ssim3f_grad stores for gOut[i].
+ *   Determinism  as for ssim3f, extended to views of gMap: the same bits alone or anywhere in a batch, at any z-chunk depth and after
+ *            any sub-batch split, on every call, with one gradient or both, and for any view (negative, permuted, interleaved or zero
+ *            strides) of the samples, of gMap or of the gradient volumes compared with the same voxels stored densely.
+ *
+ * gradOutMaps: an array of count rmgr_ssim_hip_GradOut3F in HOST memory, each describing a volume in DEVICE memory: gMap_i(x, y, z) is
+ *            topLeft[x * step + y * stride + z * sliceStride], in floats, negatives and 0 included, every offset a 64-bit product -- with
+ *            all three 0 one float stands for the whole volume (what a framework hands over as the expanded gradient of a sum).
+ * gradA / gradB: as for _enqueue_ssim3f_grad (either may be NULL, not both).  Gradients are WRITTEN, not accumulated.  A gradient volume
+ *            must not overlap an input volume, a gMap volume or another gradient volume: this is not checked.  params[i].ssimMap is
+ *            ignored.  Everything is device-resident; the call is asynchronous on the context's stream and never waits for the host.
+ * EINVAL: every EINVAL of rmgr_ssim_hip_enqueue_ssim3f_grad, a NULL gradOutMaps, a gMap topLeft that is NULL or not 4-byte aligned -- all
+ *         checked before any device is touched.  ENODEV: no device.
+ */
+typedef struct rmgr_ssim_hip_GradOut3F {
+    const float* topLeft;
+    ptrdiff_t    step, stride, sliceStride;     /* in floats; negatives and 0 allowed */
+} rmgr_ssim_hip_GradOut3F;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                   float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
+                                                   const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

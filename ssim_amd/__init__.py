@@ -11,7 +11,7 @@ from .api import (  # noqa: F401
     get_plan, get_version, kernel_source_id, load_library, make_params, memory_info, trim_default_pool,
     Img16, Params16, compute_ssim16, compute_ssim16_batch, make_params16,
     ImgF, ParamsF, GradF, compute_ssimf, compute_ssimf_batch, make_params_f,
-    Img3F, Params3F, Grad3F, compute_ssim3f, compute_ssim3f_batch, make_params3f,
+    Img3F, Params3F, Grad3F, GradOut3F, compute_ssim3f, compute_ssim3f_batch, make_params3f,
     compute_msssimf, compute_msssimf_batch, compute_msssimh, compute_msssimh_batch,
     Window, WINDOW_GAUSSIAN, WINDOW_UNIFORM, WINDOW_SIZES, make_window,
     GradH, GradOutF, SAMPLE_F16, SAMPLE_BF16, compute_ssimh, compute_ssimh_batch, sample_type_code,

@@ -100,6 +100,12 @@ class GradOutF(ctypes.Structure):
     _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
 
 
+class GradOut3F(ctypes.Structure):
+    """rmgr_ssim_hip_GradOut3F: one float32 volume dLoss/dssim(p) in device memory; step, stride and sliceStride count floats, negatives
+    and 0 allowed (all three 0: one float stands for the whole volume)."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd), ("sliceStride", c_pd)]
+
+
 class Window(ctypes.Structure):
     """rmgr_ssim_hip_Window: the window of the _ssimf_win entries -- size taps per axis (3, 5, 7, 9 or 11), kind WINDOW_GAUSSIAN (sigma
     finite, > 0) or WINDOW_UNIFORM (a box; sigma ignored)."""
@@ -202,6 +208,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssimf_win_grad", "rmgr_ssim_hip_enqueue_ssimf_win_map_grad",
     "rmgr_ssim_hip_enqueue_msssimh", "rmgr_ssim_hip_compute_msssimh_device", "rmgr_ssim_hip_compute_msssimh_host", "rmgr_ssim_hip_enqueue_msssimh_grad",
     "rmgr_ssim_hip_enqueue_ssim3f", "rmgr_ssim_hip_compute_ssim3f_device", "rmgr_ssim_hip_compute_ssim3f_host", "rmgr_ssim_hip_enqueue_ssim3f_grad",
+    "rmgr_ssim_hip_enqueue_ssim3f_map_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -291,6 +298,7 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssim3f_device": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_compute_ssim3f_host": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssim3f_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, vp, ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
+        "rmgr_ssim_hip_enqueue_ssim3f_map_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(GradOut3F), ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
         "rmgr_ssim_hip_enqueue_ssimf_map_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
         "rmgr_ssim_hip_enqueue_ssimh_map_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
         "rmgr_ssim_hip_enqueue_ssimf_win": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, vp],
@@ -1037,6 +1045,13 @@ class Context(object):
         _check("rmgr_ssim_hip_compute_ssimh_device", self.lib.rmgr_ssim_hip_compute_ssimh_device(
             self.handle, count, params_array, sample_type_code(sample_type), data_range, out))
         return np.array(out[:count], np.float32)
+
+    def enqueue_ssim3f_map_grad(self, params_array, count, data_range, grad_out_maps, grad_a=None, grad_b=None):
+        """rmgr_ssim_hip_enqueue_ssim3f_map_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes for a per-voxel
+        upstream gradient: grad_out_maps is a GradOut3F array of `count` float32 volumes dLoss/dssim_i(p) in device memory (any step /
+        stride / sliceStride, 0 included); asynchronous, written not accumulated."""
+        _check("rmgr_ssim_hip_enqueue_ssim3f_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_map_grad(
+            self.handle, count, params_array, data_range, grad_out_maps, grad_a, grad_b))
 
     def enqueue_ssimh(self, params_array, count, data_range, sample_type, sums_dev_ptr):
         """rmgr_ssim_hip_enqueue_ssimh: per-pair fp64 sums into device memory, asynchronously on the context's stream."""

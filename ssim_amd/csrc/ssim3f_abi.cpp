@@ -1,5 +1,6 @@
-// ssim3f_abi.cpp -- the entry points of the C ABI for float32 VOLUMES: SSIM under the three-dimensional window and its gradient
-// (rmgr_ssim_hip_*_ssim3f*).  The definition is in include/rmgr/ssim-hip.h, the kernels in ssim3f_kernels.hip.
+// ssim3f_abi.cpp -- the entry points of the C ABI for float32 VOLUMES: SSIM under the three-dimensional window, its gradient and the
+// gradient of its map for a per-voxel upstream gradient (rmgr_ssim_hip_*_ssim3f*).  The definition is in include/rmgr/ssim-hip.h, the
+// kernels in ssim3f_kernels.hip and ssim3w_kernels.hip.
 //
 // The flow is the one of ssim_samples_abi.cpp, written for three strides: validation before any device is touched, sub-batches under
 // kScratchCap of device scratch (cell partials, staged volumes and maps; the backward's coefficient volumes) with at least one volume
@@ -11,6 +12,7 @@
 // host, except -- at most -- for the launch that read its ring slot kSfSlots enqueues ago.
 #include "ssim_context.h"
 #include "ssim3f_kernels.h"
+#include "ssim3w_kernels.h"
 
 #include <cmath>
 
@@ -20,6 +22,7 @@ namespace {
 
 using ssim_hip::Pair3FDesc;
 using ssim_hip::Grad3FDesc;
+using ssim_hip::GradOut3FDesc;
 using ssim_hip::Geometry3F;
 
 const uint64_t kScratchCap = uint64_t(1) << 30;     // device scratch of one sub-batch
@@ -272,6 +275,56 @@ int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Par
     return 0;
 }
 
+// ---- the gradient of the map --------------------------------------------------------------------------------------------------------------------
+// grad_entry with a third table in the descriptor slot, the GradOut3FDesc of the sub-batch: the first walk reads k per voxel through it
+// (ssim3w_kernels.hip), the adjoint walk is the same launch.  s3_coef is shared with grad_entry in stream order.
+int validate_grad_maps3f(uint32_t count, const rmgr_ssim_hip_GradOut3F* maps)
+{
+    if (maps == NULL) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        if (maps[i].topLeft == NULL || ((uintptr_t)maps[i].topLeft & 3u)) return EINVAL;
+    return 0;
+}
+
+int map_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float range, const rmgr_ssim_hip_GradOut3F* maps,
+                   const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)
+{
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
+    const uint64_t per_volume = (uint64_t)ssim_hip::ssim3f_coef_planes(which) * W * H * D;
+    for (uint32_t i0 = 0; i0 < count;) {
+        uint64_t staged;
+        const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), per_volume * sizeof(float), false, staged);
+        const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+        int rc;
+        if ((rc = c->s3_coef.grow((size_t)(per_volume * n)))) return rc;
+        const size_t pair_bytes = n * sizeof(Pair3FDesc), grad_bytes = n * sizeof(Grad3FDesc);
+        rc = ring_launch(c, pair_bytes + grad_bytes + n * sizeof(GradOut3FDesc),
+            [&](uint8_t* pin) {
+                Pair3FDesc* pd = reinterpret_cast<Pair3FDesc*>(pin);
+                Grad3FDesc* gd = reinterpret_cast<Grad3FDesc*>(pin + pair_bytes);
+                GradOut3FDesc* od = reinterpret_cast<GradOut3FDesc*>(pin + pair_bytes + grad_bytes);
+                for (uint32_t i = 0; i < n; ++i) {
+                    pd[i] = make_desc(params[i0 + i], false);
+                    Grad3FDesc g = {NULL, 0, 0, 0, NULL, 0, 0, 0};
+                    if (gradA) { const rmgr_ssim_hip_Grad3F& s = gradA[i0 + i]; g.ga = s.topLeft; g.ga_step = s.step; g.ga_stride = s.stride; g.ga_slice = s.sliceStride; }
+                    if (gradB) { const rmgr_ssim_hip_Grad3F& s = gradB[i0 + i]; g.gb = s.topLeft; g.gb_step = s.step; g.gb_stride = s.stride; g.gb_slice = s.sliceStride; }
+                    gd[i] = g;
+                    const rmgr_ssim_hip_GradOut3F& m = maps[i0 + i];
+                    const GradOut3FDesc o = {m.topLeft, (int64_t)m.step, (int64_t)m.stride, (int64_t)m.sliceStride};
+                    od[i] = o;
+                }
+            },
+            [&](const uint8_t* dev) {
+                return ssim_hip::launch_ssim3w_grad(geo, reinterpret_cast<const Pair3FDesc*>(dev), reinterpret_cast<const Grad3FDesc*>(dev + pair_bytes),
+                                                    reinterpret_cast<const GradOut3FDesc*>(dev + pair_bytes + grad_bytes), range, which, c->s3_coef, c->stream);
+            });
+        if (rc) return rc;
+        i0 += n;
+    }
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -317,6 +370,19 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_grad(rmgr_ssim_hip_Context* c, rmgr_ui
     if (!c) return EINVAL;
     USE_DEVICE(c);
     return grad_entry(c, count, params, dataRange, gradOutDevice, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                   float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
+                                                   const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT
+{
+    int rc = validate3f(count, params, dataRange, gradOutMaps);
+    if (rc) return rc;
+    if ((rc = validate_grads3f(count, gradA, gradB))) return rc;
+    if ((rc = validate_grad_maps3f(count, gradOutMaps))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return map_grad_entry(c, count, params, dataRange, gradOutMaps, gradA, gradB);
 }
 
 } // extern "C"

@@ -63,6 +63,16 @@ hipError_t launch_ssim3f(const Geometry3F& geo, const Pair3FDesc* descs_dev, flo
 hipError_t launch_ssim3f_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, const float* g_out,
                               float data_range, int which, float* coef, hipStream_t stream);
 
+// The second half of launch_ssim3f_grad alone: the adjoint walk that reads the coefficient volumes in `coef` and writes the gradient
+// volumes.  The walk that fills `coef` is the caller's (ssim3w_kernels.hip: the per-voxel upstream gradient).
+hipError_t launch_ssim3f_adjoint(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, float data_range, int which,
+                                 const float* coef, hipStream_t stream);
+
+// What a walk of this file's shape takes by value besides its geometry: C1, C2 and the six taps (centre first) launch_ssim3f and
+// launch_ssim3f_grad run with.  false: a data_range or a geometry those launches refuse.
+struct Walk3FConstants { float c1, c2, gf[6]; };
+bool ssim3f_walk_constants(const Geometry3F& geo, float data_range, Walk3FConstants& out);
+
 } // namespace ssim_hip
 
 #endif

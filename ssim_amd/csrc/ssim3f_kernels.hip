@@ -15,7 +15,9 @@
 //    derivatives k d_mu, k d_aa, k d_ab (and k d_mu of B) of the voxel go to the coefficient volumes in the context's scratch.
 //  * ssim3f_reduce_kernel: each volume's cell partials summed in a fixed order.
 //  * ssim3f_adjoint_kernel<WHICH>: the same walk over the coefficient volumes, zero outside the volume: adjoint x pass and y pass in LDS as
-//    weighted gathers, the adjoint z pass in register rings, then dLoss/da = Gt(k d_mu_a) + 2 a' Gt(k d_aa) + b' Gt(k d_ab).
+//    weighted gathers, the adjoint z pass in register rings, then dLoss/da = Gt(k d_mu_a) + 2 a' Gt(k d_aa) + b' Gt(k d_ab).  Its launch
+//    is a host function of its own (launch_ssim3f_adjoint): the backward for a per-voxel upstream gradient (ssim3w_kernels.hip) fills
+//    the coefficient volumes with a walk of its own and runs this one unchanged.
 //
 // Chunks.  A chunk of z starts 5 slices early and runs 5 slices late (10 warm-up slices); every output voxel receives the 11 slice values of
 // its window in source order, the first one multiplied into zero, whatever slice the chunk starts at, and a cell never straddles two
@@ -499,10 +501,30 @@ hipError_t launch_ssim3f_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev
     else                 hipLaunchKernelGGL((ssim3f_walk_kernel<3>), grid, block, 0, stream, ka);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_ssim3f_adjoint(geo, descs_dev, grads_dev, data_range, which, coef, stream);
+}
+
+hipError_t launch_ssim3f_adjoint(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, float data_range, int which,
+                                 const float* coef, hipStream_t stream)
+{
+    if (geo.count == 0) return hipSuccess;
+    K3Args ka;
+    if (which < 1 || which > 3 || !fill_args(ka, geo, data_range)) return hipErrorInvalidValue;
+    ka.descs = descs_dev; ka.grads = grads_dev; ka.coef = const_cast<float*>(coef);
+    const dim3 grid((uint32_t)((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count)), block(256);
     if (which == 1)      hipLaunchKernelGGL((ssim3f_adjoint_kernel<1>), grid, block, 0, stream, ka);
     else if (which == 2) hipLaunchKernelGGL((ssim3f_adjoint_kernel<2>), grid, block, 0, stream, ka);
     else                 hipLaunchKernelGGL((ssim3f_adjoint_kernel<3>), grid, block, 0, stream, ka);
     return hipGetLastError();
+}
+
+bool ssim3f_walk_constants(const Geometry3F& geo, float data_range, Walk3FConstants& out)
+{
+    K3Args ka;
+    if (!fill_args(ka, geo, data_range)) return false;
+    out.c1 = ka.c1; out.c2 = ka.c2;
+    for (int i = 0; i < 6; ++i) out.gf[i] = ka.gf[i];
+    return true;
 }
 
 } // namespace ssim_hip

@@ -55,6 +55,12 @@ a 5-D tensor keeps its meaning -- one 2-D SSIM per slice --; the end of this fil
 
     loss = SSIM3DLoss()(x, y)                                       # x, y: (N, C, D, H, W) float32 on the GPU
 
+ssim3d_map(x, y, data_range) is the per-voxel map of the same definition, float32 of shape x.shape, for losses that are not a plain mean
+per volume; its backward is rmgr_ssim_hip_enqueue_ssim3f_map_grad, which reads grad_out per voxel, in place.
+
+    m = ssim3d_map(x, y)                                            # (N, C, D, H, W), float32
+    loss = 1 - (mask * m).sum() / mask.sum()                        # SSIM inside a brain or body mask
+
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
 import ctypes
@@ -486,33 +492,34 @@ class MSSSIMLoss(object):
 # Gaussian over x, y AND z, what pytorch-msssim (spatial_dims=3), torchmetrics (5-D input), MONAI (SSIMLoss(spatial_dims=3)) and skimage
 # (n-D arrays) compute for volumes.  It has a name of its own because ssim() on an (N, C, D, H, W) tensor already has a meaning: N * C * D
 # independent 2-D SSIMs with no window across slices.  The backward is rmgr_ssim_hip_enqueue_ssim3f_grad.  float32 only for now; the
-# configurable window, 16-bit tensors, a multi-scale form and a per-voxel map are follow-ups.
+# configurable window, 16-bit tensors and a multi-scale form are follow-ups; the per-voxel map, ssim3d_map, is at the end of the file.
 
 _function3d = None
 
 
-def _check3d(x, y, data_range):
-    """The documented errors of ssim3d, before any GPU call.  Returns data_range as a float."""
+def _check3d(x, y, data_range, name="ssim3d"):
+    """The documented errors of ssim3d and ssim3d_map (`name`: the one the message names), before any GPU call.  Returns data_range as a
+    float."""
     import torch
     if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
-        raise TypeError("ssim3d: x and y must be torch tensors")
+        raise TypeError("%s: x and y must be torch tensors" % name)
     if x.dtype in (torch.float16, torch.bfloat16) or y.dtype in (torch.float16, torch.bfloat16):
-        raise TypeError("ssim3d: the 3-D path is float32 for now, got %s and %s" % (x.dtype, y.dtype))
+        raise TypeError("%s: the 3-D path is float32 for now, got %s and %s" % (name, x.dtype, y.dtype))
     if x.dtype != torch.float32 or y.dtype != torch.float32:
-        raise TypeError("ssim3d: float32 tensors expected, got %s and %s" % (x.dtype, y.dtype))
+        raise TypeError("%s: float32 tensors expected, got %s and %s" % (name, x.dtype, y.dtype))
     if x.dim() < 3:
-        raise ValueError("ssim3d: tensors of shape (..., D, H, W) expected, got %d dimension(s)" % x.dim())
+        raise ValueError("%s: tensors of shape (..., D, H, W) expected, got %d dimension(s)" % (name, x.dim()))
     if x.shape != y.shape:
-        raise ValueError("ssim3d: shapes differ: %s and %s" % (tuple(x.shape), tuple(y.shape)))
+        raise ValueError("%s: shapes differ: %s and %s" % (name, tuple(x.shape), tuple(y.shape)))
     if not x.is_cuda or not y.is_cuda:
-        raise ValueError("ssim3d: the tensors must be on a GPU (there is no CPU path)")
+        raise ValueError("%s: the tensors must be on a GPU (there is no CPU path)" % name)
     if x.device != y.device:
-        raise ValueError("ssim3d: the tensors are on different devices: %s and %s" % (x.device, y.device))
+        raise ValueError("%s: the tensors are on different devices: %s and %s" % (name, x.device, y.device))
     if x.shape[-1] == 0 or x.shape[-2] == 0 or x.shape[-3] == 0:
-        raise ValueError("ssim3d: empty volumes: %s" % (tuple(x.shape),))
+        raise ValueError("%s: empty volumes: %s" % (name, tuple(x.shape)))
     r = float(data_range)
     if not (r > 0.0) or math.isinf(r):
-        raise ValueError("ssim3d: data_range must be finite and > 0, got %r" % (data_range,))
+        raise ValueError("%s: data_range must be finite and > 0, got %r" % (name, data_range))
     return r
 
 
@@ -617,3 +624,88 @@ class SSIM3DLoss(object):
     def __call__(self, x, y):
         loss = 1.0 - ssim3d(x, y, self.data_range)
         return loss.mean() if self.reduction == "mean" else loss
+
+
+# ---- volumes: the per-voxel map -----------------------------------------------------------------------------------------------------------
+# ssim3d_map(x, y, data_range) is the map rmgr_ssim_hip_enqueue_ssim3f writes; its backward is rmgr_ssim_hip_enqueue_ssim3f_map_grad, the
+# backward of ssim3d with the upstream gradient read per voxel, in place through grad_out's own strides.
+
+_map_function3d = None
+
+
+def _grad_out_volumes(g, n):
+    """GradOut3F array over the n (D, H, W) volumes of the float32 tensor g, each where it is: any strides, 0 (an expanded tensor)
+    included."""
+    arr = (api.GradOut3F * max(n, 1))()
+    base, strides = g.data_ptr(), (g.stride(-1), g.stride(-2), g.stride(-3))
+    for i, off in enumerate(_volume_offsets(g)):
+        arr[i] = api.GradOut3F(base + 4 * off, *strides)
+    return arr
+
+
+def _make_map_function3d():
+    import torch
+
+    class _SSIM3DMap(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, data_range):
+            d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
+            params, n = _params3d(x, y)
+            out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            if n:
+                sums = torch.empty(n, dtype=torch.float64, device=x.device)      # the kernel's other output, thrown away (ssim_map)
+                base = out.data_ptr()
+                for i in range(n):
+                    params[i].ssimMap = base + 4 * i * d * h * w
+                    params[i].ssimStep, params[i].ssimStride, params[i].ssimSliceStride = 1, w, w * h
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr())
+                if work is not cur:
+                    cur.wait_stream(work)
+            ctx.save_for_backward(x, y)
+            ctx.data_range = data_range
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            x, y = ctx.saved_tensors
+            d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
+            want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_x or want_y):
+                return None, None, None
+            params, n = _params3d(x, y)
+            g = grad_out if grad_out.dtype == torch.float32 else grad_out.to(torch.float32)      # read in place, through its own strides
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None
+            gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                maps = _grad_out_volumes(g, n)
+                ga = _grad_volumes(gx, n, d, h, w) if want_x else None
+                gb = _grad_volumes(gy, n, d, h, w) if want_y else None
+                _context(x.device, work).enqueue_ssim3f_map_grad(params, n, ctx.data_range, maps, ga, gb)
+                if work is not cur:
+                    cur.wait_stream(work)
+            return gx, gy, None
+
+    return _SSIM3DMap
+
+
+def ssim3d_map(x, y, data_range=1.0):
+    """Per-voxel SSIM of two float32 GPU tensors of identical shape (..., D, H, W) under the three-dimensional window of ssim3d(), any
+    strides (each volume is addressed in place, no copy): a float32 tensor of shape x.shape, the map rmgr_ssim_hip_enqueue_ssim3f
+    writes.  Differentiable with respect to x, y or both for ANY upstream gradient: the backward reads grad_out per voxel, in place
+    (expanded, sliced and permuted tensors included; another dtype is cast to float32 once) and computes the gradient only for the
+    inputs that need it.  It keeps x and y, not the map.  A zero in grad_out does not hide a NaN in the volumes.  Errors: as ssim3d().
+
+        m = ssim3d_map(x, y)                                  # (N, C, D, H, W)
+        loss = 1 - (mask * m).sum() / mask.sum()              # SSIM inside a brain mask"""
+    global _map_function3d
+    r = _check3d(x, y, data_range, "ssim3d_map")
+    if _map_function3d is None:
+        _map_function3d = _make_map_function3d()
+    return _map_function3d.apply(x, y, r)
