@@ -36,6 +36,8 @@
  *                                      VOLUMES (three-dimensional window) and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim3f_map_grad      gradient of the 3-D SSIM MAP for a per-voxel upstream gradient: no reference
  *                                      counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssim3h, rmgr_ssim_hip_compute_ssim3h_device / _host, rmgr_ssim_hip_enqueue_ssim3h_grad,
+ *   rmgr_ssim_hip_enqueue_ssim3h_map_grad      the same three for float16 / bfloat16 VOLUMES: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -826,7 +828,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* ctx
  *         but _host -- all checked before any device is touched.  ENODEV: no device.
  *
  * Follow-ups, not in this interface: a caller-chosen window (the _win entries), float16 / bfloat16 volumes and multi-scale SSIM of
- * volumes.
+ * volumes.  (The 16-bit volumes have since arrived under the ssim3h names, below.)
  */
 typedef struct rmgr_ssim_hip_Img3F {
     const float* topLeft;
@@ -894,6 +896,68 @@ typedef struct rmgr_ssim_hip_GradOut3F {
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                                    float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
                                                    const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
+
+/*
+ * SSIM of `count` pairs of float16 / bfloat16 VOLUMES of one size under the three-dimensional window, its gradient and the gradient of its
+ * map: the volumes a model produces under mixed precision, read as they are stored.  No reference counterpart.  Additions only:
+ * RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ * It is the definition of rmgr_ssim_hip_enqueue_ssim3f -- and of _enqueue_ssim3f_grad and _enqueue_ssim3f_map_grad --, word for word, on
+ * samples widened to float32 exactly as rmgr_ssim_hip_enqueue_ssimh defines widening:
+ *   Samples  16-bit, host byte order (rmgr_ssim_hip_uint16_t), in ONE encoding per call: sampleType RMGR_SSIM_HIP_SAMPLE_F16 (IEEE
+ *            binary16) or RMGR_SSIM_HIP_SAMPLE_BF16 (bfloat16: the upper half of a float32).  Each sample is widened to float32 exactly:
+ *            float16 subnormals are kept, NaN and Inf stay NaN and Inf.  Negative values and values above dataRange are not rejected.
+ *   Value    the value, the float32 map and every per-volume fp64 sum have the BITS rmgr_ssim_hip_enqueue_ssim3f gives on the widened
+ *            volumes.  The ONE centre per volume is the widened centre sample, used when its magnitude is at most dataRange, else 0.
+ *   Gradient  each gradient voxel is the float32 value rmgr_ssim_hip_enqueue_ssim3f_grad would store for the widened volumes, rounded ONCE, to
+ *            nearest-even, into the inputs' encoding (float16: subnormals are kept, overflow gives Inf; NaN stays NaN in both encodings).
+ *            For _enqueue_ssim3h_map_grad the float32 value is _enqueue_ssim3f_map_grad's.  gradOutDevice and the upstream volumes
+ *            (rmgr_ssim_hip_GradOut3F, reused as it is) stay float32: a loss scale arrives before the single rounding.
+ *   Identity  for a volume gMap_i whose every element is the float  float(double(gOut[i]) / (double(W) * double(H) * double(D)))
+ *            _enqueue_ssim3h_map_grad stores the BITS of _enqueue_ssim3h_grad for gOut[i].
+ *   Everything else is ssim3f's: the window, the clamped edges and their adjoint, the arithmetic and its summation orders, the cells of
+ *            16 x 16 x 8 voxels, determinism (alone or anywhere in a batch, at any z-chunk depth, after any sub-batch split, as any view),
+ *            the reach of a NaN sample (11 x 11 x 11 map voxels, 21 x 21 x 21 gradient voxels, clipped) and of a NaN in gMap (11 x 11 x
+ *            11), and the scratch: the coefficient volumes stay float32, 12 bytes per voxel for one gradient and 16 for both, in the
+ *            scratch the float32 entries use, in sub-batches of about 1 GB of it, at least one volume each.
+ *
+ * Inputs: params[0 .. count-1] as for ssim3f; imgA / imgB steps, strides and slice strides count 16-bit SAMPLES (signed, 0 included); the
+ * map is float32 and its strides count floats.  The entries are those of ssim3f with sampleType after params: _enqueue_ssim3h (device
+ * pointers, asynchronous, fp64 sums into sumsDevice), _compute_ssim3h_device (device pointers, blocks), _compute_ssim3h_host (host
+ * pointers, ctx NULL: a default context; 2 bytes per sample are staged and each float32 map is copied back at its own strides),
+ * _enqueue_ssim3h_grad and _enqueue_ssim3h_map_grad (device-resident, asynchronous; gradA / gradB: arrays of count rmgr_ssim_hip_Grad3H
+ * in host memory, either may be NULL, not both; gradients are WRITTEN, not accumulated, and must not overlap an input, a gMap or each
+ * other: not checked; params[i].ssimMap is ignored).
+ * EINVAL: everything rmgr_ssim_hip_enqueue_ssim3f / _ssim3f_grad / _ssim3f_map_grad refuse, with 2-byte alignment in place of 4-byte
+ *         alignment for the sample and gradient pointers (the map and gMap stay 4-byte aligned), and a sampleType that is neither of the
+ *         two constants -- all checked before any device is touched.  ENODEV: no device.
+ */
+typedef struct rmgr_ssim_hip_Img3H {
+    const rmgr_ssim_hip_uint16_t* topLeft;
+    ptrdiff_t step, stride, sliceStride;        /* in 16-bit samples */
+} rmgr_ssim_hip_Img3H;
+typedef struct rmgr_ssim_hip_Params3H {
+    rmgr_uint32_t       width, height, depth;
+    rmgr_ssim_hip_Img3H imgA, imgB;
+    float*              ssimMap;                /* NULL: no map */
+    ptrdiff_t           ssimStep, ssimStride, ssimSliceStride;    /* in floats */
+} rmgr_ssim_hip_Params3H;
+typedef struct rmgr_ssim_hip_Grad3H {
+    rmgr_ssim_hip_uint16_t* topLeft;
+    ptrdiff_t step, stride, sliceStride;        /* in 16-bit samples */
+} rmgr_ssim_hip_Grad3H;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                          rmgr_uint32_t sampleType, float dataRange, double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                 rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                               rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                               rmgr_uint32_t sampleType, float dataRange, const float* gradOutDevice,
+                                               const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                   rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
+                                                   const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

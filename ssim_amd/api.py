@@ -89,6 +89,23 @@ class Grad3F(ctypes.Structure):
     _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd), ("sliceStride", c_pd)]
 
 
+class Img3H(ctypes.Structure):
+    """rmgr_ssim_hip_Img3H: one float16 / bfloat16 volume; step, stride and sliceStride count 16-bit samples, not bytes."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd), ("sliceStride", c_pd)]
+
+
+class Params3H(ctypes.Structure):
+    """rmgr_ssim_hip_Params3H: the map is float32 -- ssimStep, ssimStride and ssimSliceStride count floats; ssimMap None = no map."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("depth", ctypes.c_uint32),
+                ("imgA", Img3H), ("imgB", Img3H),
+                ("ssimMap", ctypes.c_void_p), ("ssimStep", c_pd), ("ssimStride", c_pd), ("ssimSliceStride", c_pd)]
+
+
+class Grad3H(ctypes.Structure):
+    """rmgr_ssim_hip_Grad3H: one float16 / bfloat16 gradient volume in device memory; step, stride and sliceStride count 16-bit samples."""
+    _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd), ("sliceStride", c_pd)]
+
+
 class GradH(ctypes.Structure):
     """rmgr_ssim_hip_GradH: one float16 / bfloat16 gradient plane in device memory; step and stride count 16-bit samples."""
     _fields_ = [("topLeft", ctypes.c_void_p), ("step", c_pd), ("stride", c_pd)]
@@ -209,6 +226,8 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_msssimh", "rmgr_ssim_hip_compute_msssimh_device", "rmgr_ssim_hip_compute_msssimh_host", "rmgr_ssim_hip_enqueue_msssimh_grad",
     "rmgr_ssim_hip_enqueue_ssim3f", "rmgr_ssim_hip_compute_ssim3f_device", "rmgr_ssim_hip_compute_ssim3f_host", "rmgr_ssim_hip_enqueue_ssim3f_grad",
     "rmgr_ssim_hip_enqueue_ssim3f_map_grad",
+    "rmgr_ssim_hip_enqueue_ssim3h", "rmgr_ssim_hip_compute_ssim3h_device", "rmgr_ssim_hip_compute_ssim3h_host", "rmgr_ssim_hip_enqueue_ssim3h_grad",
+    "rmgr_ssim_hip_enqueue_ssim3h_map_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -299,6 +318,11 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssim3f_host": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssim3f_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, vp, ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
         "rmgr_ssim_hip_enqueue_ssim3f_map_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(GradOut3F), ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
+        "rmgr_ssim_hip_enqueue_ssim3h": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, vp],
+        "rmgr_ssim_hip_compute_ssim3h_device": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssim3h_host": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssim3h_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, vp, ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
+        "rmgr_ssim_hip_enqueue_ssim3h_map_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(GradOut3F), ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
         "rmgr_ssim_hip_enqueue_ssimf_map_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
         "rmgr_ssim_hip_enqueue_ssimh_map_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
         "rmgr_ssim_hip_enqueue_ssimf_win": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, vp],
@@ -784,6 +808,87 @@ def compute_ssimh_batch(pairs, data_range, sample_type=None, ctx=None):
     return np.array(out[:n], np.float32)
 
 
+def make_params3h(width, height, depth, a_ptr, a_strides, b_ptr, b_strides, map_ptr=None, map_strides=None):
+    """rmgr_ssim_hip_Params3H; a_strides, b_strides: (step, stride, sliceStride) in 16-bit samples; map_strides: the same in floats
+    (None: a dense depth x height x width map)."""
+    p = Params3H()
+    p.width, p.height, p.depth = width, height, depth
+    p.imgA = Img3H(a_ptr, *a_strides)
+    p.imgB = Img3H(b_ptr, *b_strides)
+    p.ssimMap = map_ptr
+    p.ssimStep, p.ssimStride, p.ssimSliceStride = (1, width, width * height) if map_strides is None else map_strides
+    return p
+
+
+def _h_volume(x, sample_type):
+    """_h_view() of a D x H x W array: (host-byte-order uint16 view whose strides are whole samples, sample type code)."""
+    if not isinstance(x, np.ndarray) or x.ndim != 3:
+        raise TypeError("D x H x W numpy array of float16 or uint16 expected")
+    if x.dtype.kind == "f" and x.dtype.itemsize == 2:
+        code = SAMPLE_F16 if sample_type is None else sample_type_code(sample_type)
+        if code != SAMPLE_F16:
+            raise TypeError("a float16 array cannot be read as bfloat16: pass the bit patterns as uint16")
+        x = (x if x.dtype.isnative else x.astype(np.float16)).view(np.uint16)
+    elif x.dtype.kind == "u" and x.dtype.itemsize == 2:
+        if sample_type is None:
+            raise ValueError("uint16 arrays need sample_type='bfloat16' or 'float16'")
+        code = sample_type_code(sample_type)
+        if not x.dtype.isnative:
+            x = x.astype(np.uint16)
+    else:
+        raise TypeError("float16 or uint16 arrays expected, got %s" % x.dtype)
+    if any(s % 2 for s in x.strides) or x.ctypes.data % 2:
+        x = np.ascontiguousarray(x)
+    return x, code
+
+
+def _h_volume_pair(a, b, sample_type):
+    (a, ta), (b, tb) = _h_volume(a, sample_type), _h_volume(b, sample_type)
+    if ta != tb:
+        raise TypeError("the two volumes differ in sample type")
+    if a.shape != b.shape:
+        raise ValueError("shapes differ: %s and %s" % (a.shape, b.shape))
+    return a, b, ta
+
+
+def _params3h_of(a, b, map_ptr=None):
+    d, h, w = a.shape
+    return make_params3h(w, h, d, a.ctypes.data, (a.strides[2] // 2, a.strides[1] // 2, a.strides[0] // 2),
+                         b.ctypes.data, (b.strides[2] // 2, b.strides[1] // 2, b.strides[0] // 2), map_ptr)
+
+
+def compute_ssim3h(a, b, data_range, sample_type=None, want_map=False, ctx=None):
+    """SSIM of two D x H x W host volumes of float16 or bfloat16 samples at `data_range` under the three-dimensional 11-tap window (any
+    strides numpy can express, negative ones included) through rmgr_ssim_hip_compute_ssim3h_host.  Arrays and sample_type: as
+    compute_ssimh (np.float16 arrays select float16; np.uint16 arrays carry bit patterns and need sample_type="bfloat16" or "float16").
+    Returns (float32 value, D x H x W float32 map or None)."""
+    a, b, code = _h_volume_pair(a, b, sample_type)
+    m = np.empty(a.shape, np.float32) if want_map else None
+    params = (Params3H * 1)()
+    params[0] = _params3h_of(a, b, m.ctypes.data if want_map else None)
+    out = (ctypes.c_float * 1)()
+    _check("rmgr_ssim_hip_compute_ssim3h_host", load_library().rmgr_ssim_hip_compute_ssim3h_host(
+        ctx.handle if ctx is not None else None, 1, params, code, data_range, out))
+    return np.float32(out[0]), m
+
+
+def compute_ssim3h_batch(pairs, data_range, sample_type=None, ctx=None):
+    """compute_ssim3h() of many host pairs of one size and one sample type in one call (no maps): a float32 array."""
+    pairs = [_h_volume_pair(a, b, sample_type) for a, b in pairs]
+    n = len(pairs)
+    codes = set(t for _, _, t in pairs)
+    if len(codes) > 1:
+        raise TypeError("the pairs differ in sample type")
+    code = codes.pop() if codes else sample_type_code("float16" if sample_type is None else sample_type)
+    params = (Params3H * max(n, 1))()
+    for i, (a, b, _) in enumerate(pairs):
+        params[i] = _params3h_of(a, b)
+    out = (ctypes.c_float * max(n, 1))()
+    _check("rmgr_ssim_hip_compute_ssim3h_host", load_library().rmgr_ssim_hip_compute_ssim3h_host(
+        ctx.handle if ctx is not None else None, n, params, code, data_range, out))
+    return np.array(out[:n], np.float32)
+
+
 def _weights_array(weights):
     """The `weights` argument of the multi-scale entry points: NULL (Wang's five) or a double array."""
     if weights is None:
@@ -1052,6 +1157,32 @@ class Context(object):
         stride / sliceStride, 0 included); asynchronous, written not accumulated."""
         _check("rmgr_ssim_hip_enqueue_ssim3f_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_map_grad(
             self.handle, count, params_array, data_range, grad_out_maps, grad_a, grad_b))
+
+    def ssim3h_device(self, params_array, count, data_range, sample_type):
+        """SSIM of `count` device-resident pairs of float16 / bfloat16 volumes (a Params3H array) under the three-dimensional window
+        through rmgr_ssim_hip_compute_ssim3h_device: a float32 array."""
+        out = (ctypes.c_float * count)()
+        _check("rmgr_ssim_hip_compute_ssim3h_device", self.lib.rmgr_ssim_hip_compute_ssim3h_device(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, out))
+        return np.array(out[:], np.float32)
+
+    def enqueue_ssim3h(self, params_array, count, data_range, sample_type, sums_dev_ptr):
+        """rmgr_ssim_hip_enqueue_ssim3h: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        _check("rmgr_ssim_hip_enqueue_ssim3h", self.lib.rmgr_ssim_hip_enqueue_ssim3h(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, sums_dev_ptr))
+
+    def enqueue_ssim3h_grad(self, params_array, count, data_range, sample_type, grad_out_dev_ptr, grad_a=None, grad_b=None):
+        """rmgr_ssim_hip_enqueue_ssim3h_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes into the 16-bit
+        volumes the Grad3H arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values; asynchronous, written not
+        accumulated."""
+        _check("rmgr_ssim_hip_enqueue_ssim3h_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_grad(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_dev_ptr, grad_a, grad_b))
+
+    def enqueue_ssim3h_map_grad(self, params_array, count, data_range, sample_type, grad_out_maps, grad_a=None, grad_b=None):
+        """rmgr_ssim_hip_enqueue_ssim3h_map_grad: the same for a per-voxel upstream gradient: grad_out_maps is a GradOut3F array of `count`
+        float32 volumes dLoss/dssim_i(p) in device memory (any step / stride / sliceStride in floats, 0 allowed)."""
+        _check("rmgr_ssim_hip_enqueue_ssim3h_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_map_grad(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_maps, grad_a, grad_b))
 
     def enqueue_ssimh(self, params_array, count, data_range, sample_type, sums_dev_ptr):
         """rmgr_ssim_hip_enqueue_ssimh: per-pair fp64 sums into device memory, asynchronously on the context's stream."""

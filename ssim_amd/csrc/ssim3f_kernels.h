@@ -55,6 +55,10 @@ inline uint32_t ssim3f_coef_planes(int which) { return which == 3 ? 4u : 3u; }
 //   sums        geo.count doubles: each volume's fp64 sum of its per-voxel values, in a fixed order
 hipError_t launch_ssim3f(const Geometry3F& geo, const Pair3FDesc* descs_dev, float data_range, double* partials, double* sums, hipStream_t stream);
 
+// The second half of launch_ssim3f alone: each volume's cell partials summed in a fixed order into sums[0 .. geo.count-1].  The walk that
+// fills `partials` is the caller's (ssim3h_kernels.hip: 16-bit samples).
+hipError_t launch_ssim3f_reduce(const Geometry3F& geo, const double* partials, double* sums, hipStream_t stream);
+
 // Enqueues the backward of geo.count pairs on `stream`: the forward walk that writes the coefficient volumes into `coef`
 // (geo.count * ssim3f_coef_planes(which) * geo.voxels() floats, dense, [pair][plane][z][y][x]), then the adjoint walk.
 //   g_out   geo.count floats in device memory: dLoss/dS_i

@@ -1,0 +1,288 @@
+// ssim3h_abi.cpp -- the entry points of the C ABI for float16 / bfloat16 VOLUMES: SSIM under the three-dimensional window, its gradient
+// and the gradient of its map for a per-voxel upstream gradient (rmgr_ssim_hip_*_ssim3h*).  The definition is in include/rmgr/ssim-hip.h,
+// the kernels in ssim3h_kernels.hip.
+//
+// The flow is the one of ssim3f_abi.cpp, written for 2-byte samples: the same validation order (plus the sample type), sub-batches under
+// kScratchCap of device scratch with at least one volume each, the launch limit, staging of host volumes (2 bytes per sample; the
+// float32 maps are copied back at their own strides), enqueue.  The planner, the cells and the coefficient layout are ssim3f's, so
+// neither the sub-batches nor the launch a volume lands in change a bit.
+//
+// It runs on the resources ssim3f_abi.cpp runs on: the context's ring of descriptor tables, its cell partials and its pinned sums
+// (sf_slots, sf_partials, sf_sums_pin) and the float32 coefficient scratch s3_coef: one stream, stream order.  An enqueue form never
+// waits for the host, except -- at most -- for the launch that read its ring slot kSfSlots enqueues ago.
+#include "ssim_context.h"
+#include "ssim3_flow.h"
+#include "ssim3h_kernels.h"
+
+#include <cmath>
+
+using namespace ssim_host;
+using namespace ssim_host::volumes;      // kScratchCap, round64, volume_bytes, take3f, ring_launch, copy_map_back
+
+namespace {
+
+using ssim_hip::Pair3HDesc;
+using ssim_hip::Grad3HDesc;
+using ssim_hip::GradOut3FDesc;
+using ssim_hip::Geometry3F;
+
+// ---- validation, before any device is touched -----------------------------------------------------------------------------------------------
+
+int validate3h(uint32_t count, const rmgr_ssim_hip_Params3H* params, uint32_t sampleType, float dataRange, const void* out)
+{
+    if (sampleType != RMGR_SSIM_HIP_SAMPLE_F16 && sampleType != RMGR_SSIM_HIP_SAMPLE_BF16) return EINVAL;
+    if (!(dataRange > 0.0f) || !std::isfinite(dataRange)) return EINVAL;
+    if (count == 0 || params == NULL || out == NULL) return EINVAL;
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    if (W == 0 || H == 0 || D == 0 || W > ssim_hip::kS3MaxDim || H > ssim_hip::kS3MaxDim || D > ssim_hip::kS3MaxDim) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i) {
+        const rmgr_ssim_hip_Params3H& p = params[i];
+        if (p.width != W || p.height != H || p.depth != D) return EINVAL;
+        if (p.imgA.topLeft == NULL || p.imgB.topLeft == NULL) return EINVAL;
+        if (((uintptr_t)p.imgA.topLeft & 1u) || ((uintptr_t)p.imgB.topLeft & 1u) || ((uintptr_t)p.ssimMap & 3u)) return EINVAL;
+    }
+    if (ssim_hip::ssim3f_max_count(W, H, D) == 0) return EINVAL;
+    return 0;
+}
+
+int validate_grads3h(uint32_t count, const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB)
+{
+    if (gradA == NULL && gradB == NULL) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const rmgr_ssim_hip_Grad3H* g = k ? gradB : gradA;
+            if (g && (g[i].topLeft == NULL || ((uintptr_t)g[i].topLeft & 1u))) return EINVAL;
+        }
+    return 0;
+}
+
+int validate_grad_maps3h(uint32_t count, const rmgr_ssim_hip_GradOut3F* maps)
+{
+    if (maps == NULL) return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        if (maps[i].topLeft == NULL || ((uintptr_t)maps[i].topLeft & 3u)) return EINVAL;
+    return 0;
+}
+
+int type_of(uint32_t sampleType) { return sampleType == RMGR_SSIM_HIP_SAMPLE_BF16 ? ssim_hip::kSHTypeBF16 : ssim_hip::kSHTypeF16; }
+
+// ---- descriptors (the sub-batch rule take3f, the staged bytes, the ring launch and the map copy-back: ssim3_flow.h) ----------------------
+
+Pair3HDesc make_desc(const rmgr_ssim_hip_Params3H& p, bool with_map)
+{
+    Pair3HDesc d;
+    d.a = p.imgA.topLeft; d.a_step = p.imgA.step; d.a_stride = p.imgA.stride; d.a_slice = p.imgA.sliceStride;
+    d.b = p.imgB.topLeft; d.b_step = p.imgB.step; d.b_stride = p.imgB.stride; d.b_slice = p.imgB.sliceStride;
+    const bool m = with_map && p.ssimMap;
+    d.map = m ? p.ssimMap : NULL;
+    d.map_step = m ? p.ssimStep : 0;
+    d.map_stride = m ? p.ssimStride : 0;
+    d.map_slice = m ? p.ssimSliceStride : 0;
+    return d;
+}
+
+Grad3HDesc make_grad_desc(const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB, uint32_t i)
+{
+    Grad3HDesc g = {NULL, 0, 0, 0, NULL, 0, 0, 0};
+    if (gradA) { const rmgr_ssim_hip_Grad3H& s = gradA[i]; g.ga = s.topLeft; g.ga_step = s.step; g.ga_stride = s.stride; g.ga_slice = s.sliceStride; }
+    if (gradB) { const rmgr_ssim_hip_Grad3H& s = gradB[i]; g.gb = s.topLeft; g.gb_step = s.step; g.gb_stride = s.stride; g.gb_slice = s.sliceStride; }
+    return g;
+}
+
+// ---- the forward flow -----------------------------------------------------------------------------------------------------------------------------
+
+uint64_t partials_per_volume(uint32_t W, uint32_t H, uint32_t D) { return ssim_hip::plan3f(W, H, D, 1, 0).cells_per_volume() * sizeof(double); }
+
+// Enqueues n pairs (descriptors in host memory, volumes on the device): descriptor upload, walk, reduction into sums[0 .. n-1].
+int enqueue_volumes(rmgr_ssim_hip_Context* c, int type, float range, uint32_t n, const Pair3HDesc* d, uint32_t W, uint32_t H, uint32_t D, double* sums)
+{
+    const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+    int rc;
+    if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_volume() * n)))) return rc;
+    return ring_launch(c, n * sizeof(Pair3HDesc),
+        [&](uint8_t* pin) { memcpy(pin, d, n * sizeof(Pair3HDesc)); },
+        [&](const uint8_t* dev) { return ssim_hip::launch_ssim3h(geo, reinterpret_cast<const Pair3HDesc*>(dev), type, range, c->sf_partials, sums, c->stream); });
+}
+
+int enqueue_all(rmgr_ssim_hip_Context* c, int type, float range, uint32_t count, const rmgr_ssim_hip_Params3H* params, double* sums)
+{
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    try {
+        std::vector<Pair3HDesc> d;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), partials_per_volume(W, H, D), false, staged);
+            d.resize(n);
+            for (uint32_t i = 0; i < n; ++i) d[i] = make_desc(params[i0 + i], true);
+            const int rc = enqueue_volumes(c, type, range, n, &d[0], W, H, D, sums + i0);
+            if (rc) return rc;
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    return 0;
+}
+
+// The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the volumes are copied (each
+// volume's sample range, 2 bytes per sample) into c->stage_a, a pair's float32 map is written densely into it as well and copied back at
+// its own strides.
+int blocking(rmgr_ssim_hip_Context* c, int type, float range, uint32_t count, const rmgr_ssim_hip_Params3H* params, float* ssim, bool stage)
+{
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    const double voxels = (double)W * (double)H * (double)D;
+    int rc;
+    if ((rc = c->sf_sums_pin.grow(count))) return rc;
+    try {
+        std::vector<Pair3HDesc> d;
+        std::vector<uint64_t> map_off;
+        std::vector<float> back;
+        for (uint32_t i0 = 0; i0 < count;) {
+            uint64_t staged;
+            const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), partials_per_volume(W, H, D), stage, staged);
+            d.resize(n);
+            map_off.assign(n, 0);
+            if (stage && (rc = c->stage_a.grow((size_t)staged))) return rc;
+            uint64_t off = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                const rmgr_ssim_hip_Params3H& p = params[i0 + i];
+                d[i] = make_desc(p, true);
+                if (!stage) continue;
+                for (int k = 0; k < 2; ++k) {
+                    const rmgr_ssim_hip_Img3H& im = k ? p.imgB : p.imgA;
+                    int64_t lo;
+                    const size_t bytes = volume_bytes(im, W, H, D, lo);
+                    HIP_TRY(hipMemcpyAsync(c->stage_a + off, im.topLeft + lo, bytes, hipMemcpyHostToDevice, c->stream));
+                    (k ? d[i].b : d[i].a) = reinterpret_cast<const uint16_t*>(c->stage_a + off) - lo;
+                    off += round64(bytes);
+                }
+                if (p.ssimMap) {
+                    map_off[i] = off;
+                    d[i].map = reinterpret_cast<float*>(c->stage_a + off);
+                    d[i].map_step = 1; d[i].map_stride = W; d[i].map_slice = (int64_t)W * H;
+                    off += round64((uint64_t)W * H * D * 4);
+                }
+            }
+            if ((rc = enqueue_volumes(c, type, range, n, &d[0], W, H, D, c->sf_sums_pin + i0))) return rc;
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (uint32_t i = 0; i < n && stage; ++i) {
+                const rmgr_ssim_hip_Params3H& p = params[i0 + i];
+                if (!p.ssimMap) continue;
+                if ((rc = copy_map_back(reinterpret_cast<const float*>(c->stage_a + map_off[i]), p, back))) return rc;
+            }
+            i0 += n;
+        }
+    } catch (...) {
+        return ENOMEM;
+    }
+    for (uint32_t i = 0; i < count; ++i) ssim[i] = (float)(c->sf_sums_pin[i] / voxels);
+    return 0;
+}
+
+// ---- the gradients --------------------------------------------------------------------------------------------------------------------------------
+// Per sub-batch: the walk that writes the float32 coefficient volumes (3 floats per voxel for one gradient, 4 for both) into c->s3_coef,
+// then the adjoint walk that reads them and rounds each gradient voxel once.  The next sub-batch -- and the float32 family, which shares
+// the scratch -- rewrites it in stream order.  maps == NULL: the per-volume upstream gradient gradOutDevice; else a third table in the
+// descriptor slot, the GradOut3FDesc of the sub-batch, through which the first walk reads k per voxel.
+int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3H* params, int type, float range, const float* gradOutDevice,
+               const rmgr_ssim_hip_GradOut3F* maps, const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB)
+{
+    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
+    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
+    const uint64_t per_volume = (uint64_t)ssim_hip::ssim3f_coef_planes(which) * W * H * D;
+    for (uint32_t i0 = 0; i0 < count;) {
+        uint64_t staged;
+        const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), per_volume * sizeof(float), false, staged);
+        const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+        int rc;
+        if ((rc = c->s3_coef.grow((size_t)(per_volume * n)))) return rc;
+        const size_t pair_bytes = n * sizeof(Pair3HDesc), grad_bytes = n * sizeof(Grad3HDesc);
+        rc = ring_launch(c, pair_bytes + grad_bytes + (maps ? n * sizeof(GradOut3FDesc) : 0),
+            [&](uint8_t* pin) {
+                Pair3HDesc* pd = reinterpret_cast<Pair3HDesc*>(pin);
+                Grad3HDesc* gd = reinterpret_cast<Grad3HDesc*>(pin + pair_bytes);
+                GradOut3FDesc* od = reinterpret_cast<GradOut3FDesc*>(pin + pair_bytes + grad_bytes);
+                for (uint32_t i = 0; i < n; ++i) {
+                    pd[i] = make_desc(params[i0 + i], false);
+                    gd[i] = make_grad_desc(gradA, gradB, i0 + i);
+                    if (!maps) continue;
+                    const rmgr_ssim_hip_GradOut3F& m = maps[i0 + i];
+                    const GradOut3FDesc o = {m.topLeft, (int64_t)m.step, (int64_t)m.stride, (int64_t)m.sliceStride};
+                    od[i] = o;
+                }
+            },
+            [&](const uint8_t* dev) {
+                const Pair3HDesc* pd = reinterpret_cast<const Pair3HDesc*>(dev);
+                const Grad3HDesc* gd = reinterpret_cast<const Grad3HDesc*>(dev + pair_bytes);
+                if (maps)
+                    return ssim_hip::launch_ssim3h_map_grad(geo, pd, gd, reinterpret_cast<const GradOut3FDesc*>(dev + pair_bytes + grad_bytes), type, range,
+                                                            which, c->s3_coef, c->stream);
+                return ssim_hip::launch_ssim3h_grad(geo, pd, gd, type, gradOutDevice + i0, range, which, c->s3_coef, c->stream);
+            });
+        if (rc) return rc;
+        i0 += n;
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                          rmgr_uint32_t sampleType, float dataRange, double* sumsDevice) RMGR_NOEXCEPT
+{
+    const int rc = validate3h(count, params, sampleType, dataRange, sumsDevice);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, type_of(sampleType), dataRange, count, params, sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                 rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = validate3h(count, params, sampleType, dataRange, ssim);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, type_of(sampleType), dataRange, count, params, ssim, false);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                               rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
+{
+    int rc = validate3h(count, params, sampleType, dataRange, ssim);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    USE_DEVICE(lease.c);
+    return blocking(lease.c, type_of(sampleType), dataRange, count, params, ssim, true);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                               rmgr_uint32_t sampleType, float dataRange, const float* gradOutDevice,
+                                               const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT
+{
+    int rc = validate3h(count, params, sampleType, dataRange, gradOutDevice);
+    if (rc) return rc;
+    if ((rc = validate_grads3h(count, gradA, gradB))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return grad_entry(c, count, params, type_of(sampleType), dataRange, gradOutDevice, NULL, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                   rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
+                                                   const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT
+{
+    int rc = validate3h(count, params, sampleType, dataRange, gradOutMaps);
+    if (rc) return rc;
+    if ((rc = validate_grads3h(count, gradA, gradB))) return rc;
+    if ((rc = validate_grad_maps3h(count, gradOutMaps))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return grad_entry(c, count, params, type_of(sampleType), dataRange, NULL, gradOutMaps, gradA, gradB);
+}
+
+} // extern "C"

@@ -1,54 +1,69 @@
-// ssim3f_kernels.hip -- gfx950 kernels of SSIM on float32 VOLUMES (a three-dimensional window) and of its gradient, behind
-// rmgr_ssim_hip_enqueue_ssim3f, rmgr_ssim_hip_compute_ssim3f_device / _host and rmgr_ssim_hip_enqueue_ssim3f_grad.  The definition they
-// implement is in include/rmgr/ssim-hip.h; tests/ssim3f_model.py restates it in float64 and restates the arithmetic below in fp32.
+// ssim3h_kernels.hip -- gfx950 kernels of SSIM on float16 / bfloat16 VOLUMES (a three-dimensional window), of its gradient and of the
+// gradient of its map for a per-voxel upstream gradient, behind rmgr_ssim_hip_enqueue_ssim3h, rmgr_ssim_hip_compute_ssim3h_device / _host,
+// rmgr_ssim_hip_enqueue_ssim3h_grad and rmgr_ssim_hip_enqueue_ssim3h_map_grad.  The definition they implement is in
+// include/rmgr/ssim-hip.h: ssim3f's, applied to the samples widened to float32, with the gradient rounded once into the samples' encoding.
 //
-// Kept apart from the 2-D files on purpose: their kernels are counted and budgeted by the tests.  What resembles ssimf_kernels.hip (the
-// folded row pass, the SSIM terms, the derivative, the adjoint weights, the per-image reduction) is copied here, not included.
+// This is the flow of ssim3f_kernels.hip and ssim3w_kernels.hip, copied, not included (those files' kernels are counted and budgeted by
+// the tests), and templated on the encoding: the same tiles, LDS planes, x / y passes, register rings, cells, chunks, coefficient
+// volumes and adjoint weights.  Two things differ, exactly as ssimh_kernels.hip differs from ssimf_kernels.hip:
+//  * how a sample gets into a register: a 2-byte load and an exact widening (widen<TYPE>: bfloat16 is the upper half of a float32, a
+//    shift; float16 goes through the hardware convert, which keeps subnormals and maps NaN and Inf to NaN and Inf).  Byte offsets scale
+//    by 2.  That is fetch() of the walks, centre_of, and the adjoint's re-read of a and b at the output voxel.  From `f2{va, vb} - cen`
+//    on every instruction is ssim3f's, built with the same flags (-ffp-contract=off), which is what gives value, map, sums, coefficient
+//    volumes and the float32 gradient the bits of ssim3f on the widened volumes;
+//  * how a gradient voxel leaves one: narrow<TYPE> rounds the float32 value once, to nearest-even, and a 2-byte store writes it
+//    (float16: the hardware convert, subnormals kept, overflow to Inf; bfloat16: integer rounding of the bit pattern, NaN kept NaN).
+// Loads and stores are the plain per-sample form: a base pointer is only 2-byte aligned, the strides are arbitrary, and the walks are
+// VALU- and LDS-bound.  The coefficient volumes, the map and the upstream gradient (scalar or per voxel) stay float32; the per-volume
+// reduction is ssim3f_kernels.hip's own kernel (launch_ssim3f_reduce).
 //
-//  * ssim3f_walk_kernel<MODE>: one 256-lane workgroup owns a 16 x 16 tile of (x, y) at an absolute position and walks a chunk of z.  Per
-//    source slice (edge-clamped on every axis, any step / stride / sliceStride, 64-bit offsets) the workgroup loads the tile + 5 of A and
-//    B one slice ahead into registers, centres them, writes (a', b') and (a'^2 + b'^2, a'b') of the 26 x 26 positions into LDS, runs the
-//    x pass on 26 rows x 16 columns (LDS to LDS) and the y pass on its own column (one lane = one column of z), and scatters the four
-//    blurred values into 11-deep register rings (the z pass); the rings' oldest entry is the finished slice z - 5.  No intermediate
-//    volume touches HBM.  MODE 0: the SSIM value, the optional map store and the lane's fp64 sum, flushed once per reduction cell (16 x 16
-//    x 8 voxels at an absolute position) through a fixed tree.  MODE 1 / 2 / 3 (dLoss/dA, dLoss/dB, both): the weighted partial
-//    derivatives k d_mu, k d_aa, k d_ab (and k d_mu of B) of the voxel go to the coefficient volumes in the context's scratch.
-//  * ssim3f_reduce_kernel: each volume's cell partials summed in a fixed order.
-//  * ssim3f_adjoint_kernel<WHICH>: the same walk over the coefficient volumes, zero outside the volume: adjoint x pass and y pass in LDS as
-//    weighted gathers, the adjoint z pass in register rings, then dLoss/da = Gt(k d_mu_a) + 2 a' Gt(k d_aa) + b' Gt(k d_ab).  Its launch
-//    is a host function of its own (launch_ssim3f_adjoint): the backward for a per-voxel upstream gradient (ssim3w_kernels.hip) fills
-//    the coefficient volumes with a walk of its own and runs this one unchanged.
-//
-// Chunks.  A chunk of z starts 5 slices early and runs 5 slices late (10 warm-up slices); every output voxel receives the 11 slice values of
-// its window in source order, the first one multiplied into zero, whatever slice the chunk starts at, and a cell never straddles two
-// chunks (chunk depths are multiples of the cell depth): value, map, sums and gradients have the same bits for every chunk depth.
-//
-// Centring.  Both walks blur a' = a - cA, b' = b - cB with ONE centre per volume: A's and B's sample at ((W - 1) / 2, (H - 1) / 2,
-// (D - 1) / 2) when its magnitude is at most dataRange, else 0.  One centre for the whole volume (not one per 128 columns as in 2-D) lets
-// the backward keep the coefficients of the centred variables in scratch: a coefficient and the voxel that collects it always share
-// their centre.  The derivative is taken in the centred variables, as in ssimf_kernels.hip.
-#include "ssim3f_kernels.h"
-#include <algorithm>
-#include <cmath>
+//  * ssim3h_walk_kernel<TYPE, MODE>: ssim3f_walk_kernel<MODE>, MODE 0 (value, map, sums) and 1 / 2 / 3 (coefficient volumes, uniform k).
+//  * ssim3h_mapwalk_kernel<TYPE, MODE>: ssim3w_walk_kernel<MODE>, MODE 1 / 2 / 3 with k = gMap(p) read per voxel.
+//  * ssim3h_adjoint_kernel<TYPE, WHICH>: ssim3f_adjoint_kernel<WHICH>.
+// Chunks, centring and the adjoint weights: see the top of ssim3f_kernels.hip; the rules are the same, on the widened samples.
+#include "ssim3h_kernels.h"
 
 namespace ssim_hip {
 namespace {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-typedef const float __attribute__((address_space(1)))* gptr_cf32;
-typedef float __attribute__((address_space(1)))*       gptr_f32;
-typedef double __attribute__((address_space(1)))*      gptr_f64;
+typedef const float __attribute__((address_space(1)))*    gptr_cf32;
+typedef float __attribute__((address_space(1)))*          gptr_f32;
+typedef double __attribute__((address_space(1)))*         gptr_f64;
+typedef const uint16_t __attribute__((address_space(1)))* gptr_cu16;
+typedef uint16_t __attribute__((address_space(1)))*       gptr_u16;
 
 __device__ __forceinline__ f2 fma_(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ float opaque(float v) { asm("" : "+v"(v)); return v; }
 
+// A stored sample -> float32, exactly (ssimh_kernels.hip: widen).
+template <int TYPE>
+__device__ __forceinline__ float widen(uint16_t s)
+{
+    if constexpr (TYPE == kSHTypeBF16) return __builtin_bit_cast(float, (uint32_t)s << 16);
+    else                               return (float)__builtin_bit_cast(_Float16, s);
+}
+// float32 -> the samples' encoding, one rounding to nearest-even (ssimh_kernels.hip: narrow).
+template <int TYPE>
+__device__ __forceinline__ uint16_t narrow(float v)
+{
+    if constexpr (TYPE == kSHTypeBF16) {
+        const uint32_t u = __builtin_bit_cast(uint32_t, v);
+        const uint32_t r = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;               // no carry out of a finite or infinite value
+        return (uint16_t)((u & 0x7FFFFFFFu) > 0x7F800000u ? (u >> 16) | 0x0040u : r);   // NaN: quiet, never rounded into Inf
+    } else {
+        return __builtin_bit_cast(uint16_t, (_Float16)v);
+    }
+}
+
 enum { T = kS3Tile, TIN = T + 10, NIN = TIN * TIN, NROW = TIN * T, NLOAD = (NIN + 255) / 256 };
 
-struct K3Args {
-    const Pair3FDesc* descs;
-    const Grad3FDesc* grads;
-    const float*      g_out;
+struct K3HArgs {
+    const Pair3HDesc*    descs;
+    const Grad3HDesc*    grads;
+    const GradOut3FDesc* gouts;   // the per-voxel upstream gradient (ssim3h_mapwalk_kernel)
+    const float*         g_out;   // the per-volume upstream gradient (ssim3h_walk_kernel, MODE != 0)
     uint32_t width, height, depth, tiles_x, tiles_y, chunks, chunk_slices, cells_z;
     double*  partials;            // [volume][cell_z][tile_y][tile_x]
     float*   coef;                // [volume][plane][z][y][x]
@@ -59,7 +74,7 @@ struct K3Args {
 // The workgroup's place: volume-major, then z-chunk, then tile row, then tile column.
 struct Place { uint32_t vol; int x0, y0, z0, z_end; uint32_t tx, ty; };
 
-__device__ __forceinline__ Place place_of(const K3Args& args)
+__device__ __forceinline__ Place place_of(const K3HArgs& args)
 {
     const uint32_t tiles = args.tiles_x * args.tiles_y, per_vol = tiles * args.chunks;
     Place p;
@@ -75,35 +90,36 @@ __device__ __forceinline__ Place place_of(const K3Args& args)
 
 __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
-// The volume's centre (top of the file).
-__device__ __forceinline__ f2 centre_of(const Pair3FDesc& pd, int W, int H, int D, float range)
+// The volume's centre: the widened sample at ((W - 1) / 2, (H - 1) / 2, (D - 1) / 2) when its magnitude is at most dataRange, else 0.
+template <int TYPE>
+__device__ __forceinline__ f2 centre_of(const Pair3HDesc& pd, int W, int H, int D, float range)
 {
     const int64_t cx = (W - 1) / 2, cy = (H - 1) / 2, cz = (D - 1) / 2;
-    const float sa = ((gptr_cf32)pd.a)[cx * pd.a_step + cy * pd.a_stride + cz * pd.a_slice];
-    const float sb = ((gptr_cf32)pd.b)[cx * pd.b_step + cy * pd.b_stride + cz * pd.b_slice];
+    const float sa = widen<TYPE>(((gptr_cu16)pd.a)[cx * pd.a_step + cy * pd.a_stride + cz * pd.a_slice]);
+    const float sb = widen<TYPE>(((gptr_cu16)pd.b)[cx * pd.b_step + cy * pd.b_stride + cz * pd.b_slice]);
     return f2{__builtin_fabsf(sa) <= range ? sa : 0.0f, __builtin_fabsf(sb) <= range ? sb : 0.0f};
 }
 
-// MODE 0: value, map, sums.  MODE 1 / 2 / 3: the coefficient volumes of dLoss/dA, dLoss/dB, both.  The statistics are computed in the
-// same order in all four.
-template <int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
-void ssim3f_walk_kernel(const K3Args args)
+// MODE 0: value, map, sums.  MODE 1 / 2 / 3: the coefficient volumes of dLoss/dA, dLoss/dB, both.  PERVOXEL: the weight k of the
+// voxel's partial derivatives is gMap(p), read per voxel (MODE != 0), not the launch-uniform float(gOut / (W H D)).  The statistics are
+// computed in the same order in all of them.
+template <int TYPE, int MODE, bool PERVOXEL>
+__device__ __forceinline__ void walk_body(const K3HArgs& args)
 {
     constexpr int NP = MODE == 3 ? 4 : 3;
     __shared__ __attribute__((aligned(16))) f2 inAB[NIN];     // (a', b') of the tile + 5
     __shared__ __attribute__((aligned(16))) f2 inQ[NIN];      // (a'^2 + b'^2, a'b')
     __shared__ __attribute__((aligned(16))) f2 Hab[NROW];     // x pass, 26 rows x 16 columns
     __shared__ __attribute__((aligned(16))) f2 Hq[NROW];
-    __shared__ double red[4];
+    __shared__ double red[MODE == 0 ? 4 : 1];
 
     const int tid = threadIdx.x, lx = tid & (T - 1), ly = tid >> 4;
     const int W = (int)args.width, H = (int)args.height, D = (int)args.depth;
     const Place pl = place_of(args);
-    const Pair3FDesc pd = args.descs[pl.vol];
-    const gptr_cf32 pa = (gptr_cf32)pd.a, pb = (gptr_cf32)pd.b;
+    const Pair3HDesc pd = args.descs[pl.vol];
+    const gptr_cu16 pa = (gptr_cu16)pd.a, pb = (gptr_cu16)pd.b;
     const float gf[6] = {args.gf[0], args.gf[1], args.gf[2], args.gf[3], args.gf[4], args.gf[5]};
-    const f2 cen = centre_of(pd, W, H, D, args.range);
+    const f2 cen = centre_of<TYPE>(pd, W, H, D, args.range);
 
     // staging positions: element idx of the 26 x 26 plane is voxel (clamp(x0 - 5 + idx % 26), clamp(y0 - 5 + idx / 26))
     int sp[NLOAD];
@@ -123,8 +139,8 @@ void ssim3f_walk_kernel(const K3Args args)
         const int64_t zc = clampi(s, D);
 #pragma unroll
         for (int t = 0; t < NLOAD; ++t) {
-            va[t] = pa[offA[t] + zc * pd.a_slice];
-            vb[t] = pb[offB[t] + zc * pd.b_slice];
+            va[t] = widen<TYPE>(pa[offA[t] + zc * pd.a_slice]);
+            vb[t] = widen<TYPE>(pb[offB[t] + zc * pd.b_slice]);
         }
     };
 
@@ -132,8 +148,16 @@ void ssim3f_walk_kernel(const K3Args args)
     const bool inside = qx < W && qy < H;
     const uint64_t voxels = (uint64_t)W * (uint64_t)H * (uint64_t)D;
     float k = 0.0f;
-    if constexpr (MODE != 0)
+    gptr_cf32 pg = nullptr;
+    int64_t offG = 0, sliceG = 0;
+    if constexpr (PERVOXEL) {
+        const GradOut3FDesc go = args.gouts[pl.vol];
+        pg = (gptr_cf32)go.g;
+        offG = inside ? (int64_t)qx * go.g_step + (int64_t)qy * go.g_stride : 0;      // the lane's column of gMap
+        sliceG = go.g_slice;
+    } else if constexpr (MODE != 0) {
         k = (float)((double)((gptr_cf32)args.g_out)[pl.vol] / ((double)W * (double)H * (double)D));
+    }
 
     f2 accAB[11], accQ[11];
 #pragma unroll
@@ -143,6 +167,14 @@ void ssim3f_walk_kernel(const K3Args args)
     fetch(pl.z0 - 5);
 #pragma unroll 1
     for (int s = pl.z0 - 5; s < pl.z_end + 5; ++s) {
+        const int z = s - 5;
+        // 0. (PERVOXEL) k of the slice this iteration finishes, z = s - 5 < z_end; no address is formed outside the volume or during the
+        //    warm-up; the load's latency sits under the LDS passes
+        if constexpr (PERVOXEL) {
+            k = 0.0f;
+            if (inside && z >= pl.z0)
+                k = pg[offG + (int64_t)z * sliceG];
+        }
         // 1. the slice's centred samples and products -> LDS; the next slice's samples -> registers
 #pragma unroll
         for (int t = 0; t < NLOAD; ++t) {
@@ -194,7 +226,6 @@ void ssim3f_walk_kernel(const K3Args args)
         }
         accAB[10] = m * f2{gf[5], gf[5]};
         accQ[10] = e * f2{gf[5], gf[5]};
-        const int z = s - 5;
         if (z < pl.z0) continue;
         // 5. ring entry 0 is the finished slice z
         const f2 mm = accAB[0], ee = accQ[0];
@@ -243,34 +274,22 @@ void ssim3f_walk_kernel(const K3Args args)
     }
 }
 
-// Per-volume sum of the cell partials in a fixed order: thread t of 1024 adds cells t, t + 1024, ... in that order, each wave runs a
-// fixed xor butterfly, and the 16 wave totals are added in wave order.  One workgroup per volume.
-constexpr int kReduceThreads = 1024;
-
-__global__ __launch_bounds__(kReduceThreads) void ssim3f_reduce_kernel(const double* __restrict__ partials, uint64_t per_volume, double* __restrict__ sums)
+template <int TYPE, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+void ssim3h_walk_kernel(const K3HArgs args)
 {
-    __shared__ double sh[kReduceThreads / 64];
-    const double* p = partials + (size_t)blockIdx.x * per_volume;
-    double acc = 0.0;
-    for (uint64_t i = threadIdx.x; i < per_volume; i += kReduceThreads)
-        acc += p[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63u) == 0)
-        sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = sh[0];
-#pragma unroll
-        for (int w = 1; w < kReduceThreads / 64; ++w)
-            t += sh[w];
-        sums[blockIdx.x] = t;
-    }
+    walk_body<TYPE, MODE, false>(args);
 }
 
-// What gradient voxel q of an axis of n voxels collects from p = q + j: the tap g|j| in the interior, and on the first (last) voxel the
-// sum of the taps the forward pass clamped onto it, tail[|j|] = g|j| + ... + g5 for j >= 0 (j <= 0); the sum of all taps when n == 1.
+template <int TYPE, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+void ssim3h_mapwalk_kernel(const K3HArgs args)
+{
+    static_assert(MODE >= 1 && MODE <= 3, "the value walk has no upstream gradient");
+    walk_body<TYPE, MODE, true>(args);
+}
+
+// What gradient voxel q of an axis of n voxels collects from p = q + j (ssim3f_kernels.hip: adjoint_weight).
 __device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float (&g)[6], const float (&tail)[6], float total)
 {
     const int aj = j < 0 ? -j : j;
@@ -282,10 +301,10 @@ __device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float
 }
 
 // WHICH: 1 dLoss/dA, 2 dLoss/dB, 3 both.  Every pass is a gather in the order j = -5 .. 5, the first product plain, the others fused; a
-// coefficient outside the volume is 0 (the clamp is in the weights).
-template <int WHICH>
+// coefficient outside the volume is 0 (the clamp is in the weights).  The float32 gradient voxel is rounded once on its way out.
+template <int TYPE, int WHICH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
-void ssim3f_adjoint_kernel(const K3Args args)
+void ssim3h_adjoint_kernel(const K3HArgs args)
 {
     constexpr int NP = WHICH == 3 ? 4 : 3;
     __shared__ __attribute__((aligned(16))) float P[NP][NIN];      // the slice's coefficients on the tile + 5
@@ -294,11 +313,11 @@ void ssim3f_adjoint_kernel(const K3Args args)
     const int tid = threadIdx.x, lx = tid & (T - 1), ly = tid >> 4;
     const int W = (int)args.width, H = (int)args.height, D = (int)args.depth;
     const Place pl = place_of(args);
-    const Pair3FDesc pd = args.descs[pl.vol];
-    const Grad3FDesc gd = args.grads[pl.vol];
+    const Pair3HDesc pd = args.descs[pl.vol];
+    const Grad3HDesc gd = args.grads[pl.vol];
     const float gf[6] = {args.gf[0], args.gf[1], args.gf[2], args.gf[3], args.gf[4], args.gf[5]};
     const float tail[6] = {args.tail[0], args.tail[1], args.tail[2], args.tail[3], args.tail[4], args.tail[5]};
-    const f2 cen = centre_of(pd, W, H, D, args.range);
+    const f2 cen = centre_of<TYPE>(pd, W, H, D, args.range);
     const uint64_t plane = (uint64_t)W * (uint64_t)H, voxels = plane * (uint64_t)D;
     const gptr_cf32 coef = (gptr_cf32)args.coef + (uint64_t)pl.vol * NP * voxels;
 
@@ -385,152 +404,101 @@ void ssim3f_adjoint_kernel(const K3Args args)
         }
         const int z = s - 5;
         if (z < pl.z0 || !inside) continue;
-        const float a = ((gptr_cf32)pd.a)[(int64_t)qx * pd.a_step + (int64_t)qy * pd.a_stride + (int64_t)z * pd.a_slice] - cen.x;
-        const float b = ((gptr_cf32)pd.b)[(int64_t)qx * pd.b_step + (int64_t)qy * pd.b_stride + (int64_t)z * pd.b_slice] - cen.y;
+        const float a = widen<TYPE>(((gptr_cu16)pd.a)[(int64_t)qx * pd.a_step + (int64_t)qy * pd.a_stride + (int64_t)z * pd.a_slice]) - cen.x;
+        const float b = widen<TYPE>(((gptr_cu16)pd.b)[(int64_t)qx * pd.b_step + (int64_t)qy * pd.b_stride + (int64_t)z * pd.b_slice]) - cen.y;
         if constexpr (WHICH != 2) {
             const float g = opaque(acc[0][0] + opaque(opaque(2.0f * a) * acc[1][0])) + opaque(b * acc[2][0]);
-            ((gptr_f32)gd.ga)[(int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride + (int64_t)z * gd.ga_slice] = g;
+            ((gptr_u16)gd.ga)[(int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride + (int64_t)z * gd.ga_slice] = narrow<TYPE>(g);
         }
         if constexpr (WHICH != 1) {
             const float g = opaque(acc[WHICH == 3 ? 3 : 0][0] + opaque(opaque(2.0f * b) * acc[1][0])) + opaque(a * acc[2][0]);
-            ((gptr_f32)gd.gb)[(int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride + (int64_t)z * gd.gb_slice] = g;
+            ((gptr_u16)gd.gb)[(int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride + (int64_t)z * gd.gb_slice] = narrow<TYPE>(g);
         }
     }
 }
 
-const uint64_t kMaxBlocks = (uint64_t(1) << 24) - 1;      // x 256 work-items stays below 2^32
-
-// The engine's 11-tap Gaussian, sigma 1.5, centre first: g_i = exp(-(i i) / (2 s s)), the norm accumulated in double in the order
-// i = 0 .. 5, g_0 once and the others twice; tap i = float(g_i / norm) -- the taps of every other kernel file, bit for bit.
-void engine_taps(float (&gf)[6])
+// The arguments every walk takes by value: geometry, C1, C2 and the taps of launch_ssim3f (ssim3f_walk_constants), and the adjoint's
+// tail[d] = g_d + ... + g_5 and the sum of all eleven taps: sums of the float taps in double, rounded once (ssim3f_kernels.hip: fill_args).
+bool fill_args(K3HArgs& ka, const Geometry3F& geo, int type, float data_range)
 {
-    double g[6], norm = 0.0;
-    for (int i = 0; i < 6; ++i) {
-        g[i] = std::exp(-(double)(i * i) / (2.0 * 1.5 * 1.5));
-        norm += i == 0 ? g[i] : 2.0 * g[i];
-    }
-    for (int i = 0; i < 6; ++i) gf[i] = (float)(g[i] / norm);
-}
-
-void constants3f(float data_range, float& c1, float& c2)      // ssimf_constants(), copied
-{
-    const double R = (double)data_range;
-    c1 = (float)((0.01 * R) * (0.01 * R));
-    c2 = (float)((0.03 * R) * (0.03 * R));
-}
-
-bool fill_args(K3Args& ka, const Geometry3F& geo, float data_range)
-{
-    if (!(data_range > 0.0f) || !std::isfinite(data_range) || geo.count == 0 || geo.count > ssim3f_max_count(geo.width, geo.height, geo.depth)) return false;
-    if ((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count > kMaxBlocks || geo.chunk_slices % kS3CellZ != 0) return false;
-    ka.descs = NULL; ka.grads = NULL; ka.g_out = NULL; ka.partials = NULL; ka.coef = NULL;
+    Walk3FConstants wc;
+    if ((type != kSHTypeF16 && type != kSHTypeBF16) || !ssim3f_walk_constants(geo, data_range, wc)) return false;
+    ka.descs = NULL; ka.grads = NULL; ka.gouts = NULL; ka.g_out = NULL; ka.partials = NULL; ka.coef = NULL;
     ka.width = geo.width; ka.height = geo.height; ka.depth = geo.depth;
     ka.tiles_x = geo.tiles_x; ka.tiles_y = geo.tiles_y; ka.chunks = geo.chunks; ka.chunk_slices = geo.chunk_slices; ka.cells_z = geo.cells_z;
-    ka.range = data_range;
-    constants3f(data_range, ka.c1, ka.c2);
-    engine_taps(ka.gf);
-    // tail[d] = g_d + ... + g_5 and the sum of all eleven taps: sums of the float taps in double, rounded once
+    ka.c1 = wc.c1; ka.c2 = wc.c2; ka.range = data_range;
+    for (int i = 0; i < 6; ++i) ka.gf[i] = wc.gf[i];
     double t = 0.0;
     for (int i = 5; i >= 0; --i) { t += (double)ka.gf[i]; ka.tail[i] = (float)t; }
     ka.total = (float)(2.0 * t - (double)ka.gf[0]);
     return true;
 }
 
+dim3 grid_of(const Geometry3F& geo) { return dim3((uint32_t)((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count)); }
+
+template <int TYPE>
+hipError_t launch_adjoint(const Geometry3F& geo, const K3HArgs& ka, int which, hipStream_t stream)
+{
+    const dim3 grid = grid_of(geo), block(256);
+    if (which == 1)      hipLaunchKernelGGL((ssim3h_adjoint_kernel<TYPE, 1>), grid, block, 0, stream, ka);
+    else if (which == 2) hipLaunchKernelGGL((ssim3h_adjoint_kernel<TYPE, 2>), grid, block, 0, stream, ka);
+    else                 hipLaunchKernelGGL((ssim3h_adjoint_kernel<TYPE, 3>), grid, block, 0, stream, ka);
+    return hipGetLastError();
+}
+
+template <int TYPE>
+hipError_t launch_grad(const Geometry3F& geo, const K3HArgs& ka, int which, hipStream_t stream)
+{
+    const dim3 grid = grid_of(geo), block(256);
+    if (ka.gouts) {
+        if (which == 1)      hipLaunchKernelGGL((ssim3h_mapwalk_kernel<TYPE, 1>), grid, block, 0, stream, ka);
+        else if (which == 2) hipLaunchKernelGGL((ssim3h_mapwalk_kernel<TYPE, 2>), grid, block, 0, stream, ka);
+        else                 hipLaunchKernelGGL((ssim3h_mapwalk_kernel<TYPE, 3>), grid, block, 0, stream, ka);
+    } else {
+        if (which == 1)      hipLaunchKernelGGL((ssim3h_walk_kernel<TYPE, 1>), grid, block, 0, stream, ka);
+        else if (which == 2) hipLaunchKernelGGL((ssim3h_walk_kernel<TYPE, 2>), grid, block, 0, stream, ka);
+        else                 hipLaunchKernelGGL((ssim3h_walk_kernel<TYPE, 3>), grid, block, 0, stream, ka);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_adjoint<TYPE>(geo, ka, which, stream);
+}
+
 } // namespace
 
-uint32_t ssim3f_max_count(uint32_t width, uint32_t height, uint32_t depth)
-{
-    if (width == 0 || height == 0 || depth == 0 || width > kS3MaxDim || height > kS3MaxDim || depth > kS3MaxDim) return 0;
-    const uint64_t tiles = (uint64_t)((width + kS3Tile - 1) / kS3Tile) * ((height + kS3Tile - 1) / kS3Tile);
-    return (uint32_t)std::min<uint64_t>(kMaxBlocks / tiles, 65535);
-}
-
-Geometry3F plan3f(uint32_t width, uint32_t height, uint32_t depth, uint32_t count, int cu_count)
-{
-    Geometry3F g;
-    g.width = width; g.height = height; g.depth = depth; g.count = count;
-    g.tiles_x = (width + kS3Tile - 1) / kS3Tile;
-    g.tiles_y = (height + kS3Tile - 1) / kS3Tile;
-    g.cells_z = (depth + kS3CellZ - 1) / kS3CellZ;
-    // four workgroups of four waves per CU (the walk's occupancy): a round; pick the chunk depth (whole cells, doubling) that finishes the launch's workgroups in
-    // the fewest slice-times, 10 warm-up slices included, among those whose grid fits
-    const uint64_t slots = (uint64_t)(cu_count > 0 ? cu_count : 256) * 4;
-    const uint64_t cols = (uint64_t)g.tiles_x * g.tiles_y * std::max<uint32_t>(count, 1);
-    uint64_t best = ~uint64_t(0), best_slices = 0;
-    for (uint64_t slices = kS3CellZ;; slices *= 2) {
-        const uint64_t chunks = (depth + slices - 1) / slices;
-        if (cols * chunks <= kMaxBlocks) {
-            const uint64_t rounds = (cols * chunks + slots - 1) / slots;
-            const uint64_t cost = rounds * (std::min<uint64_t>(slices, depth) + 10);
-            if (cost <= best) { best = cost; best_slices = slices; }
-        }
-        if (slices >= depth) {
-            if (best_slices == 0) best_slices = slices;
-            break;
-        }
-    }
-    g.chunk_slices = (uint32_t)best_slices;
-    g.chunks = (uint32_t)((depth + best_slices - 1) / best_slices);
-    return g;
-}
-
-hipError_t launch_ssim3f(const Geometry3F& geo, const Pair3FDesc* descs_dev, float data_range, double* partials, double* sums, hipStream_t stream)
+hipError_t launch_ssim3h(const Geometry3F& geo, const Pair3HDesc* descs_dev, int type, float data_range, double* partials, double* sums,
+                         hipStream_t stream)
 {
     if (geo.count == 0) return hipSuccess;
-    K3Args ka;
-    if (!fill_args(ka, geo, data_range)) return hipErrorInvalidValue;
+    K3HArgs ka;
+    if (!fill_args(ka, geo, type, data_range)) return hipErrorInvalidValue;
     ka.descs = descs_dev; ka.partials = partials;
-    const dim3 grid((uint32_t)((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count)), block(256);
-    hipLaunchKernelGGL((ssim3f_walk_kernel<0>), grid, block, 0, stream, ka);
-    hipError_t e = hipGetLastError();
+    const dim3 grid = grid_of(geo), block(256);
+    if (type == kSHTypeBF16) hipLaunchKernelGGL((ssim3h_walk_kernel<kSHTypeBF16, 0>), grid, block, 0, stream, ka);
+    else                     hipLaunchKernelGGL((ssim3h_walk_kernel<kSHTypeF16, 0>), grid, block, 0, stream, ka);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_ssim3f_reduce(geo, partials, sums, stream);
 }
 
-hipError_t launch_ssim3f_reduce(const Geometry3F& geo, const double* partials, double* sums, hipStream_t stream)
-{
-    if (geo.count == 0) return hipSuccess;
-    hipLaunchKernelGGL(ssim3f_reduce_kernel, dim3(geo.count), dim3(kReduceThreads), 0, stream, partials, geo.cells_per_volume(), sums);
-    return hipGetLastError();
-}
-
-hipError_t launch_ssim3f_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, const float* g_out,
+hipError_t launch_ssim3h_grad(const Geometry3F& geo, const Pair3HDesc* descs_dev, const Grad3HDesc* grads_dev, int type, const float* g_out,
                               float data_range, int which, float* coef, hipStream_t stream)
 {
     if (geo.count == 0) return hipSuccess;
-    K3Args ka;
-    if (which < 1 || which > 3 || !fill_args(ka, geo, data_range)) return hipErrorInvalidValue;
+    K3HArgs ka;
+    if (which < 1 || which > 3 || g_out == NULL || !fill_args(ka, geo, type, data_range)) return hipErrorInvalidValue;
     ka.descs = descs_dev; ka.grads = grads_dev; ka.g_out = g_out; ka.coef = coef;
-    const dim3 grid((uint32_t)((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count)), block(256);
-    if (which == 1)      hipLaunchKernelGGL((ssim3f_walk_kernel<1>), grid, block, 0, stream, ka);
-    else if (which == 2) hipLaunchKernelGGL((ssim3f_walk_kernel<2>), grid, block, 0, stream, ka);
-    else                 hipLaunchKernelGGL((ssim3f_walk_kernel<3>), grid, block, 0, stream, ka);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_ssim3f_adjoint(geo, descs_dev, grads_dev, data_range, which, coef, stream);
+    return type == kSHTypeBF16 ? launch_grad<kSHTypeBF16>(geo, ka, which, stream) : launch_grad<kSHTypeF16>(geo, ka, which, stream);
 }
 
-hipError_t launch_ssim3f_adjoint(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, float data_range, int which,
-                                 const float* coef, hipStream_t stream)
+hipError_t launch_ssim3h_map_grad(const Geometry3F& geo, const Pair3HDesc* descs_dev, const Grad3HDesc* grads_dev, const GradOut3FDesc* gouts_dev,
+                                  int type, float data_range, int which, float* coef, hipStream_t stream)
 {
     if (geo.count == 0) return hipSuccess;
-    K3Args ka;
-    if (which < 1 || which > 3 || !fill_args(ka, geo, data_range)) return hipErrorInvalidValue;
-    ka.descs = descs_dev; ka.grads = grads_dev; ka.coef = const_cast<float*>(coef);
-    const dim3 grid((uint32_t)((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count)), block(256);
-    if (which == 1)      hipLaunchKernelGGL((ssim3f_adjoint_kernel<1>), grid, block, 0, stream, ka);
-    else if (which == 2) hipLaunchKernelGGL((ssim3f_adjoint_kernel<2>), grid, block, 0, stream, ka);
-    else                 hipLaunchKernelGGL((ssim3f_adjoint_kernel<3>), grid, block, 0, stream, ka);
-    return hipGetLastError();
-}
-
-bool ssim3f_walk_constants(const Geometry3F& geo, float data_range, Walk3FConstants& out)
-{
-    K3Args ka;
-    if (!fill_args(ka, geo, data_range)) return false;
-    out.c1 = ka.c1; out.c2 = ka.c2;
-    for (int i = 0; i < 6; ++i) out.gf[i] = ka.gf[i];
-    return true;
+    K3HArgs ka;
+    if (which < 1 || which > 3 || gouts_dev == NULL || !fill_args(ka, geo, type, data_range)) return hipErrorInvalidValue;
+    ka.descs = descs_dev; ka.grads = grads_dev; ka.gouts = gouts_dev; ka.coef = coef;
+    return type == kSHTypeBF16 ? launch_grad<kSHTypeBF16>(geo, ka, which, stream) : launch_grad<kSHTypeF16>(geo, ka, which, stream);
 }
 
 } // namespace ssim_hip

@@ -200,8 +200,9 @@ struct rmgr_ssim_hip_Context_ {
     DeviceBuffer<float>    msf_pyramid, msf_grads, msf_coef;
     DeviceBuffer<double>   msf_partials, msf_out;
     PinnedBuffer<double>   msf_out_pin;
-    // SSIM of float32 volumes (rmgr_ssim_hip_*_ssim3f*, ssim3f_abi.cpp): the backward's coefficient volumes, rewritten by every sub-batch in
-    // stream order.  Descriptor tables, cell partials and pinned sums are sf_slots, sf_partials and sf_sums_pin.
+    // SSIM of float32 and of float16 / bfloat16 volumes (rmgr_ssim_hip_*_ssim3f*, ssim3f_abi.cpp; _ssim3h*, ssim3h_abi.cpp): the backward's
+    // float32 coefficient volumes, rewritten by every sub-batch in stream order.  Descriptor tables, cell partials and pinned sums are
+    // sf_slots, sf_partials and sf_sums_pin.
     DeviceBuffer<float>    s3_coef;
 
     // Every grow-only staging buffer above, once: what context_held counts and context_trim gives back.

@@ -61,6 +61,18 @@ per volume; its backward is rmgr_ssim_hip_enqueue_ssim3f_map_grad, which reads g
     m = ssim3d_map(x, y)                                            # (N, C, D, H, W), float32
     loss = 1 - (mask * m).sum() / mask.sum()                        # SSIM inside a brain or body mask
 
+float16 and bfloat16 volumes.  ssim3d_amp(x, y, data_range), ssim3d_map_amp(x, y, data_range) and SSIM3DLoss take two float32, two
+float16 or two bfloat16 tensors as they come under torch.autocast (rmgr_ssim_hip_enqueue_ssim3h, _ssim3h_grad, _ssim3h_map_grad): the
+samples are read as they are (2 B/voxel), the value and the map are float32 with the bits of ssim3d(x.float(), y.float()) /
+ssim3d_map(x.float(), y.float()), and the gradient comes back in the inputs' dtype, that call's float32 gradient rounded once by the
+kernel; grad_out stays float32, so a GradScaler's scale arrives before the rounding.  The wart of ms_ssim / ms_ssim_amp again: ssim3d and
+ssim3d_map themselves stay float32-only (16-bit tensors are a TypeError there, pinned by tests from the time there was no 16-bit volume
+path; the _amp functions are the same functions without that refusal), and two 16-bit CPU tensors are a TypeError in the _amp functions
+and SSIM3DLoss.
+
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        loss = SSIM3DLoss()(net(x), y.bfloat16())                   # read as bfloat16; the gradient is bfloat16
+
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
 import ctypes
@@ -491,21 +503,27 @@ class MSSSIMLoss(object):
 # ssim3d(x, y, data_range) is the per-volume mean of the definition in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssim3f): the 11-tap
 # Gaussian over x, y AND z, what pytorch-msssim (spatial_dims=3), torchmetrics (5-D input), MONAI (SSIMLoss(spatial_dims=3)) and skimage
 # (n-D arrays) compute for volumes.  It has a name of its own because ssim() on an (N, C, D, H, W) tensor already has a meaning: N * C * D
-# independent 2-D SSIMs with no window across slices.  The backward is rmgr_ssim_hip_enqueue_ssim3f_grad.  float32 only for now; the
-# configurable window, 16-bit tensors and a multi-scale form are follow-ups; the per-voxel map, ssim3d_map, is at the end of the file.
+# independent 2-D SSIMs with no window across slices.  The backward is rmgr_ssim_hip_enqueue_ssim3f_grad.  ssim3d and ssim3d_map are
+# float32-only; ssim3d_amp and ssim3d_map_amp (the end of the file) take float16 / bfloat16 volumes as well, on the ssim3h entries, through
+# the same two autograd functions.  The configurable window and a multi-scale form are follow-ups.
 
 _function3d = None
 
 
-def _check3d(x, y, data_range, name="ssim3d"):
+def _check3d(x, y, data_range, name="ssim3d", half=False):
     """The documented errors of ssim3d and ssim3d_map (`name`: the one the message names), before any GPU call.  Returns data_range as a
-    float."""
+    float.  half (ssim3d_amp, ssim3d_map_amp): float16 and bfloat16 pairs are taken too, on a GPU."""
     import torch
     if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
         raise TypeError("%s: x and y must be torch tensors" % name)
-    if x.dtype in (torch.float16, torch.bfloat16) or y.dtype in (torch.float16, torch.bfloat16):
-        raise TypeError("%s: the 3-D path is float32 for now, got %s and %s" % (name, x.dtype, y.dtype))
-    if x.dtype != torch.float32 or y.dtype != torch.float32:
+    if half:
+        if x.dtype != y.dtype or x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError("%s: two float32, two float16 or two bfloat16 tensors expected, got %s and %s" % (name, x.dtype, y.dtype))
+        if x.dtype != torch.float32 and not x.is_cuda and not y.is_cuda:
+            raise TypeError("%s: float16 / bfloat16 tensors are taken on a GPU only, got %s on %s and %s" % (name, x.dtype, x.device, y.device))
+    elif x.dtype in (torch.float16, torch.bfloat16) or y.dtype in (torch.float16, torch.bfloat16):
+        raise TypeError("%s: the 3-D path is float32 for now, got %s and %s; %s_amp() takes float16 / bfloat16 tensors" % (name, x.dtype, y.dtype, name))
+    elif x.dtype != torch.float32 or y.dtype != torch.float32:
         raise TypeError("%s: float32 tensors expected, got %s and %s" % (name, x.dtype, y.dtype))
     if x.dim() < 3:
         raise ValueError("%s: tensors of shape (..., D, H, W) expected, got %d dimension(s)" % (name, x.dim()))
@@ -535,20 +553,23 @@ def _params3d(x, y):
     d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
     ox, oy = _volume_offsets(x), _volume_offsets(y)
     n = len(ox)
-    params = (api.Params3F * max(n, 1))()
+    es = x.element_size()                      # 4: Params3F; 2 (float16, bfloat16): Params3H -- steps and strides count samples in both
+    make, params = (api.make_params3f, (api.Params3F * max(n, 1))()) if es == 4 else (api.make_params3h, (api.Params3H * max(n, 1))())
     px, py = x.data_ptr(), y.data_ptr()
     sx, sy = (x.stride(-1), x.stride(-2), x.stride(-3)), (y.stride(-1), y.stride(-2), y.stride(-3))
     for i in range(n):
-        params[i] = api.make_params3f(w, h, d, px + 4 * ox[i], sx, py + 4 * oy[i], sy)
+        params[i] = make(w, h, d, px + es * ox[i], sx, py + es * oy[i], sy)
     return params, n
 
 
 def _grad_volumes(g, n, d, h, w):
-    """Grad3F array over the n contiguous volumes of the float32 tensor g."""
-    arr = (api.Grad3F * max(n, 1))()
+    """Grad3F (float32) or Grad3H (float16, bfloat16) array over the n contiguous volumes of g."""
+    es = g.element_size()
+    cls = api.Grad3F if es == 4 else api.Grad3H
+    arr = (cls * max(n, 1))()
     base = g.data_ptr()
     for i in range(n):
-        arr[i] = api.Grad3F(base + 4 * i * d * h * w, 1, w, w * h)
+        arr[i] = cls(base + es * i * d * h * w, 1, w, w * h)
     return arr
 
 
@@ -565,7 +586,11 @@ def _make_function3d():
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
-                _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr())
+                st = _sample_type(torch, x.dtype)
+                if st is None:
+                    _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr())
+                else:
+                    _context(x.device, work).enqueue_ssim3h(params, n, data_range, st, sums.data_ptr())
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
@@ -582,15 +607,19 @@ def _make_function3d():
                 return None, None, None
             params, n = _params3d(x, y)
             g = grad_out.to(torch.float32).reshape(-1).contiguous()
-            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
             gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
             if n:
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
+                st = _sample_type(torch, x.dtype)
                 ga = _grad_volumes(gx, n, d, h, w) if want_x else None
                 gb = _grad_volumes(gy, n, d, h, w) if want_y else None
-                _context(x.device, work).enqueue_ssim3f_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb)
+                if st is None:
+                    _context(x.device, work).enqueue_ssim3f_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb)
+                else:
+                    _context(x.device, work).enqueue_ssim3h_grad(params, n, ctx.data_range, st, g.data_ptr(), ga, gb)
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None
@@ -603,18 +632,21 @@ def ssim3d(x, y, data_range=1.0):
     (sigma 1.5, clamped edges on every axis), any strides (each volume is addressed in place, no copy): a float32 tensor of shape
     x.shape[:-3].  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that need it.  It runs on
     torch's current stream through the cached context, as ssim() does.  TypeError: not tensors, float16 / bfloat16 tensors (the 3-D path
-    is float32 for now), any other dtype.  ValueError: CPU tensors, differing shapes or devices, fewer than 3 dimensions, empty volumes, a
-    data_range that is not finite and > 0.  Not ssim() on a 5-D tensor: that is one 2-D SSIM per slice."""
+    is float32 for now: ssim3d_amp() takes them), any other dtype.  ValueError: CPU tensors, differing shapes or devices, fewer than 3
+    dimensions, empty volumes, a data_range that is not finite and > 0.  Not ssim() on a 5-D tensor: that is one 2-D SSIM per slice."""
+    return _ssim3d(x, y, _check3d(x, y, data_range))
+
+
+def _ssim3d(x, y, r):
     global _function3d
-    r = _check3d(x, y, data_range)
     if _function3d is None:
         _function3d = _make_function3d()
     return _function3d.apply(x, y, r)
 
 
 class SSIM3DLoss(object):
-    """1 - ssim3d(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per volume).  A plain callable: it has no
-    parameters."""
+    """1 - ssim3d_amp(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per volume).  A plain callable: it has no
+    parameters.  float32, float16 or bfloat16 tensors, as ssim3d_amp(); the loss is float32 at every input dtype."""
 
     def __init__(self, data_range=1.0, reduction="mean"):
         if reduction not in ("mean", "none"):
@@ -622,7 +654,7 @@ class SSIM3DLoss(object):
         self.data_range, self.reduction = data_range, reduction
 
     def __call__(self, x, y):
-        loss = 1.0 - ssim3d(x, y, self.data_range)
+        loss = 1.0 - ssim3d_amp(x, y, self.data_range)
         return loss.mean() if self.reduction == "mean" else loss
 
 
@@ -661,7 +693,11 @@ def _make_map_function3d():
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
-                _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr())
+                st = _sample_type(torch, x.dtype)
+                if st is None:
+                    _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr())
+                else:
+                    _context(x.device, work).enqueue_ssim3h(params, n, data_range, st, sums.data_ptr())
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
@@ -678,16 +714,20 @@ def _make_map_function3d():
                 return None, None, None
             params, n = _params3d(x, y)
             g = grad_out if grad_out.dtype == torch.float32 else grad_out.to(torch.float32)      # read in place, through its own strides
-            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
             gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
             if n:
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
+                st = _sample_type(torch, x.dtype)
                 maps = _grad_out_volumes(g, n)
                 ga = _grad_volumes(gx, n, d, h, w) if want_x else None
                 gb = _grad_volumes(gy, n, d, h, w) if want_y else None
-                _context(x.device, work).enqueue_ssim3f_map_grad(params, n, ctx.data_range, maps, ga, gb)
+                if st is None:
+                    _context(x.device, work).enqueue_ssim3f_map_grad(params, n, ctx.data_range, maps, ga, gb)
+                else:
+                    _context(x.device, work).enqueue_ssim3h_map_grad(params, n, ctx.data_range, st, maps, ga, gb)
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None
@@ -704,8 +744,38 @@ def ssim3d_map(x, y, data_range=1.0):
 
         m = ssim3d_map(x, y)                                  # (N, C, D, H, W)
         loss = 1 - (mask * m).sum() / mask.sum()              # SSIM inside a brain mask"""
+    return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map"))
+
+
+def _ssim3d_map(x, y, r):
     global _map_function3d
-    r = _check3d(x, y, data_range, "ssim3d_map")
     if _map_function3d is None:
         _map_function3d = _make_map_function3d()
     return _map_function3d.apply(x, y, r)
+
+
+# ---- volumes: float16 and bfloat16 ----------------------------------------------------------------------------------------------------------
+# ssim3d_amp and ssim3d_map_amp are ssim3d and ssim3d_map without their refusal of 16-bit tensors (the top of this file has why there are
+# two names): float32 pairs take exactly the path above, float16 and bfloat16 pairs the rmgr_ssim_hip_*_ssim3h* entries.
+
+def ssim3d_amp(x, y, data_range=1.0):
+    """ssim3d() for tensors as they come under mixed precision: two GPU tensors of identical shape (..., D, H, W), both float32, both
+    float16 or both bfloat16, any strides (each volume is addressed in place, no copy or widening): a float32 tensor of shape
+    x.shape[:-3] at every input dtype.  float32 tensors: exactly ssim3d().  float16 and bfloat16: the value has the bits of
+    ssim3d(x.float(), y.float()), the gradient has the inputs' dtype and is that call's float32 gradient rounded once, by the kernel
+    (see the top of this file for autocast and loss scaling).  Errors: as ssim3d(), under this function's name, except that a mixed pair
+    is a TypeError and two float16 or two bfloat16 CPU tensors are a TypeError too: 16-bit tensors are taken on a GPU only (one of the
+    two on a GPU: the ValueError)."""
+    return _ssim3d(x, y, _check3d(x, y, data_range, "ssim3d_amp", half=True))
+
+
+def ssim3d_map_amp(x, y, data_range=1.0):
+    """ssim3d_map() for tensors as they come under mixed precision: two float32, two float16 or two bfloat16 GPU tensors of identical
+    shape (..., D, H, W), any strides: the per-voxel map, float32 of shape x.shape at every input dtype (16-bit inputs: the bits of
+    ssim3d_map(x.float(), y.float())).  The backward reads grad_out per voxel, in place, as ssim3d_map's does, keeps x and y, not the
+    map, and returns the gradient in the inputs' dtype, the float32 value rounded once.  Errors: as ssim3d_amp(), under this function's
+    name.
+
+        m = ssim3d_map_amp(x, y)                              # x, y: (N, C, D, H, W) bfloat16; m: float32
+        loss = 1 - (mask * m).sum() / mask.sum()"""
+    return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map_amp", half=True))
