@@ -38,6 +38,9 @@
  *                                      counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim3h, rmgr_ssim_hip_compute_ssim3h_device / _host, rmgr_ssim_hip_enqueue_ssim3h_grad,
  *   rmgr_ssim_hip_enqueue_ssim3h_map_grad      the same three for float16 / bfloat16 VOLUMES: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssim3f_win, rmgr_ssim_hip_compute_ssim3f_win_device / _host, rmgr_ssim_hip_enqueue_ssim3f_win_grad,
+ *   rmgr_ssim_hip_enqueue_ssim3f_win_map_grad  the float32 VOLUME entries under a caller-chosen window (size, sigma, box): no reference
+ *                                      counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -828,7 +831,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* ctx
  *         but _host -- all checked before any device is touched.  ENODEV: no device.
  *
  * Follow-ups, not in this interface: a caller-chosen window (the _win entries), float16 / bfloat16 volumes and multi-scale SSIM of
- * volumes.  (The 16-bit volumes have since arrived under the ssim3h names, below.)
+ * volumes.  (The 16-bit volumes have since arrived under the ssim3h names, below, and the caller-chosen window for float32 volumes
+ * under the ssim3f_win names, further below.)
  */
 typedef struct rmgr_ssim_hip_Img3F {
     const float* topLeft;
@@ -896,6 +900,55 @@ typedef struct rmgr_ssim_hip_GradOut3F {
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                                    float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
                                                    const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
+
+/*
+ * SSIM of float32 VOLUMES under a caller-chosen WINDOW: the five entries of the float32 volume family -- _enqueue_ssim3f,
+ * _compute_ssim3f_device, _compute_ssim3f_host, _enqueue_ssim3f_grad, _enqueue_ssim3f_map_grad -- with one more argument, `window`, after
+ * dataRange: the rmgr_ssim_hip_Window of the 2-D _win entries, unchanged.  What MONAI, torchmetrics and pytorch-msssim call win_size /
+ * kernel_size / sigma with spatial_dims = 3, and the 7-tap box skimage applies to n-D arrays; the window for volumes that are thin along
+ * one axis (clips of 8 to 16 frames, slabs of a few slices), where an 11-tap clamped window is mostly border.  No reference counterpart:
+ * tests/ssim3k_model.py restates it in float64.  Additions only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ *   Window   size is 3, 5, 7, 9 or 11 taps on ALL THREE axes (the window is isotropic); R = (size - 1) / 2.  The taps are those of the 2-D
+ *            _win entries, bit for bit: GAUSSIAN taps normalised in double in the order i = 0 .. R, a UNIFORM tap float(1.0 / size).
+ *            A NULL window means {11, GAUSSIAN, 1.5f}.
+ *   Everything else is the text of rmgr_ssim_hip_enqueue_ssim3f (and _ssim3f_grad, _ssim3f_map_grad) with 5 replaced by R: clamped edges
+ *            on every axis and same-size output; ONE centre per volume; the x pass centre tap first on folded symmetric sums, the y pass
+ *            and the z pass in source order with the first product plain; fp32 arithmetic without contraction; fixed cells of 16 x 16 x 8
+ *            voxels at absolute positions, one writer per voxel, no floating-point atomics; 12 / 16 bytes per voxel of coefficient scratch
+ *            in sub-batches of about 1 GB; 64-bit offsets and arbitrary signed strides; Gt, the adjoint of the clamped window -- the R
+ *            results beyond each end fold onto the end voxel: tail[d] = g_d + ... + g_R and the total of all taps are summed in double and
+ *            rounded once --, down to 1 x 1 x 1.
+ *   Identity with the fixed-window entries  {11, GAUSSIAN, 1.5f} and a NULL window give the BITS of the entries without _win: value, map,
+ *            sums and both gradient forms.
+ *   Identity of the two gradient forms  a gMap whose every element is float(double(gOut[i]) / (double(W) * double(H) * double(D))) gives the
+ *            BITS of _enqueue_ssim3f_win_grad for gOut[i] under the same window.
+ *   Determinism  that of ssim3f: the same bits alone or anywhere in a batch, at any z-chunk depth and after any sub-batch split, on every
+ *            call, through every entry point, with one gradient or both, and for any view compared with the same voxels stored densely.
+ *   Reach    a window reads nothing beyond its radius: a NaN sample makes NaN exactly the (2R + 1)^3 map voxels and the (4R + 1)^3
+ *            gradient voxels around it, clipped to the volume (clamping taken into account); a NaN in gMap reaches (2R + 1)^3 gradient
+ *            voxels.  A window of 3 taps is not a zero-padded 11-tap window.
+ *   Borders  box windows here CLAMP at the borders where skimage and monodepth-style code reflect or crop: the interior is identical, the
+ *            outermost R voxels of every axis differ.
+ *   Accuracy measured per window against the float64 model: tests/ssim3k_model.py (EMU_*, TOL_FACTOR) and DESIGN.md section 21.
+ *
+ * Arguments, EINVAL / ENODEV rules, sub-batches, scratch and stream behaviour are those of the entry without _win.  Additional EINVAL,
+ * checked before any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
+ *
+ * Follow-up, not in this interface: float16 / bfloat16 volumes (the ssim3h entries) keep the fixed window {11, GAUSSIAN, 1.5f}.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                              float dataRange, const rmgr_ssim_hip_Window* window, double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_win_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                     float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_win_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                   float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_win_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                   float dataRange, const rmgr_ssim_hip_Window* window, const float* gradOutDevice,
+                                                   const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_win_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                       float dataRange, const rmgr_ssim_hip_Window* window, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
+                                                       const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
 
 /*
  * SSIM of `count` pairs of float16 / bfloat16 VOLUMES of one size under the three-dimensional window, its gradient and the gradient of its

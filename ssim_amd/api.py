@@ -228,6 +228,8 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssim3f_map_grad",
     "rmgr_ssim_hip_enqueue_ssim3h", "rmgr_ssim_hip_compute_ssim3h_device", "rmgr_ssim_hip_compute_ssim3h_host", "rmgr_ssim_hip_enqueue_ssim3h_grad",
     "rmgr_ssim_hip_enqueue_ssim3h_map_grad",
+    "rmgr_ssim_hip_enqueue_ssim3f_win", "rmgr_ssim_hip_compute_ssim3f_win_device", "rmgr_ssim_hip_compute_ssim3f_win_host",
+    "rmgr_ssim_hip_enqueue_ssim3f_win_grad", "rmgr_ssim_hip_enqueue_ssim3f_win_map_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -318,6 +320,11 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssim3f_host": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssim3f_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, vp, ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
         "rmgr_ssim_hip_enqueue_ssim3f_map_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, ctypes.POINTER(GradOut3F), ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
+        "rmgr_ssim_hip_enqueue_ssim3f_win": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, vp],
+        "rmgr_ssim_hip_compute_ssim3f_win_device": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssim3f_win_host": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssim3f_win_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, vp, ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
+        "rmgr_ssim_hip_enqueue_ssim3f_win_map_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, ctypes.POINTER(GradOut3F), ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
         "rmgr_ssim_hip_enqueue_ssim3h": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, vp],
         "rmgr_ssim_hip_compute_ssim3h_device": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_compute_ssim3h_host": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
@@ -711,21 +718,30 @@ def _params3f_of(a, b, map_ptr=None):
                          b.ctypes.data, (b.strides[2] // 4, b.strides[1] // 4, b.strides[0] // 4), map_ptr)
 
 
-def compute_ssim3f(a, b, data_range, want_map=False, ctx=None):
+def _ssim3f_host(handle, count, params, data_range, window, out):
+    """rmgr_ssim_hip_compute_ssim3f_host, or -- a window given -- rmgr_ssim_hip_compute_ssim3f_win_host."""
+    lib = load_library()
+    if window is None:
+        _check("rmgr_ssim_hip_compute_ssim3f_host", lib.rmgr_ssim_hip_compute_ssim3f_host(handle, count, params, data_range, out))
+    else:
+        _check("rmgr_ssim_hip_compute_ssim3f_win_host", lib.rmgr_ssim_hip_compute_ssim3f_win_host(handle, count, params, data_range, _window_ref(window), out))
+
+
+def compute_ssim3f(a, b, data_range, want_map=False, ctx=None, window=None):
     """SSIM of two D x H x W float32 host volumes at `data_range` under the three-dimensional 11-tap window (any strides numpy can
-    express, negative ones included) through rmgr_ssim_hip_compute_ssim3f_host.  Returns (float32 value, D x H x W float32 map or None)."""
+    express, negative ones included) through rmgr_ssim_hip_compute_ssim3f_host; window (a Window, make_window): through
+    rmgr_ssim_hip_compute_ssim3f_win_host under that window on all three axes.  Returns (float32 value, D x H x W float32 map or None)."""
     a, b = _f32_volume(a), _f32_volume(b)
     assert a.shape == b.shape
     m = np.empty(a.shape, np.float32) if want_map else None
     params = (Params3F * 1)()
     params[0] = _params3f_of(a, b, m.ctypes.data if want_map else None)
     out = (ctypes.c_float * 1)()
-    _check("rmgr_ssim_hip_compute_ssim3f_host",
-           load_library().rmgr_ssim_hip_compute_ssim3f_host(ctx.handle if ctx is not None else None, 1, params, data_range, out))
+    _ssim3f_host(ctx.handle if ctx is not None else None, 1, params, data_range, window, out)
     return np.float32(out[0]), m
 
 
-def compute_ssim3f_batch(pairs, data_range, ctx=None):
+def compute_ssim3f_batch(pairs, data_range, ctx=None, window=None):
     """compute_ssim3f() of many host pairs of one size in one call (no maps): a float32 array."""
     pairs = [(_f32_volume(a), _f32_volume(b)) for a, b in pairs]
     n = len(pairs)
@@ -733,8 +749,7 @@ def compute_ssim3f_batch(pairs, data_range, ctx=None):
     for i, (a, b) in enumerate(pairs):
         params[i] = _params3f_of(a, b)
     out = (ctypes.c_float * max(n, 1))()
-    _check("rmgr_ssim_hip_compute_ssim3f_host",
-           load_library().rmgr_ssim_hip_compute_ssim3f_host(ctx.handle if ctx is not None else None, n, params, data_range, out))
+    _ssim3f_host(ctx.handle if ctx is not None else None, n, params, data_range, window, out)
     return np.array(out[:n], np.float32)
 
 
@@ -1126,22 +1141,37 @@ class Context(object):
             _check("rmgr_ssim_hip_enqueue_ssimf_win_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_win_grad(
                 self.handle, count, params_array, data_range, _window_ref(window), grad_out_dev_ptr, grad_a, grad_b))
 
-    def ssim3f_device(self, params_array, count, data_range):
+    # The float32 volume family takes window=None (the engine's 11-tap Gaussian of sigma 1.5: the entry without _win) or a Window
+    # (make_window): the _win entry under that window on all three axes.
+
+    def ssim3f_device(self, params_array, count, data_range, window=None):
         """SSIM of `count` device-resident pairs of float32 volumes (a Params3F array) under the three-dimensional window through
-        rmgr_ssim_hip_compute_ssim3f_device: a float32 array."""
+        rmgr_ssim_hip_compute_ssim3f_device (window: _ssim3f_win_device): a float32 array."""
         out = (ctypes.c_float * max(count, 1))()
-        _check("rmgr_ssim_hip_compute_ssim3f_device", self.lib.rmgr_ssim_hip_compute_ssim3f_device(self.handle, count, params_array, data_range, out))
+        if window is None:
+            _check("rmgr_ssim_hip_compute_ssim3f_device", self.lib.rmgr_ssim_hip_compute_ssim3f_device(self.handle, count, params_array, data_range, out))
+        else:
+            _check("rmgr_ssim_hip_compute_ssim3f_win_device", self.lib.rmgr_ssim_hip_compute_ssim3f_win_device(
+                self.handle, count, params_array, data_range, _window_ref(window), out))
         return np.array(out[:count], np.float32)
 
-    def enqueue_ssim3f(self, params_array, count, data_range, sums_dev_ptr):
-        """rmgr_ssim_hip_enqueue_ssim3f: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
-        _check("rmgr_ssim_hip_enqueue_ssim3f", self.lib.rmgr_ssim_hip_enqueue_ssim3f(self.handle, count, params_array, data_range, sums_dev_ptr))
+    def enqueue_ssim3f(self, params_array, count, data_range, sums_dev_ptr, window=None):
+        """rmgr_ssim_hip_enqueue_ssim3f (window: _ssim3f_win): per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssim3f", self.lib.rmgr_ssim_hip_enqueue_ssim3f(self.handle, count, params_array, data_range, sums_dev_ptr))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssim3f_win", self.lib.rmgr_ssim_hip_enqueue_ssim3f_win(
+                self.handle, count, params_array, data_range, _window_ref(window), sums_dev_ptr))
 
-    def enqueue_ssim3f_grad(self, params_array, count, data_range, grad_out_dev_ptr, grad_a=None, grad_b=None):
-        """rmgr_ssim_hip_enqueue_ssim3f_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes into the volumes the
+    def enqueue_ssim3f_grad(self, params_array, count, data_range, grad_out_dev_ptr, grad_a=None, grad_b=None, window=None):
+        """rmgr_ssim_hip_enqueue_ssim3f_grad (window: _ssim3f_win_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes into the volumes the
         Grad3F arrays grad_a / grad_b describe (None: not wanted), from `count` floats dLoss/dS_i in device memory; asynchronous, written
         not accumulated."""
-        _check("rmgr_ssim_hip_enqueue_ssim3f_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_grad(self.handle, count, params_array, data_range, grad_out_dev_ptr, grad_a, grad_b))
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssim3f_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_grad(self.handle, count, params_array, data_range, grad_out_dev_ptr, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssim3f_win_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_win_grad(
+                self.handle, count, params_array, data_range, _window_ref(window), grad_out_dev_ptr, grad_a, grad_b))
 
     def ssimh_device(self, params_array, count, data_range, sample_type):
         """SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_ssimh_device: a
@@ -1151,12 +1181,16 @@ class Context(object):
             self.handle, count, params_array, sample_type_code(sample_type), data_range, out))
         return np.array(out[:count], np.float32)
 
-    def enqueue_ssim3f_map_grad(self, params_array, count, data_range, grad_out_maps, grad_a=None, grad_b=None):
-        """rmgr_ssim_hip_enqueue_ssim3f_map_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes for a per-voxel
+    def enqueue_ssim3f_map_grad(self, params_array, count, data_range, grad_out_maps, grad_a=None, grad_b=None, window=None):
+        """rmgr_ssim_hip_enqueue_ssim3f_map_grad (window: _ssim3f_win_map_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes for a per-voxel
         upstream gradient: grad_out_maps is a GradOut3F array of `count` float32 volumes dLoss/dssim_i(p) in device memory (any step /
         stride / sliceStride, 0 included); asynchronous, written not accumulated."""
-        _check("rmgr_ssim_hip_enqueue_ssim3f_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_map_grad(
-            self.handle, count, params_array, data_range, grad_out_maps, grad_a, grad_b))
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssim3f_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_map_grad(
+                self.handle, count, params_array, data_range, grad_out_maps, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssim3f_win_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_win_map_grad(
+                self.handle, count, params_array, data_range, _window_ref(window), grad_out_maps, grad_a, grad_b))
 
     def ssim3h_device(self, params_array, count, data_range, sample_type):
         """SSIM of `count` device-resident pairs of float16 / bfloat16 volumes (a Params3H array) under the three-dimensional window

@@ -1,6 +1,7 @@
 // ssim3f_abi.cpp -- the entry points of the C ABI for float32 VOLUMES: SSIM under the three-dimensional window, its gradient and the
-// gradient of its map for a per-voxel upstream gradient (rmgr_ssim_hip_*_ssim3f*).  The definition is in include/rmgr/ssim-hip.h, the
-// kernels in ssim3f_kernels.hip and ssim3w_kernels.hip.
+// gradient of its map for a per-voxel upstream gradient (rmgr_ssim_hip_*_ssim3f*), each under the engine's window and, _win, under the
+// caller's.  The definition is in include/rmgr/ssim-hip.h, the kernels in ssim3f_kernels.hip and ssim3w_kernels.hip (11 taps) and in
+// ssim3k_kernels.hip (3, 5, 7 and 9 taps).
 //
 // The flow is the one of ssim_samples_abi.cpp, written for three strides: validation before any device is touched, sub-batches under
 // kScratchCap of device scratch (cell partials, staged volumes and maps; the backward's coefficient volumes) with at least one volume
@@ -14,6 +15,7 @@
 #include "ssim3_flow.h"
 #include "ssim3f_kernels.h"
 #include "ssim3w_kernels.h"
+#include "ssim3k_kernels.h"
 
 #include <cmath>
 
@@ -26,6 +28,22 @@ using ssim_hip::Pair3FDesc;
 using ssim_hip::Grad3FDesc;
 using ssim_hip::GradOut3FDesc;
 using ssim_hip::Geometry3F;
+
+// The window of a launch: its radius and taps, centre first (ssimk_kernels.h: window_taps).  Radius 5 runs on the kernels of
+// ssim3f_kernels.hip / ssim3w_kernels.hip, the smaller ones on ssim3k_kernels.hip.
+struct Window3 {
+    uint32_t radius;
+    float    gf[ssim_hip::kSKMaxRadius + 1];
+};
+
+// The engine's window, that of every entry without _win: 11 taps, Gaussian, sigma 1.5.
+Window3 default_window()
+{
+    Window3 w;
+    w.radius = 5;
+    ssim_hip::window_taps(5, ssim_hip::kSKGaussian, 1.5f, w.gf);
+    return w;
+}
 
 // ---- validation, before any device is touched -----------------------------------------------------------------------------------------------
 
@@ -43,6 +61,18 @@ int validate3f(uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataR
     }
     if (ssim_hip::ssim3f_max_count(W, H, D) == 0) return EINVAL;
     return 0;
+}
+
+// The window of a _win entry: NULL is the engine's; else size 3, 5, 7, 9 or 11, a known kind and -- Gaussian -- a finite sigma > 0.
+int window_validate(const rmgr_ssim_hip_Window* window, Window3& w)
+{
+    if (window == NULL) { w = default_window(); return 0; }
+    const uint32_t size = window->size;
+    if (size < 3 || size > 11 || (size & 1u) == 0) return EINVAL;
+    if (window->kind != RMGR_SSIM_HIP_WINDOW_GAUSSIAN && window->kind != RMGR_SSIM_HIP_WINDOW_UNIFORM) return EINVAL;
+    w.radius = (size - 1) / 2;
+    return ssim_hip::window_taps(w.radius, window->kind == RMGR_SSIM_HIP_WINDOW_UNIFORM ? ssim_hip::kSKUniform : ssim_hip::kSKGaussian, window->sigma, w.gf)
+               ? 0 : EINVAL;
 }
 
 int validate_grads3f(uint32_t count, const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)
@@ -76,17 +106,23 @@ Pair3FDesc make_desc(const rmgr_ssim_hip_Params3F& p, bool with_map)
 uint64_t partials_per_volume(uint32_t W, uint32_t H, uint32_t D) { return ssim_hip::plan3f(W, H, D, 1, 0).cells_per_volume() * sizeof(double); }
 
 // Enqueues n pairs (descriptors in host memory, volumes on the device): descriptor upload, walk, reduction into sums[0 .. n-1].
-int enqueue_volumes(rmgr_ssim_hip_Context* c, float range, uint32_t n, const Pair3FDesc* d, uint32_t W, uint32_t H, uint32_t D, double* sums)
+// The cells (and with them the partials) are the same for every radius; a smaller window's chunks pay fewer warm-up slices.
+int enqueue_volumes(rmgr_ssim_hip_Context* c, float range, const Window3& win, uint32_t n, const Pair3FDesc* d, uint32_t W, uint32_t H, uint32_t D, double* sums)
 {
-    const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+    const Geometry3F geo = ssim_hip::plan3k(win.radius, W, H, D, n, c->cu_count);
     int rc;
     if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_volume() * n)))) return rc;
     return ring_launch(c, n * sizeof(Pair3FDesc),
         [&](uint8_t* pin) { memcpy(pin, d, n * sizeof(Pair3FDesc)); },
-        [&](const uint8_t* dev) { return ssim_hip::launch_ssim3f(geo, reinterpret_cast<const Pair3FDesc*>(dev), range, c->sf_partials, sums, c->stream); });
+        [&](const uint8_t* dev) {
+            const Pair3FDesc* descs = reinterpret_cast<const Pair3FDesc*>(dev);
+            if (win.radius == 5)
+                return ssim_hip::launch_ssim3f(geo, descs, range, c->sf_partials, sums, c->stream, win.gf);
+            return ssim_hip::launch_ssim3k(win.radius, win.gf, geo, descs, range, c->sf_partials, sums, c->stream);
+        });
 }
 
-int enqueue_all(rmgr_ssim_hip_Context* c, float range, uint32_t count, const rmgr_ssim_hip_Params3F* params, double* sums)
+int enqueue_all(rmgr_ssim_hip_Context* c, float range, const Window3& win, uint32_t count, const rmgr_ssim_hip_Params3F* params, double* sums)
 {
     const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
     try {
@@ -96,7 +132,7 @@ int enqueue_all(rmgr_ssim_hip_Context* c, float range, uint32_t count, const rmg
             const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), partials_per_volume(W, H, D), false, staged);
             d.resize(n);
             for (uint32_t i = 0; i < n; ++i) d[i] = make_desc(params[i0 + i], true);
-            const int rc = enqueue_volumes(c, range, n, &d[0], W, H, D, sums + i0);
+            const int rc = enqueue_volumes(c, range, win, n, &d[0], W, H, D, sums + i0);
             if (rc) return rc;
             i0 += n;
         }
@@ -108,7 +144,7 @@ int enqueue_all(rmgr_ssim_hip_Context* c, float range, uint32_t count, const rmg
 
 // The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the volumes are copied (each
 // volume's sample range) into c->stage_a, a pair's map is written densely into it as well and copied back at its own strides.
-int blocking(rmgr_ssim_hip_Context* c, float range, uint32_t count, const rmgr_ssim_hip_Params3F* params, float* ssim, bool stage)
+int blocking(rmgr_ssim_hip_Context* c, float range, const Window3& win, uint32_t count, const rmgr_ssim_hip_Params3F* params, float* ssim, bool stage)
 {
     const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
     const double voxels = (double)W * (double)H * (double)D;
@@ -144,7 +180,7 @@ int blocking(rmgr_ssim_hip_Context* c, float range, uint32_t count, const rmgr_s
                     off += round64((uint64_t)W * H * D * 4);
                 }
             }
-            if ((rc = enqueue_volumes(c, range, n, &d[0], W, H, D, c->sf_sums_pin + i0))) return rc;
+            if ((rc = enqueue_volumes(c, range, win, n, &d[0], W, H, D, c->sf_sums_pin + i0))) return rc;
             HIP_TRY(hipStreamSynchronize(c->stream));
             for (uint32_t i = 0; i < n && stage; ++i) {
                 const rmgr_ssim_hip_Params3F& p = params[i0 + i];
@@ -160,47 +196,11 @@ int blocking(rmgr_ssim_hip_Context* c, float range, uint32_t count, const rmgr_s
     return 0;
 }
 
-// ---- the gradient ---------------------------------------------------------------------------------------------------------------------------------
+// ---- the gradient and the gradient of the map ---------------------------------------------------------------------------------------------
 // Per sub-batch: the walk that writes the coefficient volumes (3 floats per voxel for one gradient, 4 for both) into c->s3_coef, then the
-// adjoint walk that reads them.  The next sub-batch rewrites the scratch in stream order.
-int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float range, const float* gradOutDevice,
-               const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)
-{
-    const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
-    const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
-    const uint64_t per_volume = (uint64_t)ssim_hip::ssim3f_coef_planes(which) * W * H * D;
-    for (uint32_t i0 = 0; i0 < count;) {
-        uint64_t staged;
-        const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), per_volume * sizeof(float), false, staged);
-        const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
-        int rc;
-        if ((rc = c->s3_coef.grow((size_t)(per_volume * n)))) return rc;
-        const size_t pair_bytes = n * sizeof(Pair3FDesc);
-        rc = ring_launch(c, pair_bytes + n * sizeof(Grad3FDesc),
-            [&](uint8_t* pin) {
-                Pair3FDesc* pd = reinterpret_cast<Pair3FDesc*>(pin);
-                Grad3FDesc* gd = reinterpret_cast<Grad3FDesc*>(pin + pair_bytes);
-                for (uint32_t i = 0; i < n; ++i) {
-                    pd[i] = make_desc(params[i0 + i], false);
-                    Grad3FDesc g = {NULL, 0, 0, 0, NULL, 0, 0, 0};
-                    if (gradA) { const rmgr_ssim_hip_Grad3F& s = gradA[i0 + i]; g.ga = s.topLeft; g.ga_step = s.step; g.ga_stride = s.stride; g.ga_slice = s.sliceStride; }
-                    if (gradB) { const rmgr_ssim_hip_Grad3F& s = gradB[i0 + i]; g.gb = s.topLeft; g.gb_step = s.step; g.gb_stride = s.stride; g.gb_slice = s.sliceStride; }
-                    gd[i] = g;
-                }
-            },
-            [&](const uint8_t* dev) {
-                return ssim_hip::launch_ssim3f_grad(geo, reinterpret_cast<const Pair3FDesc*>(dev), reinterpret_cast<const Grad3FDesc*>(dev + pair_bytes),
-                                                    gradOutDevice + i0, range, which, c->s3_coef, c->stream);
-            });
-        if (rc) return rc;
-        i0 += n;
-    }
-    return 0;
-}
-
-// ---- the gradient of the map --------------------------------------------------------------------------------------------------------------------
-// grad_entry with a third table in the descriptor slot, the GradOut3FDesc of the sub-batch: the first walk reads k per voxel through it
-// (ssim3w_kernels.hip), the adjoint walk is the same launch.  s3_coef is shared with grad_entry in stream order.
+// adjoint walk that reads them.  The next sub-batch rewrites the scratch in stream order.  One flow serves both upstream forms: the scalar
+// form (gradOutDevice) or -- maps -- a third table in the descriptor slot, the GradOut3FDesc of the sub-batch, through which the first walk
+// reads k per voxel (ssim3w_kernels.hip; ssim3k_kernels.hip for the smaller windows).
 int validate_grad_maps3f(uint32_t count, const rmgr_ssim_hip_GradOut3F* maps)
 {
     if (maps == NULL) return EINVAL;
@@ -209,8 +209,8 @@ int validate_grad_maps3f(uint32_t count, const rmgr_ssim_hip_GradOut3F* maps)
     return 0;
 }
 
-int map_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float range, const rmgr_ssim_hip_GradOut3F* maps,
-                   const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)
+int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float range, const Window3& win,
+               const float* gradOutDevice, const rmgr_ssim_hip_GradOut3F* maps, const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)
 {
     const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
     const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
@@ -218,11 +218,11 @@ int map_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip
     for (uint32_t i0 = 0; i0 < count;) {
         uint64_t staged;
         const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), per_volume * sizeof(float), false, staged);
-        const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+        const Geometry3F geo = ssim_hip::plan3k(win.radius, W, H, D, n, c->cu_count);
         int rc;
         if ((rc = c->s3_coef.grow((size_t)(per_volume * n)))) return rc;
         const size_t pair_bytes = n * sizeof(Pair3FDesc), grad_bytes = n * sizeof(Grad3FDesc);
-        rc = ring_launch(c, pair_bytes + grad_bytes + n * sizeof(GradOut3FDesc),
+        rc = ring_launch(c, pair_bytes + grad_bytes + (maps ? n * sizeof(GradOut3FDesc) : 0),
             [&](uint8_t* pin) {
                 Pair3FDesc* pd = reinterpret_cast<Pair3FDesc*>(pin);
                 Grad3FDesc* gd = reinterpret_cast<Grad3FDesc*>(pin + pair_bytes);
@@ -233,14 +233,22 @@ int map_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip
                     if (gradA) { const rmgr_ssim_hip_Grad3F& s = gradA[i0 + i]; g.ga = s.topLeft; g.ga_step = s.step; g.ga_stride = s.stride; g.ga_slice = s.sliceStride; }
                     if (gradB) { const rmgr_ssim_hip_Grad3F& s = gradB[i0 + i]; g.gb = s.topLeft; g.gb_step = s.step; g.gb_stride = s.stride; g.gb_slice = s.sliceStride; }
                     gd[i] = g;
+                    if (!maps) continue;
                     const rmgr_ssim_hip_GradOut3F& m = maps[i0 + i];
                     const GradOut3FDesc o = {m.topLeft, (int64_t)m.step, (int64_t)m.stride, (int64_t)m.sliceStride};
                     od[i] = o;
                 }
             },
             [&](const uint8_t* dev) {
-                return ssim_hip::launch_ssim3w_grad(geo, reinterpret_cast<const Pair3FDesc*>(dev), reinterpret_cast<const Grad3FDesc*>(dev + pair_bytes),
-                                                    reinterpret_cast<const GradOut3FDesc*>(dev + pair_bytes + grad_bytes), range, which, c->s3_coef, c->stream);
+                const Pair3FDesc* pd = reinterpret_cast<const Pair3FDesc*>(dev);
+                const Grad3FDesc* gd = reinterpret_cast<const Grad3FDesc*>(dev + pair_bytes);
+                const GradOut3FDesc* od = maps ? reinterpret_cast<const GradOut3FDesc*>(dev + pair_bytes + grad_bytes) : NULL;
+                const float* g_out = maps ? NULL : gradOutDevice + i0;
+                if (win.radius != 5)
+                    return ssim_hip::launch_ssim3k_grad(win.radius, win.gf, geo, pd, gd, g_out, od, range, which, c->s3_coef, c->stream);
+                if (maps)
+                    return ssim_hip::launch_ssim3w_grad(geo, pd, gd, od, range, which, c->s3_coef, c->stream, win.gf);
+                return ssim_hip::launch_ssim3f_grad(geo, pd, gd, g_out, range, which, c->s3_coef, c->stream, win.gf);
             });
         if (rc) return rc;
         i0 += n;
@@ -248,64 +256,134 @@ int map_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip
     return 0;
 }
 
+// ---- what an entry does once its pairs are valid; `window` is NULL (the engine's window) or the caller's ---------------------------------
+
+int enqueue_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataRange, const rmgr_ssim_hip_Window* window,
+                  double* sumsDevice)
+{
+    Window3 win;
+    const int rc = window_validate(window, win);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, dataRange, win, count, params, sumsDevice);
+}
+
+int device_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataRange, const rmgr_ssim_hip_Window* window,
+                 float* ssim)
+{
+    Window3 win;
+    const int rc = window_validate(window, win);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, dataRange, win, count, params, ssim, false);
+}
+
+int host_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataRange, const rmgr_ssim_hip_Window* window,
+               float* ssim)
+{
+    Window3 win;
+    int rc = window_validate(window, win);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    USE_DEVICE(lease.c);
+    return blocking(lease.c, dataRange, win, count, params, ssim, true);
+}
+
+int grad_entry_checked(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataRange, const rmgr_ssim_hip_Window* window,
+                       const float* gradOutDevice, const rmgr_ssim_hip_GradOut3F* maps, const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)
+{
+    Window3 win;
+    int rc = validate_grads3f(count, gradA, gradB);
+    if (rc) return rc;
+    if (gradOutDevice == NULL && (rc = validate_grad_maps3f(count, maps))) return rc;
+    if ((rc = window_validate(window, win))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return grad_entry(c, count, params, dataRange, win, gradOutDevice, gradOutDevice ? NULL : maps, gradA, gradB);
+}
+
 } // namespace
 
 extern "C" {
+
+// Every entry exists twice: under the engine's window and, _win, under the caller's (include/rmgr/ssim-hip.h: rmgr_ssim_hip_Window).
+// Both run the same flow; the window is one more input.
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                           float dataRange, double* sumsDevice) RMGR_NOEXCEPT
 {
     const int rc = validate3f(count, params, dataRange, sumsDevice);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return enqueue_all(c, dataRange, count, params, sumsDevice);
+    return rc ? rc : enqueue_entry(c, count, params, dataRange, NULL, sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                              float dataRange, const rmgr_ssim_hip_Window* window, double* sumsDevice) RMGR_NOEXCEPT
+{
+    const int rc = validate3f(count, params, dataRange, sumsDevice);
+    return rc ? rc : enqueue_entry(c, count, params, dataRange, window, sumsDevice);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                                  float dataRange, float* ssim) RMGR_NOEXCEPT
 {
     const int rc = validate3f(count, params, dataRange, ssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return blocking(c, dataRange, count, params, ssim, false);
+    return rc ? rc : device_entry(c, count, params, dataRange, NULL, ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                     float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = validate3f(count, params, dataRange, ssim);
+    return rc ? rc : device_entry(c, count, params, dataRange, window, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                                float dataRange, float* ssim) RMGR_NOEXCEPT
 {
-    int rc = validate3f(count, params, dataRange, ssim);
-    if (rc) return rc;
-    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
-    if ((rc = lease.take(c))) return rc;
-    USE_DEVICE(lease.c);
-    return blocking(lease.c, dataRange, count, params, ssim, true);
+    const int rc = validate3f(count, params, dataRange, ssim);
+    return rc ? rc : host_entry(c, count, params, dataRange, NULL, ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3f_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                   float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = validate3f(count, params, dataRange, ssim);
+    return rc ? rc : host_entry(c, count, params, dataRange, window, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                                float dataRange, const float* gradOutDevice,
                                                const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT
 {
-    int rc = validate3f(count, params, dataRange, gradOutDevice);
-    if (rc) return rc;
-    if ((rc = validate_grads3f(count, gradA, gradB))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return grad_entry(c, count, params, dataRange, gradOutDevice, gradA, gradB);
+    const int rc = validate3f(count, params, dataRange, gradOutDevice);
+    return rc ? rc : grad_entry_checked(c, count, params, dataRange, NULL, gradOutDevice, NULL, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_win_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                   float dataRange, const rmgr_ssim_hip_Window* window, const float* gradOutDevice,
+                                                   const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT
+{
+    const int rc = validate3f(count, params, dataRange, gradOutDevice);
+    return rc ? rc : grad_entry_checked(c, count, params, dataRange, window, gradOutDevice, NULL, gradA, gradB);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                                    float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
                                                    const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT
 {
-    int rc = validate3f(count, params, dataRange, gradOutMaps);
-    if (rc) return rc;
-    if ((rc = validate_grads3f(count, gradA, gradB))) return rc;
-    if ((rc = validate_grad_maps3f(count, gradOutMaps))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return map_grad_entry(c, count, params, dataRange, gradOutMaps, gradA, gradB);
+    const int rc = validate3f(count, params, dataRange, gradOutMaps);
+    return rc ? rc : grad_entry_checked(c, count, params, dataRange, NULL, NULL, gradOutMaps, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_win_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                       float dataRange, const rmgr_ssim_hip_Window* window, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
+                                                       const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT
+{
+    const int rc = validate3f(count, params, dataRange, gradOutMaps);
+    return rc ? rc : grad_entry_checked(c, count, params, dataRange, window, NULL, gradOutMaps, gradA, gradB);
 }
 
 } // extern "C"

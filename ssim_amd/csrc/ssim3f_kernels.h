@@ -43,8 +43,9 @@ struct Geometry3F {
 uint32_t ssim3f_max_count(uint32_t width, uint32_t height, uint32_t depth);
 
 // The walk of `count` volumes: chunk_slices chosen so that the workgroups fill the chip's wave slots (cu_count CUs; <= 0: 256) in as
-// few slice-times as possible, 10 warm-up slices per chunk included.  Results do not depend on it.
-Geometry3F plan3f(uint32_t width, uint32_t height, uint32_t depth, uint32_t count, int cu_count);
+// few slice-times as possible, `warmup` warm-up slices per chunk included (twice the window's radius: 10 for the 11-tap window).  Results
+// do not depend on it.
+Geometry3F plan3f(uint32_t width, uint32_t height, uint32_t depth, uint32_t count, int cu_count, uint32_t warmup = 10);
 
 // Floats of coefficient scratch per voxel of the backward: k d_mu, k d_aa, k d_ab, and k d_mu of B when both gradients are wanted.
 inline uint32_t ssim3f_coef_planes(int which) { return which == 3 ? 4u : 3u; }
@@ -53,7 +54,9 @@ inline uint32_t ssim3f_coef_planes(int which) { return which == 3 ? 4u : 3u; }
 //   descs_dev   geo.count descriptors in device memory (map NULL: that pair has no map)
 //   partials    geo.count * geo.cells_per_volume() doubles of device scratch
 //   sums        geo.count doubles: each volume's fp64 sum of its per-voxel values, in a fixed order
-hipError_t launch_ssim3f(const Geometry3F& geo, const Pair3FDesc* descs_dev, float data_range, double* partials, double* sums, hipStream_t stream);
+//   taps        NULL: the engine's 11-tap Gaussian of sigma 1.5; else the six taps of an 11-tap window, centre first (here and below)
+hipError_t launch_ssim3f(const Geometry3F& geo, const Pair3FDesc* descs_dev, float data_range, double* partials, double* sums, hipStream_t stream,
+                         const float* taps = NULL);
 
 // The second half of launch_ssim3f alone: each volume's cell partials summed in a fixed order into sums[0 .. geo.count-1].  The walk that
 // fills `partials` is the caller's (ssim3h_kernels.hip: 16-bit samples).
@@ -65,17 +68,17 @@ hipError_t launch_ssim3f_reduce(const Geometry3F& geo, const double* partials, d
 //   which   1: dLoss/dA into ga; 2: dLoss/dB into gb; 3: both, each with the bits it has alone
 // Gradient volumes are written, not accumulated; every voxel by exactly one work-item.
 hipError_t launch_ssim3f_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, const float* g_out,
-                              float data_range, int which, float* coef, hipStream_t stream);
+                              float data_range, int which, float* coef, hipStream_t stream, const float* taps = NULL);
 
 // The second half of launch_ssim3f_grad alone: the adjoint walk that reads the coefficient volumes in `coef` and writes the gradient
 // volumes.  The walk that fills `coef` is the caller's (ssim3w_kernels.hip: the per-voxel upstream gradient).
 hipError_t launch_ssim3f_adjoint(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, float data_range, int which,
-                                 const float* coef, hipStream_t stream);
+                                 const float* coef, hipStream_t stream, const float* taps = NULL);
 
 // What a walk of this file's shape takes by value besides its geometry: C1, C2 and the six taps (centre first) launch_ssim3f and
 // launch_ssim3f_grad run with.  false: a data_range or a geometry those launches refuse.
 struct Walk3FConstants { float c1, c2, gf[6]; };
-bool ssim3f_walk_constants(const Geometry3F& geo, float data_range, Walk3FConstants& out);
+bool ssim3f_walk_constants(const Geometry3F& geo, float data_range, Walk3FConstants& out, const float* taps = NULL);
 
 } // namespace ssim_hip
 

@@ -419,7 +419,7 @@ void constants3f(float data_range, float& c1, float& c2)      // ssimf_constants
     c2 = (float)((0.03 * R) * (0.03 * R));
 }
 
-bool fill_args(K3Args& ka, const Geometry3F& geo, float data_range)
+bool fill_args(K3Args& ka, const Geometry3F& geo, float data_range, const float* taps)
 {
     if (!(data_range > 0.0f) || !std::isfinite(data_range) || geo.count == 0 || geo.count > ssim3f_max_count(geo.width, geo.height, geo.depth)) return false;
     if ((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count > kMaxBlocks || geo.chunk_slices % kS3CellZ != 0) return false;
@@ -428,7 +428,8 @@ bool fill_args(K3Args& ka, const Geometry3F& geo, float data_range)
     ka.tiles_x = geo.tiles_x; ka.tiles_y = geo.tiles_y; ka.chunks = geo.chunks; ka.chunk_slices = geo.chunk_slices; ka.cells_z = geo.cells_z;
     ka.range = data_range;
     constants3f(data_range, ka.c1, ka.c2);
-    engine_taps(ka.gf);
+    if (taps) { for (int i = 0; i < 6; ++i) ka.gf[i] = taps[i]; }       // an 11-tap window of the caller's
+    else engine_taps(ka.gf);
     // tail[d] = g_d + ... + g_5 and the sum of all eleven taps: sums of the float taps in double, rounded once
     double t = 0.0;
     for (int i = 5; i >= 0; --i) { t += (double)ka.gf[i]; ka.tail[i] = (float)t; }
@@ -445,7 +446,7 @@ uint32_t ssim3f_max_count(uint32_t width, uint32_t height, uint32_t depth)
     return (uint32_t)std::min<uint64_t>(kMaxBlocks / tiles, 65535);
 }
 
-Geometry3F plan3f(uint32_t width, uint32_t height, uint32_t depth, uint32_t count, int cu_count)
+Geometry3F plan3f(uint32_t width, uint32_t height, uint32_t depth, uint32_t count, int cu_count, uint32_t warmup)
 {
     Geometry3F g;
     g.width = width; g.height = height; g.depth = depth; g.count = count;
@@ -453,7 +454,7 @@ Geometry3F plan3f(uint32_t width, uint32_t height, uint32_t depth, uint32_t coun
     g.tiles_y = (height + kS3Tile - 1) / kS3Tile;
     g.cells_z = (depth + kS3CellZ - 1) / kS3CellZ;
     // four workgroups of four waves per CU (the walk's occupancy): a round; pick the chunk depth (whole cells, doubling) that finishes the launch's workgroups in
-    // the fewest slice-times, 10 warm-up slices included, among those whose grid fits
+    // the fewest slice-times, the warm-up slices (10 for the 11-tap window) included, among those whose grid fits
     const uint64_t slots = (uint64_t)(cu_count > 0 ? cu_count : 256) * 4;
     const uint64_t cols = (uint64_t)g.tiles_x * g.tiles_y * std::max<uint32_t>(count, 1);
     uint64_t best = ~uint64_t(0), best_slices = 0;
@@ -461,7 +462,7 @@ Geometry3F plan3f(uint32_t width, uint32_t height, uint32_t depth, uint32_t coun
         const uint64_t chunks = (depth + slices - 1) / slices;
         if (cols * chunks <= kMaxBlocks) {
             const uint64_t rounds = (cols * chunks + slots - 1) / slots;
-            const uint64_t cost = rounds * (std::min<uint64_t>(slices, depth) + 10);
+            const uint64_t cost = rounds * (std::min<uint64_t>(slices, depth) + warmup);
             if (cost <= best) { best = cost; best_slices = slices; }
         }
         if (slices >= depth) {
@@ -474,11 +475,12 @@ Geometry3F plan3f(uint32_t width, uint32_t height, uint32_t depth, uint32_t coun
     return g;
 }
 
-hipError_t launch_ssim3f(const Geometry3F& geo, const Pair3FDesc* descs_dev, float data_range, double* partials, double* sums, hipStream_t stream)
+hipError_t launch_ssim3f(const Geometry3F& geo, const Pair3FDesc* descs_dev, float data_range, double* partials, double* sums, hipStream_t stream,
+                         const float* taps)
 {
     if (geo.count == 0) return hipSuccess;
     K3Args ka;
-    if (!fill_args(ka, geo, data_range)) return hipErrorInvalidValue;
+    if (!fill_args(ka, geo, data_range, taps)) return hipErrorInvalidValue;
     ka.descs = descs_dev; ka.partials = partials;
     const dim3 grid((uint32_t)((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count)), block(256);
     hipLaunchKernelGGL((ssim3f_walk_kernel<0>), grid, block, 0, stream, ka);
@@ -495,11 +497,11 @@ hipError_t launch_ssim3f_reduce(const Geometry3F& geo, const double* partials, d
 }
 
 hipError_t launch_ssim3f_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, const float* g_out,
-                              float data_range, int which, float* coef, hipStream_t stream)
+                              float data_range, int which, float* coef, hipStream_t stream, const float* taps)
 {
     if (geo.count == 0) return hipSuccess;
     K3Args ka;
-    if (which < 1 || which > 3 || !fill_args(ka, geo, data_range)) return hipErrorInvalidValue;
+    if (which < 1 || which > 3 || !fill_args(ka, geo, data_range, taps)) return hipErrorInvalidValue;
     ka.descs = descs_dev; ka.grads = grads_dev; ka.g_out = g_out; ka.coef = coef;
     const dim3 grid((uint32_t)((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count)), block(256);
     if (which == 1)      hipLaunchKernelGGL((ssim3f_walk_kernel<1>), grid, block, 0, stream, ka);
@@ -507,15 +509,15 @@ hipError_t launch_ssim3f_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev
     else                 hipLaunchKernelGGL((ssim3f_walk_kernel<3>), grid, block, 0, stream, ka);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_ssim3f_adjoint(geo, descs_dev, grads_dev, data_range, which, coef, stream);
+    return launch_ssim3f_adjoint(geo, descs_dev, grads_dev, data_range, which, coef, stream, taps);
 }
 
 hipError_t launch_ssim3f_adjoint(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, float data_range, int which,
-                                 const float* coef, hipStream_t stream)
+                                 const float* coef, hipStream_t stream, const float* taps)
 {
     if (geo.count == 0) return hipSuccess;
     K3Args ka;
-    if (which < 1 || which > 3 || !fill_args(ka, geo, data_range)) return hipErrorInvalidValue;
+    if (which < 1 || which > 3 || !fill_args(ka, geo, data_range, taps)) return hipErrorInvalidValue;
     ka.descs = descs_dev; ka.grads = grads_dev; ka.coef = const_cast<float*>(coef);
     const dim3 grid((uint32_t)((uint64_t)geo.tiles_x * geo.tiles_y * geo.chunks * geo.count)), block(256);
     if (which == 1)      hipLaunchKernelGGL((ssim3f_adjoint_kernel<1>), grid, block, 0, stream, ka);
@@ -524,10 +526,10 @@ hipError_t launch_ssim3f_adjoint(const Geometry3F& geo, const Pair3FDesc* descs_
     return hipGetLastError();
 }
 
-bool ssim3f_walk_constants(const Geometry3F& geo, float data_range, Walk3FConstants& out)
+bool ssim3f_walk_constants(const Geometry3F& geo, float data_range, Walk3FConstants& out, const float* taps)
 {
     K3Args ka;
-    if (!fill_args(ka, geo, data_range)) return false;
+    if (!fill_args(ka, geo, data_range, taps)) return false;
     out.c1 = ka.c1; out.c2 = ka.c2;
     for (int i = 0; i < 6; ++i) out.gf[i] = ka.gf[i];
     return true;

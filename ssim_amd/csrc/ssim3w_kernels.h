@@ -23,9 +23,10 @@ struct GradOut3FDesc {
 //   gouts_dev   geo.count GradOut3FDesc in device memory
 //   which       1: dLoss/dA into ga; 2: dLoss/dB into gb; 3: both, each with the bits it has alone
 //   coef        geo.count * ssim3f_coef_planes(which) * geo.voxels() floats of device scratch
+//   taps        NULL: the engine's window; else the six taps of an 11-tap window, centre first (launch_ssim3f)
 // Gradient volumes are written, not accumulated; every voxel by exactly one work-item.
 hipError_t launch_ssim3w_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, const GradOut3FDesc* gouts_dev,
-                              float data_range, int which, float* coef, hipStream_t stream);
+                              float data_range, int which, float* coef, hipStream_t stream, const float* taps = NULL);
 
 } // namespace ssim_hip
 

@@ -207,11 +207,11 @@ void ssim3w_walk_kernel(const K3WArgs args)
 } // namespace
 
 hipError_t launch_ssim3w_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, const GradOut3FDesc* gouts_dev,
-                              float data_range, int which, float* coef, hipStream_t stream)
+                              float data_range, int which, float* coef, hipStream_t stream, const float* taps)
 {
     if (geo.count == 0) return hipSuccess;
     Walk3FConstants wc;
-    if (which < 1 || which > 3 || !ssim3f_walk_constants(geo, data_range, wc)) return hipErrorInvalidValue;
+    if (which < 1 || which > 3 || !ssim3f_walk_constants(geo, data_range, wc, taps)) return hipErrorInvalidValue;
     K3WArgs ka;
     ka.descs = descs_dev; ka.gouts = gouts_dev; ka.coef = coef;
     ka.width = geo.width; ka.height = geo.height; ka.depth = geo.depth;
@@ -224,7 +224,7 @@ hipError_t launch_ssim3w_grad(const Geometry3F& geo, const Pair3FDesc* descs_dev
     else                 hipLaunchKernelGGL((ssim3w_walk_kernel<3>), grid, block, 0, stream, ka);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_ssim3f_adjoint(geo, descs_dev, grads_dev, data_range, which, coef, stream);
+    return launch_ssim3f_adjoint(geo, descs_dev, grads_dev, data_range, which, coef, stream, taps);
 }
 
 } // namespace ssim_hip

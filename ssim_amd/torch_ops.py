@@ -138,17 +138,18 @@ def _check(x, y, data_range, half=False):
     return r
 
 
-def _window(x, y, win_size, win_sigma, window):
-    """The documented errors of the window arguments, before any GPU call.  Returns None for the defaults (today's path) or an api.Window."""
+def _window(x, y, win_size, win_sigma, window, name="ssim"):
+    """The documented errors of the window arguments (`name`: the function the message names), before any GPU call.  Returns None for
+    the defaults (today's path) or an api.Window."""
     if not isinstance(window, str):
-        raise TypeError("ssim: window must be 'gaussian' or 'uniform', got %s" % type(window).__name__)
+        raise TypeError("%s: window must be 'gaussian' or 'uniform', got %s" % (name, type(window).__name__))
     win = api.make_window(win_size, 1.5 if window == "uniform" else win_sigma, window)      # TypeError / ValueError
     if win.size == 11 and win.kind == api.WINDOW_GAUSSIAN and win.sigma == 1.5:
         return None
     for t in (x, y):
         if str(getattr(t, "dtype", "")) in ("torch.float16", "torch.bfloat16"):
-            raise TypeError("ssim: float16 / bfloat16 tensors keep the fixed window (win_size=11, win_sigma=1.5, window='gaussian'); "
-                            "a configurable window needs float32 tensors")
+            raise TypeError("%s: float16 / bfloat16 tensors keep the fixed window (win_size=11, win_sigma=1.5, window='gaussian'); "
+                            "a configurable window needs float32 tensors" % name)
     return win
 
 
@@ -505,7 +506,12 @@ class MSSSIMLoss(object):
 # (n-D arrays) compute for volumes.  It has a name of its own because ssim() on an (N, C, D, H, W) tensor already has a meaning: N * C * D
 # independent 2-D SSIMs with no window across slices.  The backward is rmgr_ssim_hip_enqueue_ssim3f_grad.  ssim3d and ssim3d_map are
 # float32-only; ssim3d_amp and ssim3d_map_amp (the end of the file) take float16 / bfloat16 volumes as well, on the ssim3h entries, through
-# the same two autograd functions.  The configurable window and a multi-scale form are follow-ups.
+# the same two autograd functions.
+# The window: win_size, win_sigma and window are ssim()'s keywords, checked by the same helper, and mean the same window on all three axes
+# (the rmgr_ssim_hip_*_ssim3f_win* entries; what MONAI, torchmetrics and pytorch-msssim call win_size / kernel_size / sigma with
+# spatial_dims=3, and skimage's 7-tap box).  The defaults are the engine's window and take exactly the path without these arguments; any
+# other window is stored on the autograd context and the backward runs under it.  float16 / bfloat16 volumes keep the fixed window: with
+# them a non-default window is a TypeError.  A multi-scale form is a follow-up.
 
 _function3d = None
 
@@ -578,7 +584,7 @@ def _make_function3d():
 
     class _SSIM3D(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, y, data_range):
+        def forward(ctx, x, y, data_range, win):
             lead, d, h, w = x.shape[:-3], x.shape[-3], x.shape[-2], x.shape[-1]
             params, n = _params3d(x, y)
             sums = torch.empty(n, dtype=torch.float64, device=x.device)
@@ -588,13 +594,13 @@ def _make_function3d():
                     work.wait_stream(cur)
                 st = _sample_type(torch, x.dtype)
                 if st is None:
-                    _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr())
+                    _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr(), **_win_kw(win))
                 else:
                     _context(x.device, work).enqueue_ssim3h(params, n, data_range, st, sums.data_ptr())
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
-            ctx.data_range = data_range
+            ctx.data_range, ctx.win = data_range, win
             return (sums / (float(w) * float(h) * float(d))).to(torch.float32).reshape(lead)
 
         @staticmethod
@@ -604,7 +610,7 @@ def _make_function3d():
             d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
             want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             if not (want_x or want_y):
-                return None, None, None
+                return None, None, None, None
             params, n = _params3d(x, y)
             g = grad_out.to(torch.float32).reshape(-1).contiguous()
             gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
@@ -617,44 +623,52 @@ def _make_function3d():
                 ga = _grad_volumes(gx, n, d, h, w) if want_x else None
                 gb = _grad_volumes(gy, n, d, h, w) if want_y else None
                 if st is None:
-                    _context(x.device, work).enqueue_ssim3f_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb)
+                    _context(x.device, work).enqueue_ssim3f_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb, **_win_kw(ctx.win))
                 else:
                     _context(x.device, work).enqueue_ssim3h_grad(params, n, ctx.data_range, st, g.data_ptr(), ga, gb)
                 if work is not cur:
                     cur.wait_stream(work)
-            return gx, gy, None
+            return gx, gy, None, None
 
     return _SSIM3D
 
 
-def ssim3d(x, y, data_range=1.0):
+def ssim3d(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
     """Per-volume SSIM of two float32 GPU tensors of identical shape (..., D, H, W) under the three-dimensional 11-tap Gaussian window
     (sigma 1.5, clamped edges on every axis), any strides (each volume is addressed in place, no copy): a float32 tensor of shape
     x.shape[:-3].  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that need it.  It runs on
     torch's current stream through the cached context, as ssim() does.  TypeError: not tensors, float16 / bfloat16 tensors (the 3-D path
     is float32 for now: ssim3d_amp() takes them), any other dtype.  ValueError: CPU tensors, differing shapes or devices, fewer than 3
-    dimensions, empty volumes, a data_range that is not finite and > 0.  Not ssim() on a 5-D tensor: that is one 2-D SSIM per slice."""
-    return _ssim3d(x, y, _check3d(x, y, data_range))
+    dimensions, empty volumes, a data_range that is not finite and > 0.  Not ssim() on a 5-D tensor: that is one 2-D SSIM per slice.
+    The window: win_size taps on every one of the three axes (3, 5, 7, 9 or 11), window "gaussian" with win_sigma or "uniform" (a box;
+    win_sigma ignored; edges are clamped, where skimage reflects); the defaults are the engine's window and take exactly the path without
+    these arguments.  TypeError: a win_size that is not an int, a window that is not a str.  ValueError: any other win_size, an unknown
+    window name, a win_sigma that is not finite and > 0."""
+    win = _window(x, y, win_size, win_sigma, window, "ssim3d")
+    return _ssim3d(x, y, _check3d(x, y, data_range), win)
 
 
-def _ssim3d(x, y, r):
+def _ssim3d(x, y, r, win=None):
     global _function3d
     if _function3d is None:
         _function3d = _make_function3d()
-    return _function3d.apply(x, y, r)
+    return _function3d.apply(x, y, r, win)
 
 
 class SSIM3DLoss(object):
     """1 - ssim3d_amp(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per volume).  A plain callable: it has no
-    parameters.  float32, float16 or bfloat16 tensors, as ssim3d_amp(); the loss is float32 at every input dtype."""
+    parameters.  float32, float16 or bfloat16 tensors, as ssim3d_amp(); the loss is float32 at every input dtype.  win_size, win_sigma,
+    window: the window, as ssim3d(), checked here."""
 
-    def __init__(self, data_range=1.0, reduction="mean"):
+    def __init__(self, data_range=1.0, reduction="mean", win_size=11, win_sigma=1.5, window="gaussian"):
         if reduction not in ("mean", "none"):
             raise ValueError("SSIM3DLoss: reduction must be 'mean' or 'none', got %r" % (reduction,))
+        _window(None, None, win_size, win_sigma, window, "SSIM3DLoss")
         self.data_range, self.reduction = data_range, reduction
+        self.win_size, self.win_sigma, self.window = win_size, win_sigma, window
 
     def __call__(self, x, y):
-        loss = 1.0 - ssim3d_amp(x, y, self.data_range)
+        loss = 1.0 - ssim3d_amp(x, y, self.data_range, self.win_size, self.win_sigma, self.window)
         return loss.mean() if self.reduction == "mean" else loss
 
 
@@ -680,7 +694,7 @@ def _make_map_function3d():
 
     class _SSIM3DMap(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, y, data_range):
+        def forward(ctx, x, y, data_range, win):
             d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
             params, n = _params3d(x, y)
             out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
@@ -695,13 +709,13 @@ def _make_map_function3d():
                     work.wait_stream(cur)
                 st = _sample_type(torch, x.dtype)
                 if st is None:
-                    _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr())
+                    _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr(), **_win_kw(win))
                 else:
                     _context(x.device, work).enqueue_ssim3h(params, n, data_range, st, sums.data_ptr())
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
-            ctx.data_range = data_range
+            ctx.data_range, ctx.win = data_range, win
             return out
 
         @staticmethod
@@ -711,7 +725,7 @@ def _make_map_function3d():
             d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
             want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             if not (want_x or want_y):
-                return None, None, None
+                return None, None, None, None
             params, n = _params3d(x, y)
             g = grad_out if grad_out.dtype == torch.float32 else grad_out.to(torch.float32)      # read in place, through its own strides
             gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
@@ -725,57 +739,62 @@ def _make_map_function3d():
                 ga = _grad_volumes(gx, n, d, h, w) if want_x else None
                 gb = _grad_volumes(gy, n, d, h, w) if want_y else None
                 if st is None:
-                    _context(x.device, work).enqueue_ssim3f_map_grad(params, n, ctx.data_range, maps, ga, gb)
+                    _context(x.device, work).enqueue_ssim3f_map_grad(params, n, ctx.data_range, maps, ga, gb, **_win_kw(ctx.win))
                 else:
                     _context(x.device, work).enqueue_ssim3h_map_grad(params, n, ctx.data_range, st, maps, ga, gb)
                 if work is not cur:
                     cur.wait_stream(work)
-            return gx, gy, None
+            return gx, gy, None, None
 
     return _SSIM3DMap
 
 
-def ssim3d_map(x, y, data_range=1.0):
+def ssim3d_map(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
     """Per-voxel SSIM of two float32 GPU tensors of identical shape (..., D, H, W) under the three-dimensional window of ssim3d(), any
     strides (each volume is addressed in place, no copy): a float32 tensor of shape x.shape, the map rmgr_ssim_hip_enqueue_ssim3f
     writes.  Differentiable with respect to x, y or both for ANY upstream gradient: the backward reads grad_out per voxel, in place
     (expanded, sliced and permuted tensors included; another dtype is cast to float32 once) and computes the gradient only for the
-    inputs that need it.  It keeps x and y, not the map.  A zero in grad_out does not hide a NaN in the volumes.  Errors: as ssim3d().
+    inputs that need it.  It keeps x and y, not the map.  A zero in grad_out does not hide a NaN in the volumes.  win_size, win_sigma,
+    window: as ssim3d().  Errors: as ssim3d().
 
         m = ssim3d_map(x, y)                                  # (N, C, D, H, W)
         loss = 1 - (mask * m).sum() / mask.sum()              # SSIM inside a brain mask"""
-    return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map"))
+    win = _window(x, y, win_size, win_sigma, window, "ssim3d_map")
+    return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map"), win)
 
 
-def _ssim3d_map(x, y, r):
+def _ssim3d_map(x, y, r, win=None):
     global _map_function3d
     if _map_function3d is None:
         _map_function3d = _make_map_function3d()
-    return _map_function3d.apply(x, y, r)
+    return _map_function3d.apply(x, y, r, win)
 
 
 # ---- volumes: float16 and bfloat16 ----------------------------------------------------------------------------------------------------------
 # ssim3d_amp and ssim3d_map_amp are ssim3d and ssim3d_map without their refusal of 16-bit tensors (the top of this file has why there are
 # two names): float32 pairs take exactly the path above, float16 and bfloat16 pairs the rmgr_ssim_hip_*_ssim3h* entries.
 
-def ssim3d_amp(x, y, data_range=1.0):
+def ssim3d_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
     """ssim3d() for tensors as they come under mixed precision: two GPU tensors of identical shape (..., D, H, W), both float32, both
     float16 or both bfloat16, any strides (each volume is addressed in place, no copy or widening): a float32 tensor of shape
     x.shape[:-3] at every input dtype.  float32 tensors: exactly ssim3d().  float16 and bfloat16: the value has the bits of
     ssim3d(x.float(), y.float()), the gradient has the inputs' dtype and is that call's float32 gradient rounded once, by the kernel
     (see the top of this file for autocast and loss scaling).  Errors: as ssim3d(), under this function's name, except that a mixed pair
     is a TypeError and two float16 or two bfloat16 CPU tensors are a TypeError too: 16-bit tensors are taken on a GPU only (one of the
-    two on a GPU: the ValueError)."""
-    return _ssim3d(x, y, _check3d(x, y, data_range, "ssim3d_amp", half=True))
+    two on a GPU: the ValueError).  win_size, win_sigma, window: as ssim3d(), for float32 tensors; float16 and bfloat16 tensors keep the
+    fixed window, and any other window with them is a TypeError."""
+    win = _window(x, y, win_size, win_sigma, window, "ssim3d_amp")
+    return _ssim3d(x, y, _check3d(x, y, data_range, "ssim3d_amp", half=True), win)
 
 
-def ssim3d_map_amp(x, y, data_range=1.0):
+def ssim3d_map_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
     """ssim3d_map() for tensors as they come under mixed precision: two float32, two float16 or two bfloat16 GPU tensors of identical
     shape (..., D, H, W), any strides: the per-voxel map, float32 of shape x.shape at every input dtype (16-bit inputs: the bits of
     ssim3d_map(x.float(), y.float())).  The backward reads grad_out per voxel, in place, as ssim3d_map's does, keeps x and y, not the
-    map, and returns the gradient in the inputs' dtype, the float32 value rounded once.  Errors: as ssim3d_amp(), under this function's
-    name.
+    map, and returns the gradient in the inputs' dtype, the float32 value rounded once.  win_size, win_sigma, window: as ssim3d_amp().
+    Errors: as ssim3d_amp(), under this function's name.
 
         m = ssim3d_map_amp(x, y)                              # x, y: (N, C, D, H, W) bfloat16; m: float32
         loss = 1 - (mask * m).sum() / mask.sum()"""
-    return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map_amp", half=True))
+    win = _window(x, y, win_size, win_sigma, window, "ssim3d_map_amp")
+    return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map_amp", half=True), win)
