@@ -41,6 +41,9 @@
  *   rmgr_ssim_hip_enqueue_ssim3f_win, rmgr_ssim_hip_compute_ssim3f_win_device / _host, rmgr_ssim_hip_enqueue_ssim3f_win_grad,
  *   rmgr_ssim_hip_enqueue_ssim3f_win_map_grad  the float32 VOLUME entries under a caller-chosen window (size, sigma, box): no reference
  *                                      counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssim3h_win, rmgr_ssim_hip_compute_ssim3h_win_device / _host, rmgr_ssim_hip_enqueue_ssim3h_win_grad,
+ *   rmgr_ssim_hip_enqueue_ssim3h_win_map_grad  the float16 / bfloat16 VOLUME entries under a caller-chosen window: no reference
+ *                                      counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -831,8 +834,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* ctx
  *         but _host -- all checked before any device is touched.  ENODEV: no device.
  *
  * Follow-ups, not in this interface: a caller-chosen window (the _win entries), float16 / bfloat16 volumes and multi-scale SSIM of
- * volumes.  (The 16-bit volumes have since arrived under the ssim3h names, below, and the caller-chosen window for float32 volumes
- * under the ssim3f_win names, further below.)
+ * volumes.  (The 16-bit volumes have since arrived under the ssim3h names, below, the caller-chosen window for float32 volumes
+ * under the ssim3f_win names and the one for 16-bit volumes under the ssim3h_win names, both further below.)
  */
 typedef struct rmgr_ssim_hip_Img3F {
     const float* topLeft;
@@ -935,7 +938,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_map_grad(rmgr_ssim_hip_Context* ctx, r
  * Arguments, EINVAL / ENODEV rules, sub-batches, scratch and stream behaviour are those of the entry without _win.  Additional EINVAL,
  * checked before any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
  *
- * Follow-up, not in this interface: float16 / bfloat16 volumes (the ssim3h entries) keep the fixed window {11, GAUSSIAN, 1.5f}.
+ * float16 / bfloat16 volumes under a caller-chosen window: the ssim3h_win entries, below.
  */
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3f_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                               float dataRange, const rmgr_ssim_hip_Window* window, double* sumsDevice) RMGR_NOEXCEPT;
@@ -1011,6 +1014,55 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_grad(rmgr_ssim_hip_Context* ctx, rmgr_
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
                                                    rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
                                                    const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
+
+/*
+ * SSIM of float16 / bfloat16 VOLUMES under a caller-chosen WINDOW: the five entries of the 16-bit volume family -- _enqueue_ssim3h,
+ * _compute_ssim3h_device, _compute_ssim3h_host, _enqueue_ssim3h_grad, _enqueue_ssim3h_map_grad -- with one more argument, `window`, after
+ * dataRange: the rmgr_ssim_hip_Window of the float32 _win entries, unchanged.  What a volumetric model trained under mixed precision
+ * needs when its clips or slabs are thin along one axis, or when its metric is MONAI's, torchmetrics' or skimage's 7-tap window: the
+ * 16-bit tensors are read as they are stored, without float32 copies and without a float32 gradient.  No reference counterpart.
+ * Additions only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ * It is the definition of rmgr_ssim_hip_enqueue_ssim3f_win -- and of _enqueue_ssim3f_win_grad and _enqueue_ssim3f_win_map_grad --, word
+ * for word, on samples widened to float32 exactly as the ssim3h entries define widening:
+ *   Window   size 3, 5, 7, 9 or 11 taps on all three axes, GAUSSIAN of any finite sigma > 0 or UNIFORM; the taps of the float32 _win
+ *            entries, bit for bit.  A NULL window means {11, GAUSSIAN, 1.5f}.
+ *   Value    the value, the float32 map and every per-volume fp64 sum have the BITS rmgr_ssim_hip_enqueue_ssim3f_win gives on the widened
+ *            volumes under the same window.
+ *   Gradient  each gradient voxel is the float32 value _enqueue_ssim3f_win_grad / _enqueue_ssim3f_win_map_grad would store for the widened
+ *            volumes under the same window, rounded ONCE, to nearest-even, into the inputs' encoding (float16: subnormals are kept,
+ *            overflow gives Inf; NaN stays NaN in both encodings).  gradOutDevice and rmgr_ssim_hip_GradOut3F stay float32: a loss scale
+ *            arrives before the single rounding.
+ *   Identity with the fixed-window entries  a NULL window and {11, GAUSSIAN, 1.5f} give the BITS of the ssim3h entries without _win:
+ *            value, map, sums and both gradient forms.
+ *   Identity of the two gradient forms  a gMap whose every element is float(double(gOut[i]) / (double(W) * double(H) * double(D))) gives the
+ *            BITS of _enqueue_ssim3h_win_grad for gOut[i] under the same window.
+ *   Everything else is ssim3f_win's: determinism (alone or anywhere in a batch, at any z-chunk depth, after any sub-batch split, as any
+ *            view), the reach of a NaN sample ((2R + 1)^3 map voxels, (4R + 1)^3 gradient voxels, clipped) and of a NaN in gMap
+ *            ((2R + 1)^3), the clamped borders, and the scratch: float32 coefficient volumes, 12 / 16 bytes per voxel, in the scratch the
+ *            float32 entries use, in sub-batches of about 1 GB of it.
+ *
+ * Arguments, strides (in 16-bit samples; the map and gMap in floats), EINVAL / ENODEV rules, sub-batches, scratch and stream behaviour are
+ * those of the ssim3h entry without _win.  Additional EINVAL, checked after that entry's and before any device is touched: a size outside
+ * the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                              rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                              double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_win_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                     rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                     float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_win_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                   rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                   float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                   rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                   const float* gradOutDevice, const rmgr_ssim_hip_Grad3H* gradA,
+                                                   const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                       rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                       const rmgr_ssim_hip_GradOut3F* gradOutMaps, const rmgr_ssim_hip_Grad3H* gradA,
+                                                       const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

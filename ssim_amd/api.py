@@ -230,6 +230,8 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssim3h_map_grad",
     "rmgr_ssim_hip_enqueue_ssim3f_win", "rmgr_ssim_hip_compute_ssim3f_win_device", "rmgr_ssim_hip_compute_ssim3f_win_host",
     "rmgr_ssim_hip_enqueue_ssim3f_win_grad", "rmgr_ssim_hip_enqueue_ssim3f_win_map_grad",
+    "rmgr_ssim_hip_enqueue_ssim3h_win", "rmgr_ssim_hip_compute_ssim3h_win_device", "rmgr_ssim_hip_compute_ssim3h_win_host",
+    "rmgr_ssim_hip_enqueue_ssim3h_win_grad", "rmgr_ssim_hip_enqueue_ssim3h_win_map_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -330,6 +332,11 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssim3h_host": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssim3h_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, vp, ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
         "rmgr_ssim_hip_enqueue_ssim3h_map_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(GradOut3F), ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
+        "rmgr_ssim_hip_enqueue_ssim3h_win": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, vp],
+        "rmgr_ssim_hip_compute_ssim3h_win_device": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssim3h_win_host": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssim3h_win_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, vp, ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
+        "rmgr_ssim_hip_enqueue_ssim3h_win_map_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, ctypes.POINTER(GradOut3F), ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
         "rmgr_ssim_hip_enqueue_ssimf_map_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
         "rmgr_ssim_hip_enqueue_ssimh_map_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, ctypes.POINTER(GradOutF), ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
         "rmgr_ssim_hip_enqueue_ssimf_win": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, vp],
@@ -872,9 +879,20 @@ def _params3h_of(a, b, map_ptr=None):
                          b.ctypes.data, (b.strides[2] // 2, b.strides[1] // 2, b.strides[0] // 2), map_ptr)
 
 
-def compute_ssim3h(a, b, data_range, sample_type=None, want_map=False, ctx=None):
+def _ssim3h_host(handle, count, params, code, data_range, window, out):
+    """rmgr_ssim_hip_compute_ssim3h_host, or -- a window given -- rmgr_ssim_hip_compute_ssim3h_win_host."""
+    lib = load_library()
+    if window is None:
+        _check("rmgr_ssim_hip_compute_ssim3h_host", lib.rmgr_ssim_hip_compute_ssim3h_host(handle, count, params, code, data_range, out))
+    else:
+        _check("rmgr_ssim_hip_compute_ssim3h_win_host", lib.rmgr_ssim_hip_compute_ssim3h_win_host(
+            handle, count, params, code, data_range, _window_ref(window), out))
+
+
+def compute_ssim3h(a, b, data_range, sample_type=None, want_map=False, ctx=None, window=None):
     """SSIM of two D x H x W host volumes of float16 or bfloat16 samples at `data_range` under the three-dimensional 11-tap window (any
-    strides numpy can express, negative ones included) through rmgr_ssim_hip_compute_ssim3h_host.  Arrays and sample_type: as
+    strides numpy can express, negative ones included) through rmgr_ssim_hip_compute_ssim3h_host; window (a Window, make_window): through
+    rmgr_ssim_hip_compute_ssim3h_win_host under that window on all three axes.  Arrays and sample_type: as
     compute_ssimh (np.float16 arrays select float16; np.uint16 arrays carry bit patterns and need sample_type="bfloat16" or "float16").
     Returns (float32 value, D x H x W float32 map or None)."""
     a, b, code = _h_volume_pair(a, b, sample_type)
@@ -882,12 +900,11 @@ def compute_ssim3h(a, b, data_range, sample_type=None, want_map=False, ctx=None)
     params = (Params3H * 1)()
     params[0] = _params3h_of(a, b, m.ctypes.data if want_map else None)
     out = (ctypes.c_float * 1)()
-    _check("rmgr_ssim_hip_compute_ssim3h_host", load_library().rmgr_ssim_hip_compute_ssim3h_host(
-        ctx.handle if ctx is not None else None, 1, params, code, data_range, out))
+    _ssim3h_host(ctx.handle if ctx is not None else None, 1, params, code, data_range, window, out)
     return np.float32(out[0]), m
 
 
-def compute_ssim3h_batch(pairs, data_range, sample_type=None, ctx=None):
+def compute_ssim3h_batch(pairs, data_range, sample_type=None, ctx=None, window=None):
     """compute_ssim3h() of many host pairs of one size and one sample type in one call (no maps): a float32 array."""
     pairs = [_h_volume_pair(a, b, sample_type) for a, b in pairs]
     n = len(pairs)
@@ -899,8 +916,7 @@ def compute_ssim3h_batch(pairs, data_range, sample_type=None, ctx=None):
     for i, (a, b, _) in enumerate(pairs):
         params[i] = _params3h_of(a, b)
     out = (ctypes.c_float * max(n, 1))()
-    _check("rmgr_ssim_hip_compute_ssim3h_host", load_library().rmgr_ssim_hip_compute_ssim3h_host(
-        ctx.handle if ctx is not None else None, n, params, code, data_range, out))
+    _ssim3h_host(ctx.handle if ctx is not None else None, n, params, code, data_range, window, out)
     return np.array(out[:n], np.float32)
 
 
@@ -1192,31 +1208,51 @@ class Context(object):
             _check("rmgr_ssim_hip_enqueue_ssim3f_win_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_win_map_grad(
                 self.handle, count, params_array, data_range, _window_ref(window), grad_out_maps, grad_a, grad_b))
 
-    def ssim3h_device(self, params_array, count, data_range, sample_type):
+    # The 16-bit volume family takes window=None (the engine's 11-tap Gaussian of sigma 1.5: the entry without _win) or a Window
+    # (make_window): the _win entry under that window on all three axes.
+
+    def ssim3h_device(self, params_array, count, data_range, sample_type, window=None):
         """SSIM of `count` device-resident pairs of float16 / bfloat16 volumes (a Params3H array) under the three-dimensional window
-        through rmgr_ssim_hip_compute_ssim3h_device: a float32 array."""
+        through rmgr_ssim_hip_compute_ssim3h_device (window: _ssim3h_win_device): a float32 array."""
         out = (ctypes.c_float * count)()
-        _check("rmgr_ssim_hip_compute_ssim3h_device", self.lib.rmgr_ssim_hip_compute_ssim3h_device(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, out))
+        if window is None:
+            _check("rmgr_ssim_hip_compute_ssim3h_device", self.lib.rmgr_ssim_hip_compute_ssim3h_device(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, out))
+        else:
+            _check("rmgr_ssim_hip_compute_ssim3h_win_device", self.lib.rmgr_ssim_hip_compute_ssim3h_win_device(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), out))
         return np.array(out[:], np.float32)
 
-    def enqueue_ssim3h(self, params_array, count, data_range, sample_type, sums_dev_ptr):
-        """rmgr_ssim_hip_enqueue_ssim3h: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
-        _check("rmgr_ssim_hip_enqueue_ssim3h", self.lib.rmgr_ssim_hip_enqueue_ssim3h(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, sums_dev_ptr))
+    def enqueue_ssim3h(self, params_array, count, data_range, sample_type, sums_dev_ptr, window=None):
+        """rmgr_ssim_hip_enqueue_ssim3h (window: _ssim3h_win): per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssim3h", self.lib.rmgr_ssim_hip_enqueue_ssim3h(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, sums_dev_ptr))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssim3h_win", self.lib.rmgr_ssim_hip_enqueue_ssim3h_win(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), sums_dev_ptr))
 
-    def enqueue_ssim3h_grad(self, params_array, count, data_range, sample_type, grad_out_dev_ptr, grad_a=None, grad_b=None):
-        """rmgr_ssim_hip_enqueue_ssim3h_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes into the 16-bit
-        volumes the Grad3H arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values; asynchronous, written not
-        accumulated."""
-        _check("rmgr_ssim_hip_enqueue_ssim3h_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_grad(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_dev_ptr, grad_a, grad_b))
+    def enqueue_ssim3h_grad(self, params_array, count, data_range, sample_type, grad_out_dev_ptr, grad_a=None, grad_b=None, window=None):
+        """rmgr_ssim_hip_enqueue_ssim3h_grad (window: _ssim3h_win_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs of
+        volumes into the 16-bit volumes the Grad3H arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values;
+        asynchronous, written not accumulated."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssim3h_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_dev_ptr, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssim3h_win_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_win_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), grad_out_dev_ptr, grad_a, grad_b))
 
-    def enqueue_ssim3h_map_grad(self, params_array, count, data_range, sample_type, grad_out_maps, grad_a=None, grad_b=None):
-        """rmgr_ssim_hip_enqueue_ssim3h_map_grad: the same for a per-voxel upstream gradient: grad_out_maps is a GradOut3F array of `count`
-        float32 volumes dLoss/dssim_i(p) in device memory (any step / stride / sliceStride in floats, 0 allowed)."""
-        _check("rmgr_ssim_hip_enqueue_ssim3h_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_map_grad(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_maps, grad_a, grad_b))
+    def enqueue_ssim3h_map_grad(self, params_array, count, data_range, sample_type, grad_out_maps, grad_a=None, grad_b=None, window=None):
+        """rmgr_ssim_hip_enqueue_ssim3h_map_grad (window: _ssim3h_win_map_grad): the same for a per-voxel upstream gradient: grad_out_maps
+        is a GradOut3F array of `count` float32 volumes dLoss/dssim_i(p) in device memory (any step / stride / sliceStride in floats, 0
+        allowed)."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssim3h_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_map_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_maps, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssim3h_win_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_win_map_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), grad_out_maps, grad_a, grad_b))
 
     def enqueue_ssimh(self, params_array, count, data_range, sample_type, sums_dev_ptr):
         """rmgr_ssim_hip_enqueue_ssimh: per-pair fp64 sums into device memory, asynchronously on the context's stream."""

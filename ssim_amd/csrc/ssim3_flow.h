@@ -1,10 +1,11 @@
 // ssim3_flow.h -- what the host flows of the two volume families share (ssim3f_abi.cpp: float32 volumes; ssim3h_abi.cpp: float16 /
 // bfloat16 volumes), written once over the sample type: the sub-batch rule, the bytes of a staged volume, the launch through the
-// context's ring of descriptor tables and the strided copy-back of a map.  Not installed.
+// context's ring of descriptor tables, the strided copy-back of a map, and the parsed window of a launch.  Not installed.
 #ifndef SSIM_AMD_SSIM3_FLOW_H
 #define SSIM_AMD_SSIM3_FLOW_H
 
 #include "ssim_context.h"
+#include "ssimk_kernels.h"      // kSKMaxRadius, window_taps
 
 #include <vector>
 
@@ -92,6 +93,34 @@ int copy_map_back(const float* src, const Params& p, std::vector<float>& back)
             for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = s[x];
         }
     return 0;
+}
+
+// The window of a launch: its radius and taps, centre first (ssimk_kernels.h: window_taps).  Radius 5 runs on the 11-tap kernels
+// (ssim3f_kernels.hip / ssim3w_kernels.hip; ssim3h_kernels.hip), the smaller ones on ssim3k_kernels.hip / ssim3hk_kernels.hip.
+struct Window3 {
+    uint32_t radius;
+    float    gf[ssim_hip::kSKMaxRadius + 1];
+};
+
+// The engine's window, that of every entry without _win: 11 taps, Gaussian, sigma 1.5.
+inline Window3 default_window()
+{
+    Window3 w;
+    w.radius = 5;
+    ssim_hip::window_taps(5, ssim_hip::kSKGaussian, 1.5f, w.gf);
+    return w;
+}
+
+// The window of a _win entry: NULL is the engine's; else size 3, 5, 7, 9 or 11, a known kind and -- Gaussian -- a finite sigma > 0.
+inline int window_validate(const rmgr_ssim_hip_Window* window, Window3& w)
+{
+    if (window == NULL) { w = default_window(); return 0; }
+    const uint32_t size = window->size;
+    if (size < 3 || size > 11 || (size & 1u) == 0) return EINVAL;
+    if (window->kind != RMGR_SSIM_HIP_WINDOW_GAUSSIAN && window->kind != RMGR_SSIM_HIP_WINDOW_UNIFORM) return EINVAL;
+    w.radius = (size - 1) / 2;
+    return ssim_hip::window_taps(w.radius, window->kind == RMGR_SSIM_HIP_WINDOW_UNIFORM ? ssim_hip::kSKUniform : ssim_hip::kSKGaussian, window->sigma, w.gf)
+               ? 0 : EINVAL;
 }
 
 } // namespace volumes

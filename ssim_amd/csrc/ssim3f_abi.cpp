@@ -20,7 +20,7 @@
 #include <cmath>
 
 using namespace ssim_host;
-using namespace ssim_host::volumes;      // kScratchCap, round64, volume_bytes, take3f, ring_launch, copy_map_back
+using namespace ssim_host::volumes;      // kScratchCap, round64, volume_bytes, take3f, ring_launch, copy_map_back, Window3, window_validate
 
 namespace {
 
@@ -28,22 +28,6 @@ using ssim_hip::Pair3FDesc;
 using ssim_hip::Grad3FDesc;
 using ssim_hip::GradOut3FDesc;
 using ssim_hip::Geometry3F;
-
-// The window of a launch: its radius and taps, centre first (ssimk_kernels.h: window_taps).  Radius 5 runs on the kernels of
-// ssim3f_kernels.hip / ssim3w_kernels.hip, the smaller ones on ssim3k_kernels.hip.
-struct Window3 {
-    uint32_t radius;
-    float    gf[ssim_hip::kSKMaxRadius + 1];
-};
-
-// The engine's window, that of every entry without _win: 11 taps, Gaussian, sigma 1.5.
-Window3 default_window()
-{
-    Window3 w;
-    w.radius = 5;
-    ssim_hip::window_taps(5, ssim_hip::kSKGaussian, 1.5f, w.gf);
-    return w;
-}
 
 // ---- validation, before any device is touched -----------------------------------------------------------------------------------------------
 
@@ -61,18 +45,6 @@ int validate3f(uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataR
     }
     if (ssim_hip::ssim3f_max_count(W, H, D) == 0) return EINVAL;
     return 0;
-}
-
-// The window of a _win entry: NULL is the engine's; else size 3, 5, 7, 9 or 11, a known kind and -- Gaussian -- a finite sigma > 0.
-int window_validate(const rmgr_ssim_hip_Window* window, Window3& w)
-{
-    if (window == NULL) { w = default_window(); return 0; }
-    const uint32_t size = window->size;
-    if (size < 3 || size > 11 || (size & 1u) == 0) return EINVAL;
-    if (window->kind != RMGR_SSIM_HIP_WINDOW_GAUSSIAN && window->kind != RMGR_SSIM_HIP_WINDOW_UNIFORM) return EINVAL;
-    w.radius = (size - 1) / 2;
-    return ssim_hip::window_taps(w.radius, window->kind == RMGR_SSIM_HIP_WINDOW_UNIFORM ? ssim_hip::kSKUniform : ssim_hip::kSKGaussian, window->sigma, w.gf)
-               ? 0 : EINVAL;
 }
 
 int validate_grads3f(uint32_t count, const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB)

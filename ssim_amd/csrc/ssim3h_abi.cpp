@@ -1,6 +1,7 @@
 // ssim3h_abi.cpp -- the entry points of the C ABI for float16 / bfloat16 VOLUMES: SSIM under the three-dimensional window, its gradient
-// and the gradient of its map for a per-voxel upstream gradient (rmgr_ssim_hip_*_ssim3h*).  The definition is in include/rmgr/ssim-hip.h,
-// the kernels in ssim3h_kernels.hip.
+// and the gradient of its map for a per-voxel upstream gradient (rmgr_ssim_hip_*_ssim3h*), each under the engine's window and, _win,
+// under the caller's.  The definition is in include/rmgr/ssim-hip.h, the kernels in ssim3h_kernels.hip (11 taps) and in
+// ssim3hk_kernels.hip (3, 5, 7 and 9 taps).
 //
 // The flow is the one of ssim3f_abi.cpp, written for 2-byte samples: the same validation order (plus the sample type), sub-batches under
 // kScratchCap of device scratch with at least one volume each, the launch limit, staging of host volumes (2 bytes per sample; the
@@ -13,11 +14,12 @@
 #include "ssim_context.h"
 #include "ssim3_flow.h"
 #include "ssim3h_kernels.h"
+#include "ssim3hk_kernels.h"
 
 #include <cmath>
 
 using namespace ssim_host;
-using namespace ssim_host::volumes;      // kScratchCap, round64, volume_bytes, take3f, ring_launch, copy_map_back
+using namespace ssim_host::volumes;      // kScratchCap, round64, volume_bytes, take3f, ring_launch, copy_map_back, Window3, window_validate
 
 namespace {
 
@@ -94,17 +96,24 @@ Grad3HDesc make_grad_desc(const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip
 uint64_t partials_per_volume(uint32_t W, uint32_t H, uint32_t D) { return ssim_hip::plan3f(W, H, D, 1, 0).cells_per_volume() * sizeof(double); }
 
 // Enqueues n pairs (descriptors in host memory, volumes on the device): descriptor upload, walk, reduction into sums[0 .. n-1].
-int enqueue_volumes(rmgr_ssim_hip_Context* c, int type, float range, uint32_t n, const Pair3HDesc* d, uint32_t W, uint32_t H, uint32_t D, double* sums)
+// The cells (and with them the partials) are the same for every radius; a smaller window's chunks pay fewer warm-up slices.
+int enqueue_volumes(rmgr_ssim_hip_Context* c, int type, float range, const Window3& win, uint32_t n, const Pair3HDesc* d, uint32_t W, uint32_t H, uint32_t D,
+                    double* sums)
 {
-    const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+    const Geometry3F geo = ssim_hip::plan3k(win.radius, W, H, D, n, c->cu_count);
     int rc;
     if ((rc = c->sf_partials.grow((size_t)(geo.cells_per_volume() * n)))) return rc;
     return ring_launch(c, n * sizeof(Pair3HDesc),
         [&](uint8_t* pin) { memcpy(pin, d, n * sizeof(Pair3HDesc)); },
-        [&](const uint8_t* dev) { return ssim_hip::launch_ssim3h(geo, reinterpret_cast<const Pair3HDesc*>(dev), type, range, c->sf_partials, sums, c->stream); });
+        [&](const uint8_t* dev) {
+            const Pair3HDesc* descs = reinterpret_cast<const Pair3HDesc*>(dev);
+            if (win.radius == 5)
+                return ssim_hip::launch_ssim3h(geo, descs, type, range, c->sf_partials, sums, c->stream, win.gf);
+            return ssim_hip::launch_ssim3hk(win.radius, win.gf, geo, descs, type, range, c->sf_partials, sums, c->stream);
+        });
 }
 
-int enqueue_all(rmgr_ssim_hip_Context* c, int type, float range, uint32_t count, const rmgr_ssim_hip_Params3H* params, double* sums)
+int enqueue_all(rmgr_ssim_hip_Context* c, int type, float range, const Window3& win, uint32_t count, const rmgr_ssim_hip_Params3H* params, double* sums)
 {
     const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
     try {
@@ -114,7 +123,7 @@ int enqueue_all(rmgr_ssim_hip_Context* c, int type, float range, uint32_t count,
             const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), partials_per_volume(W, H, D), false, staged);
             d.resize(n);
             for (uint32_t i = 0; i < n; ++i) d[i] = make_desc(params[i0 + i], true);
-            const int rc = enqueue_volumes(c, type, range, n, &d[0], W, H, D, sums + i0);
+            const int rc = enqueue_volumes(c, type, range, win, n, &d[0], W, H, D, sums + i0);
             if (rc) return rc;
             i0 += n;
         }
@@ -127,7 +136,8 @@ int enqueue_all(rmgr_ssim_hip_Context* c, int type, float range, uint32_t count,
 // The blocking entry points: every sub-batch into the pinned sums, then the means.  stage: host pointers -- the volumes are copied (each
 // volume's sample range, 2 bytes per sample) into c->stage_a, a pair's float32 map is written densely into it as well and copied back at
 // its own strides.
-int blocking(rmgr_ssim_hip_Context* c, int type, float range, uint32_t count, const rmgr_ssim_hip_Params3H* params, float* ssim, bool stage)
+int blocking(rmgr_ssim_hip_Context* c, int type, float range, const Window3& win, uint32_t count, const rmgr_ssim_hip_Params3H* params, float* ssim,
+             bool stage)
 {
     const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
     const double voxels = (double)W * (double)H * (double)D;
@@ -163,7 +173,7 @@ int blocking(rmgr_ssim_hip_Context* c, int type, float range, uint32_t count, co
                     off += round64((uint64_t)W * H * D * 4);
                 }
             }
-            if ((rc = enqueue_volumes(c, type, range, n, &d[0], W, H, D, c->sf_sums_pin + i0))) return rc;
+            if ((rc = enqueue_volumes(c, type, range, win, n, &d[0], W, H, D, c->sf_sums_pin + i0))) return rc;
             HIP_TRY(hipStreamSynchronize(c->stream));
             for (uint32_t i = 0; i < n && stage; ++i) {
                 const rmgr_ssim_hip_Params3H& p = params[i0 + i];
@@ -184,8 +194,8 @@ int blocking(rmgr_ssim_hip_Context* c, int type, float range, uint32_t count, co
 // then the adjoint walk that reads them and rounds each gradient voxel once.  The next sub-batch -- and the float32 family, which shares
 // the scratch -- rewrites it in stream order.  maps == NULL: the per-volume upstream gradient gradOutDevice; else a third table in the
 // descriptor slot, the GradOut3FDesc of the sub-batch, through which the first walk reads k per voxel.
-int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3H* params, int type, float range, const float* gradOutDevice,
-               const rmgr_ssim_hip_GradOut3F* maps, const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB)
+int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3H* params, int type, float range, const Window3& win,
+               const float* gradOutDevice, const rmgr_ssim_hip_GradOut3F* maps, const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB)
 {
     const uint32_t W = params[0].width, H = params[0].height, D = params[0].depth;
     const int which = (gradA ? 1 : 0) | (gradB ? 2 : 0);
@@ -193,7 +203,7 @@ int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Par
     for (uint32_t i0 = 0; i0 < count;) {
         uint64_t staged;
         const uint32_t n = take3f(params, i0, count, ssim_hip::ssim3f_max_count(W, H, D), per_volume * sizeof(float), false, staged);
-        const Geometry3F geo = ssim_hip::plan3f(W, H, D, n, c->cu_count);
+        const Geometry3F geo = ssim_hip::plan3k(win.radius, W, H, D, n, c->cu_count);
         int rc;
         if ((rc = c->s3_coef.grow((size_t)(per_volume * n)))) return rc;
         const size_t pair_bytes = n * sizeof(Pair3HDesc), grad_bytes = n * sizeof(Grad3HDesc);
@@ -214,10 +224,13 @@ int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Par
             [&](const uint8_t* dev) {
                 const Pair3HDesc* pd = reinterpret_cast<const Pair3HDesc*>(dev);
                 const Grad3HDesc* gd = reinterpret_cast<const Grad3HDesc*>(dev + pair_bytes);
+                const GradOut3FDesc* od = maps ? reinterpret_cast<const GradOut3FDesc*>(dev + pair_bytes + grad_bytes) : NULL;
+                const float* g_out = maps ? NULL : gradOutDevice + i0;
+                if (win.radius != 5)
+                    return ssim_hip::launch_ssim3hk_grad(win.radius, win.gf, geo, pd, gd, type, g_out, od, range, which, c->s3_coef, c->stream);
                 if (maps)
-                    return ssim_hip::launch_ssim3h_map_grad(geo, pd, gd, reinterpret_cast<const GradOut3FDesc*>(dev + pair_bytes + grad_bytes), type, range,
-                                                            which, c->s3_coef, c->stream);
-                return ssim_hip::launch_ssim3h_grad(geo, pd, gd, type, gradOutDevice + i0, range, which, c->s3_coef, c->stream);
+                    return ssim_hip::launch_ssim3h_map_grad(geo, pd, gd, od, type, range, which, c->s3_coef, c->stream, win.gf);
+                return ssim_hip::launch_ssim3h_grad(geo, pd, gd, type, g_out, range, which, c->s3_coef, c->stream, win.gf);
             });
         if (rc) return rc;
         i0 += n;
@@ -225,64 +238,141 @@ int grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Par
     return 0;
 }
 
+// ---- what an entry does once its pairs are valid; `window` is NULL (the engine's window) or the caller's ---------------------------------
+
+int enqueue_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3H* params, uint32_t sampleType, float dataRange,
+                  const rmgr_ssim_hip_Window* window, double* sumsDevice)
+{
+    Window3 win;
+    const int rc = window_validate(window, win);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, type_of(sampleType), dataRange, win, count, params, sumsDevice);
+}
+
+int device_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3H* params, uint32_t sampleType, float dataRange,
+                 const rmgr_ssim_hip_Window* window, float* ssim)
+{
+    Window3 win;
+    const int rc = window_validate(window, win);
+    if (rc) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, type_of(sampleType), dataRange, win, count, params, ssim, false);
+}
+
+int host_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3H* params, uint32_t sampleType, float dataRange,
+               const rmgr_ssim_hip_Window* window, float* ssim)
+{
+    Window3 win;
+    int rc = window_validate(window, win);
+    if (rc) return rc;
+    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
+    if ((rc = lease.take(c))) return rc;
+    USE_DEVICE(lease.c);
+    return blocking(lease.c, type_of(sampleType), dataRange, win, count, params, ssim, true);
+}
+
+// gradOutDevice == NULL: the per-voxel upstream form, `maps`.
+int grad_entry_checked(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params3H* params, uint32_t sampleType, float dataRange,
+                       const rmgr_ssim_hip_Window* window, const float* gradOutDevice, const rmgr_ssim_hip_GradOut3F* maps,
+                       const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB)
+{
+    Window3 win;
+    int rc = validate_grads3h(count, gradA, gradB);
+    if (rc) return rc;
+    if (gradOutDevice == NULL && (rc = validate_grad_maps3h(count, maps))) return rc;
+    if ((rc = window_validate(window, win))) return rc;
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return grad_entry(c, count, params, type_of(sampleType), dataRange, win, gradOutDevice, gradOutDevice ? NULL : maps, gradA, gradB);
+}
+
 } // namespace
 
 extern "C" {
+
+// Every entry exists twice: under the engine's window and, _win, under the caller's (include/rmgr/ssim-hip.h: rmgr_ssim_hip_Window).
+// Both run the same flow; the window is one more input.
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
                                           rmgr_uint32_t sampleType, float dataRange, double* sumsDevice) RMGR_NOEXCEPT
 {
     const int rc = validate3h(count, params, sampleType, dataRange, sumsDevice);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return enqueue_all(c, type_of(sampleType), dataRange, count, params, sumsDevice);
+    return rc ? rc : enqueue_entry(c, count, params, sampleType, dataRange, NULL, sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                              rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                              double* sumsDevice) RMGR_NOEXCEPT
+{
+    const int rc = validate3h(count, params, sampleType, dataRange, sumsDevice);
+    return rc ? rc : enqueue_entry(c, count, params, sampleType, dataRange, window, sumsDevice);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
                                                  rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
 {
     const int rc = validate3h(count, params, sampleType, dataRange, ssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return blocking(c, type_of(sampleType), dataRange, count, params, ssim, false);
+    return rc ? rc : device_entry(c, count, params, sampleType, dataRange, NULL, ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                     rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                     float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = validate3h(count, params, sampleType, dataRange, ssim);
+    return rc ? rc : device_entry(c, count, params, sampleType, dataRange, window, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
                                                rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
 {
-    int rc = validate3h(count, params, sampleType, dataRange, ssim);
-    if (rc) return rc;
-    Lease lease;                         // ctx == NULL: one of the default contexts, for this call only
-    if ((rc = lease.take(c))) return rc;
-    USE_DEVICE(lease.c);
-    return blocking(lease.c, type_of(sampleType), dataRange, count, params, ssim, true);
+    const int rc = validate3h(count, params, sampleType, dataRange, ssim);
+    return rc ? rc : host_entry(c, count, params, sampleType, dataRange, NULL, ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssim3h_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                   rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                   float* ssim) RMGR_NOEXCEPT
+{
+    const int rc = validate3h(count, params, sampleType, dataRange, ssim);
+    return rc ? rc : host_entry(c, count, params, sampleType, dataRange, window, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
                                                rmgr_uint32_t sampleType, float dataRange, const float* gradOutDevice,
                                                const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT
 {
-    int rc = validate3h(count, params, sampleType, dataRange, gradOutDevice);
-    if (rc) return rc;
-    if ((rc = validate_grads3h(count, gradA, gradB))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return grad_entry(c, count, params, type_of(sampleType), dataRange, gradOutDevice, NULL, gradA, gradB);
+    const int rc = validate3h(count, params, sampleType, dataRange, gradOutDevice);
+    return rc ? rc : grad_entry_checked(c, count, params, sampleType, dataRange, NULL, gradOutDevice, NULL, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                   rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                   const float* gradOutDevice, const rmgr_ssim_hip_Grad3H* gradA,
+                                                   const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT
+{
+    const int rc = validate3h(count, params, sampleType, dataRange, gradOutDevice);
+    return rc ? rc : grad_entry_checked(c, count, params, sampleType, dataRange, window, gradOutDevice, NULL, gradA, gradB);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
                                                    rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_GradOut3F* gradOutMaps,
                                                    const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT
 {
-    int rc = validate3h(count, params, sampleType, dataRange, gradOutMaps);
-    if (rc) return rc;
-    if ((rc = validate_grads3h(count, gradA, gradB))) return rc;
-    if ((rc = validate_grad_maps3h(count, gradOutMaps))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return grad_entry(c, count, params, type_of(sampleType), dataRange, NULL, gradOutMaps, gradA, gradB);
+    const int rc = validate3h(count, params, sampleType, dataRange, gradOutMaps);
+    return rc ? rc : grad_entry_checked(c, count, params, sampleType, dataRange, NULL, NULL, gradOutMaps, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                       rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                       const rmgr_ssim_hip_GradOut3F* gradOutMaps, const rmgr_ssim_hip_Grad3H* gradA,
+                                                       const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT
+{
+    const int rc = validate3h(count, params, sampleType, dataRange, gradOutMaps);
+    return rc ? rc : grad_entry_checked(c, count, params, sampleType, dataRange, window, NULL, gradOutMaps, gradA, gradB);
 }
 
 } // extern "C"

@@ -29,19 +29,20 @@ struct Grad3HDesc {
 
 // Enqueues the forward walk and the per-volume reduction of geo.count pairs on `stream` (launch_ssim3f for 16-bit samples).
 //   type   kSHTypeF16 or kSHTypeBF16
+//   taps   NULL: the engine's 11-tap Gaussian of sigma 1.5; else the six taps of an 11-tap window, centre first (here and below)
 hipError_t launch_ssim3h(const Geometry3F& geo, const Pair3HDesc* descs_dev, int type, float data_range, double* partials, double* sums,
-                         hipStream_t stream);
+                         hipStream_t stream, const float* taps = NULL);
 
 // Enqueues the backward of geo.count pairs on `stream` (launch_ssim3f_grad for 16-bit samples): the walk that writes the float32
 // coefficient volumes into `coef`, then the adjoint walk, which rounds each gradient voxel once, to nearest-even, into the samples'
 // encoding.  g_out, which, coef: as for launch_ssim3f_grad.
 hipError_t launch_ssim3h_grad(const Geometry3F& geo, const Pair3HDesc* descs_dev, const Grad3HDesc* grads_dev, int type, const float* g_out,
-                              float data_range, int which, float* coef, hipStream_t stream);
+                              float data_range, int which, float* coef, hipStream_t stream, const float* taps = NULL);
 
 // The same for a per-voxel upstream gradient (launch_ssim3w_grad for 16-bit samples): k(p) = gMap(p), float32, read per voxel through
 // gouts_dev.  A constant volume of float(gOut / (W H D)) gives the bits of launch_ssim3h_grad.
 hipError_t launch_ssim3h_map_grad(const Geometry3F& geo, const Pair3HDesc* descs_dev, const Grad3HDesc* grads_dev, const GradOut3FDesc* gouts_dev,
-                                  int type, float data_range, int which, float* coef, hipStream_t stream);
+                                  int type, float data_range, int which, float* coef, hipStream_t stream, const float* taps = NULL);
 
 } // namespace ssim_hip
 

@@ -44,8 +44,9 @@ ignores win_sigma): pytorch-msssim's win_size / win_sigma, torchmetrics' and piq
 filter_sigma, kornia's window_size, skimage's 7 x 7 box, the 3 x 3 box of monodepth-style losses.  The defaults (11, 1.5, "gaussian") take
 exactly the path above; anything else runs the _win entries of the float32 family (rmgr_ssim_hip_enqueue_ssimf_win, _ssimf_win_grad,
 _ssimf_win_map_grad), the small windows on kernels of their own radius.  Edges are clamped for every window: where monodepth-style code
-reflects, the interior is identical and the outermost (win_size - 1) / 2 pixels differ.  float16 / bfloat16 tensors and ms_ssim keep the
-fixed window for now: a non-default window with 16-bit tensors is a TypeError.
+reflects, the interior is identical and the outermost (win_size - 1) / 2 pixels differ.  The 2-D functions with float16 / bfloat16
+tensors, and ms_ssim, keep the fixed window for now: a non-default window with 16-bit tensors is a TypeError there (volumes take one:
+ssim3d_amp, ssim3d_map_amp and SSIM3DLoss, below).
 
     photo = 0.85 * (1 - ssim_map(warped, target, win_size=3, window="uniform")) / 2 + 0.15 * (warped - target).abs()
 
@@ -65,13 +66,16 @@ float16 and bfloat16 volumes.  ssim3d_amp(x, y, data_range), ssim3d_map_amp(x, y
 float16 or two bfloat16 tensors as they come under torch.autocast (rmgr_ssim_hip_enqueue_ssim3h, _ssim3h_grad, _ssim3h_map_grad): the
 samples are read as they are (2 B/voxel), the value and the map are float32 with the bits of ssim3d(x.float(), y.float()) /
 ssim3d_map(x.float(), y.float()), and the gradient comes back in the inputs' dtype, that call's float32 gradient rounded once by the
-kernel; grad_out stays float32, so a GradScaler's scale arrives before the rounding.  The wart of ms_ssim / ms_ssim_amp again: ssim3d and
+kernel; grad_out stays float32, so a GradScaler's scale arrives before the rounding.  They take the window keywords with 16-bit tensors
+as well (rmgr_ssim_hip_enqueue_ssim3h_win, _ssim3h_win_grad, _ssim3h_win_map_grad): the bits of ssim3d(x.float(), y.float(), win_size=...)
+and that call's gradient rounded once, without the float32 copies.  The wart of ms_ssim / ms_ssim_amp again: ssim3d and
 ssim3d_map themselves stay float32-only (16-bit tensors are a TypeError there, pinned by tests from the time there was no 16-bit volume
 path; the _amp functions are the same functions without that refusal), and two 16-bit CPU tensors are a TypeError in the _amp functions
 and SSIM3DLoss.
 
     with torch.autocast("cuda", dtype=torch.bfloat16):
         loss = SSIM3DLoss()(net(x), y.bfloat16())                   # read as bfloat16; the gradient is bfloat16
+        loss = SSIM3DLoss(win_size=7, window="uniform")(net(x), y.bfloat16())      # MONAI's / skimage's 7-tap box, still 2 B/voxel
 
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
@@ -138,15 +142,16 @@ def _check(x, y, data_range, half=False):
     return r
 
 
-def _window(x, y, win_size, win_sigma, window, name="ssim"):
+def _window(x, y, win_size, win_sigma, window, name="ssim", fixed16=True):
     """The documented errors of the window arguments (`name`: the function the message names), before any GPU call.  Returns None for
-    the defaults (today's path) or an api.Window."""
+    the defaults (today's path) or an api.Window.  fixed16 (the 2-D names): float16 / bfloat16 tensors keep the fixed window; the 3-D
+    names pass False, their 16-bit path takes a window (ssim3d and ssim3d_map go on to refuse the tensors themselves)."""
     if not isinstance(window, str):
         raise TypeError("%s: window must be 'gaussian' or 'uniform', got %s" % (name, type(window).__name__))
     win = api.make_window(win_size, 1.5 if window == "uniform" else win_sigma, window)      # TypeError / ValueError
     if win.size == 11 and win.kind == api.WINDOW_GAUSSIAN and win.sigma == 1.5:
         return None
-    for t in (x, y):
+    for t in (x, y) if fixed16 else ():
         if str(getattr(t, "dtype", "")) in ("torch.float16", "torch.bfloat16"):
             raise TypeError("%s: float16 / bfloat16 tensors keep the fixed window (win_size=11, win_sigma=1.5, window='gaussian'); "
                             "a configurable window needs float32 tensors" % name)
@@ -510,8 +515,8 @@ class MSSSIMLoss(object):
 # The window: win_size, win_sigma and window are ssim()'s keywords, checked by the same helper, and mean the same window on all three axes
 # (the rmgr_ssim_hip_*_ssim3f_win* entries; what MONAI, torchmetrics and pytorch-msssim call win_size / kernel_size / sigma with
 # spatial_dims=3, and skimage's 7-tap box).  The defaults are the engine's window and take exactly the path without these arguments; any
-# other window is stored on the autograd context and the backward runs under it.  float16 / bfloat16 volumes keep the fixed window: with
-# them a non-default window is a TypeError.  A multi-scale form is a follow-up.
+# other window is stored on the autograd context and the backward runs under it -- for float16 / bfloat16 volumes too, on the
+# rmgr_ssim_hip_*_ssim3h_win* entries.  A multi-scale form is a follow-up.
 
 _function3d = None
 
@@ -596,7 +601,7 @@ def _make_function3d():
                 if st is None:
                     _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr(), **_win_kw(win))
                 else:
-                    _context(x.device, work).enqueue_ssim3h(params, n, data_range, st, sums.data_ptr())
+                    _context(x.device, work).enqueue_ssim3h(params, n, data_range, st, sums.data_ptr(), **_win_kw(win))
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
@@ -625,7 +630,7 @@ def _make_function3d():
                 if st is None:
                     _context(x.device, work).enqueue_ssim3f_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb, **_win_kw(ctx.win))
                 else:
-                    _context(x.device, work).enqueue_ssim3h_grad(params, n, ctx.data_range, st, g.data_ptr(), ga, gb)
+                    _context(x.device, work).enqueue_ssim3h_grad(params, n, ctx.data_range, st, g.data_ptr(), ga, gb, **_win_kw(ctx.win))
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None, None
@@ -644,7 +649,7 @@ def ssim3d(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
     win_sigma ignored; edges are clamped, where skimage reflects); the defaults are the engine's window and take exactly the path without
     these arguments.  TypeError: a win_size that is not an int, a window that is not a str.  ValueError: any other win_size, an unknown
     window name, a win_sigma that is not finite and > 0."""
-    win = _window(x, y, win_size, win_sigma, window, "ssim3d")
+    win = _window(x, y, win_size, win_sigma, window, "ssim3d", fixed16=False)
     return _ssim3d(x, y, _check3d(x, y, data_range), win)
 
 
@@ -658,7 +663,7 @@ def _ssim3d(x, y, r, win=None):
 class SSIM3DLoss(object):
     """1 - ssim3d_amp(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per volume).  A plain callable: it has no
     parameters.  float32, float16 or bfloat16 tensors, as ssim3d_amp(); the loss is float32 at every input dtype.  win_size, win_sigma,
-    window: the window, as ssim3d(), checked here."""
+    window: the window, as ssim3d_amp() (every input dtype), checked here."""
 
     def __init__(self, data_range=1.0, reduction="mean", win_size=11, win_sigma=1.5, window="gaussian"):
         if reduction not in ("mean", "none"):
@@ -711,7 +716,7 @@ def _make_map_function3d():
                 if st is None:
                     _context(x.device, work).enqueue_ssim3f(params, n, data_range, sums.data_ptr(), **_win_kw(win))
                 else:
-                    _context(x.device, work).enqueue_ssim3h(params, n, data_range, st, sums.data_ptr())
+                    _context(x.device, work).enqueue_ssim3h(params, n, data_range, st, sums.data_ptr(), **_win_kw(win))
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
@@ -741,7 +746,7 @@ def _make_map_function3d():
                 if st is None:
                     _context(x.device, work).enqueue_ssim3f_map_grad(params, n, ctx.data_range, maps, ga, gb, **_win_kw(ctx.win))
                 else:
-                    _context(x.device, work).enqueue_ssim3h_map_grad(params, n, ctx.data_range, st, maps, ga, gb)
+                    _context(x.device, work).enqueue_ssim3h_map_grad(params, n, ctx.data_range, st, maps, ga, gb, **_win_kw(ctx.win))
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None, None
@@ -759,7 +764,7 @@ def ssim3d_map(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussia
 
         m = ssim3d_map(x, y)                                  # (N, C, D, H, W)
         loss = 1 - (mask * m).sum() / mask.sum()              # SSIM inside a brain mask"""
-    win = _window(x, y, win_size, win_sigma, window, "ssim3d_map")
+    win = _window(x, y, win_size, win_sigma, window, "ssim3d_map", fixed16=False)
     return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map"), win)
 
 
@@ -781,9 +786,10 @@ def ssim3d_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussia
     ssim3d(x.float(), y.float()), the gradient has the inputs' dtype and is that call's float32 gradient rounded once, by the kernel
     (see the top of this file for autocast and loss scaling).  Errors: as ssim3d(), under this function's name, except that a mixed pair
     is a TypeError and two float16 or two bfloat16 CPU tensors are a TypeError too: 16-bit tensors are taken on a GPU only (one of the
-    two on a GPU: the ValueError).  win_size, win_sigma, window: as ssim3d(), for float32 tensors; float16 and bfloat16 tensors keep the
-    fixed window, and any other window with them is a TypeError."""
-    win = _window(x, y, win_size, win_sigma, window, "ssim3d_amp")
+    two on a GPU: the ValueError).  win_size, win_sigma, window: as ssim3d(), at every input dtype: with float16 and bfloat16 tensors
+    the value has the bits of ssim3d(x.float(), y.float(), win_size=...) under the same window and the gradient is that call's, rounded
+    once (the rmgr_ssim_hip_*_ssim3h_win* entries; the window is stored on the autograd context and the backward runs under it)."""
+    win = _window(x, y, win_size, win_sigma, window, "ssim3d_amp", fixed16=False)
     return _ssim3d(x, y, _check3d(x, y, data_range, "ssim3d_amp", half=True), win)
 
 
@@ -796,5 +802,5 @@ def ssim3d_map_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gau
 
         m = ssim3d_map_amp(x, y)                              # x, y: (N, C, D, H, W) bfloat16; m: float32
         loss = 1 - (mask * m).sum() / mask.sum()"""
-    win = _window(x, y, win_size, win_sigma, window, "ssim3d_map_amp")
+    win = _window(x, y, win_size, win_sigma, window, "ssim3d_map_amp", fixed16=False)
     return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map_amp", half=True), win)
