@@ -107,36 +107,16 @@ $(OBJ)/ssimk_kernels.o: $(SRC)/ssimk_kernels.hip $(SRC)/ssimk_kernels.h $(SRC)/s
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# SSIM of float32 volumes under the three-dimensional window and its gradient (rmgr_ssim_hip_*_ssim3f*): its own file for the same reason,
-# and the same flags (-ffp-contract=off: tests/ssim3f_model.py restates its arithmetic operation by operation).
-$(OBJ)/ssim3f_kernels.o: $(SRC)/ssim3f_kernels.hip $(SRC)/ssim3f_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# Gradient of the 3-D SSIM map for a per-voxel upstream gradient (rmgr_ssim_hip_enqueue_ssim3f_map_grad): its own file -- the tests of
-# ssim3f_kernels.hip count that file's kernels -- and the same flags: its results are held to that object's, bit for bit.
-$(OBJ)/ssim3w_kernels.o: $(SRC)/ssim3w_kernels.hip $(SRC)/ssim3w_kernels.h $(SRC)/ssim3f_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# SSIM of float16 / bfloat16 volumes, its gradient and the gradient of its map (rmgr_ssim_hip_*_ssim3h*): its own file -- the tests of
-# ssim3f_kernels.hip and ssim3w_kernels.hip count those files' kernels -- and the same flags: its results are held to those objects', bit
-# for bit.
-$(OBJ)/ssim3h_kernels.o: $(SRC)/ssim3h_kernels.hip $(SRC)/ssim3h_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssimh_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# SSIM of float32 volumes under a window of 3, 5, 7 or 9 taps, its gradient for both upstream forms (rmgr_ssim_hip_*_ssim3f_win*): its own
-# file -- the tests of ssim3f_kernels.hip and ssim3w_kernels.hip count those files' kernels -- and the same flags as ssim3f_kernels.o, whose
-# flow it copies.
-$(OBJ)/ssim3k_kernels.o: $(SRC)/ssim3k_kernels.hip $(SRC)/ssim3k_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# SSIM of float16 / bfloat16 volumes under a window of 3, 5, 7 or 9 taps, its gradient for both upstream forms
-# (rmgr_ssim_hip_*_ssim3h_win*): its own file -- the tests of ssim3k_kernels.hip and ssim3h_kernels.hip count those files' kernels -- and
-# the same flags as ssim3k_kernels.o and ssim3h_kernels.o: its results are held to the former's, bit for bit.
-$(OBJ)/ssim3hk_kernels.o: $(SRC)/ssim3hk_kernels.hip $(SRC)/ssim3hk_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
+# The volume (3-D) family: five kernel files, one per group of entry points, whose tests count and budget their kernels.  The slice
+# walk and its adjoint are written once, in ssim3_walk.h, which every one of the five includes; the same flags as the 2-D float files
+# (-ffp-contract=off: tests/ssim3f_model.py and tests/ssim3k_model.py restate the arithmetic operation by operation).
+#   ssim3f   float32 volumes under the 11-tap window and its gradient (rmgr_ssim_hip_*_ssim3f*); the reduction and the planner
+#   ssim3w   gradient of the map for a per-voxel upstream gradient (rmgr_ssim_hip_enqueue_ssim3f_map_grad)
+#   ssim3h   float16 / bfloat16 volumes, both upstream forms (rmgr_ssim_hip_*_ssim3h*)
+#   ssim3k   float32 volumes under a window of 3, 5, 7 or 9 taps (rmgr_ssim_hip_*_ssim3f_win*)
+#   ssim3hk  float16 / bfloat16 volumes under a window of 3, 5, 7 or 9 taps (rmgr_ssim_hip_*_ssim3h_win*)
+SSIM3_HDRS := $(SRC)/ssim3_walk.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
+$(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o: $(OBJ)/%.o: $(SRC)/%.hip $(SSIM3_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
