@@ -44,6 +44,8 @@
  *   rmgr_ssim_hip_enqueue_ssim3h_win, rmgr_ssim_hip_compute_ssim3h_win_device / _host, rmgr_ssim_hip_enqueue_ssim3h_win_grad,
  *   rmgr_ssim_hip_enqueue_ssim3h_win_map_grad  the float16 / bfloat16 VOLUME entries under a caller-chosen window: no reference
  *                                      counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_msssim3f, rmgr_ssim_hip_compute_msssim3f_device / _host, rmgr_ssim_hip_enqueue_msssim3f_grad   multi-scale
+ *                                      SSIM of float32 VOLUMES and its gradient: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -835,7 +837,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* ctx
  *
  * Follow-ups, not in this interface: a caller-chosen window (the _win entries), float16 / bfloat16 volumes and multi-scale SSIM of
  * volumes.  (The 16-bit volumes have since arrived under the ssim3h names, below, the caller-chosen window for float32 volumes
- * under the ssim3f_win names and the one for 16-bit volumes under the ssim3h_win names, both further below.)
+ * under the ssim3f_win names and the one for 16-bit volumes under the ssim3h_win names, both further below, and multi-scale SSIM of
+ * float32 volumes under the msssim3f names, last of the volume entries.)
  */
 typedef struct rmgr_ssim_hip_Img3F {
     const float* topLeft;
@@ -1063,6 +1066,71 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win_map_grad(rmgr_ssim_hip_Context* ct
                                                        rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
                                                        const rmgr_ssim_hip_GradOut3F* gradOutMaps, const rmgr_ssim_hip_Grad3H* gradA,
                                                        const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
+
+/*
+ * Multi-scale SSIM (MS-SSIM) of `count` pairs of float32 VOLUMES of one size, and its gradient.  No reference counterpart.  It is the
+ * definition of rmgr_ssim_hip_enqueue_msssimf carried to three axes, with the per-voxel terms of rmgr_ssim_hip_enqueue_ssim3f; float32
+ * and the engine's 11-tap window only.
+ *
+ *   Samples, addressing, data range, C1 / C2, size limit, alignment  as rmgr_ssim_hip_enqueue_ssim3f: Params3F, signed strides of any
+ *            kind, 64-bit offsets.  params[i].ssimMap must be NULL.
+ *   Scales and weights  as rmgr_ssim_hip_enqueue_msssimf: 1 <= scales <= RMGR_SSIM_HIP_MSSSIM_MAX_SCALES; weights NULL: Wang's five
+ *            {0.0448, 0.2856, 0.3001, 0.2363, 0.1333}, and then scales must be 5; otherwise `scales` finite weights >= 0 in HOST memory.
+ *   Pyramid  scale 0 is the input.  Scale s+1 is ceil(W_s/2) x ceil(H_s/2) x ceil(D_s/2), coordinates clamped to scale s:
+ *              P'(x,y,z) = (((P(2x,2y,2z) + P(2x+1,2y,2z)) + (P(2x,2y+1,2z) + P(2x+1,2y+1,2z))) +
+ *                           ((P(2x,2y,2z+1) + P(2x+1,2y,2z+1)) + (P(2x,2y+1,2z+1) + P(2x+1,2y+1,2z+1)))) * 0.125f,
+ *            every operation rounded to fp32 in that order.  All three axes are halved (avg_pool3d of pytorch-msssim does the same); an
+ *            axis that has reached 1 stays 1, so the pyramid runs down to 1 x 1 x 1.
+ *   Per scale  with ssim3f's A1, A2, B1, B2 under the 11-tap Gaussian clamped on all three axes: cs = A2 / B2, ssim = A1 A2 / (B1 B2);
+ *            mcs_s and mssim_s are the fp64 sums of the fp32 values over double(W_s) * double(H_s) * double(D_s).  Both are reported for
+ *            every scale, whatever its weight.
+ *   Value    MS = prod_{s < M-1} max(mcs_s, 0)^w_s * max(mssim_{M-1}, 0)^w_{M-1}, in double on the device, x^0 = 1.  A NaN mean gives NaN.
+ *   Gradient  for gOut[i] = dLoss/dMS_i.  All +0 when MS = 0, and when gOut[i] = 0 whatever the samples are.  Otherwise, with m_s = mcs_s (mssim_s on the last scale),
+ *              k_s = float((((double(gOut) * w_s) * MS) / m_s) / (double(W_s) * double(H_s) * double(D_s))),
+ *            in that order, rounded once, and 0 where w_s = 0.  The local gradient of scale s is Gt(k d_mu) + 2 a Gt(k d_aa) + b Gt(k d_ab)
+ *            with ssim3f's partial derivatives on the last scale and the cs form on the others: d_ab = 2 / B2, d_aa = -cs / B2,
+ *            d_mu = -2 mu_a d_aa - mu_b d_ab.  The total is
+ *              g_s(x,y,z) = fp32(local_s + fp32(0.125 c g_{s+1}(x >> 1, y >> 1, z >> 1))),   c = cx cy cz,
+ *            cx = 2 on the last column of an odd W_s (1 included), else 1; cy and cz likewise; 0.125 c is a power of two, so the product is
+ *            exact.  A scale whose k_s is 0 for a volume contributes +0 whatever its samples are, NaN included: decided on the device, no
+ *            host wait.  A gather: one writer per voxel, no floating-point atomics.  Gradients are written, not accumulated; either of
+ *            gradA / gradB may be NULL, not both.  The backward recomputes the pyramid, not the means: scaleMeansDevice is the forward's.
+ *   Arithmetic  fp32 with one centre per volume AT EVERY SCALE: the scale's own sample at ((W_s-1)/2, (H_s-1)/2, (D_s-1)/2) when its
+ *            magnitude is at most dataRange, else 0.  Cells are 16 x 16 x 8 at absolute positions of each scale, summed in a fixed tree.
+ *   Determinism  ssim3f's, for value, per-scale means and gradients: the same bits alone or anywhere in a batch, at any z-chunk depth of
+ *            any scale, after any sub-batch split, through every entry, with one gradient or both, for any view against the dense volume.
+ *   Identities  mssim_s has the BITS of rmgr_ssim_hip_enqueue_ssim3f's per-volume sum on the scale-s volume, divided by its voxel count in
+ *            double.  With scales = 1 and weights = {1} the gradient has the BITS of rmgr_ssim_hip_enqueue_ssim3f_map_grad under a
+ *            zero-stride gMap holding k_0.
+ *   Scratch  belongs to the context and is reused in stream order.  The pyramid volumes of scales >= 1 take about 8/7 bytes per scale-0
+ *            voxel of a pair; in the backward the coarse gradient volumes take 4/7 (one gradient) or 8/7 (both) bytes more; ssim3f's
+ *            coefficient volumes take 12 / 16 bytes per voxel of the LARGEST scale and are reused by every scale.  A batch runs in
+ *            sub-batches of about 1 GB of it, at least one volume each.
+ *   scaleMeans  [pair][scale]{mcs, mssim}: count x scales x 2 doubles; may be NULL for compute_*, not for enqueue.
+ *
+ * EINVAL, before any device is touched: every EINVAL of the ssim3f entries and of msssimf's scales / weights checks; a non-NULL ssimMap;
+ * a NULL msssim, valuesDevice, scaleMeansDevice or gradOutDevice; a volume whose first pyramid step alone needs 2^32 work-items.
+ * ENODEV: no device.
+ *
+ * Against pytorch-msssim's MS_SSIM(spatial_dims=3): that one uses a valid window and zero-padded pooling and refuses small sides; this
+ * one clamps the window at the borders, pools with clamped coordinates and runs down to 1 x 1 x 1, so values are close, not equal.
+ *
+ * Follow-ups, not in this interface: float16 / bfloat16 volumes, a caller-chosen window for the multi-scale form, and a multi-scale map
+ * gradient.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                            float dataRange, rmgr_uint32_t scales, const double* weights, double* valuesDevice,
+                                            double* scaleMeansDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                   float dataRange, rmgr_uint32_t scales, const double* weights, float* msssim,
+                                                   double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                 float dataRange, rmgr_uint32_t scales, const double* weights, float* msssim,
+                                                 double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                 float dataRange, rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice,
+                                                 const float* gradOutDevice, const rmgr_ssim_hip_Grad3F* gradA,
+                                                 const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

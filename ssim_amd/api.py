@@ -232,6 +232,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssim3f_win_grad", "rmgr_ssim_hip_enqueue_ssim3f_win_map_grad",
     "rmgr_ssim_hip_enqueue_ssim3h_win", "rmgr_ssim_hip_compute_ssim3h_win_device", "rmgr_ssim_hip_compute_ssim3h_win_host",
     "rmgr_ssim_hip_enqueue_ssim3h_win_grad", "rmgr_ssim_hip_enqueue_ssim3h_win_map_grad",
+    "rmgr_ssim_hip_enqueue_msssim3f", "rmgr_ssim_hip_compute_msssim3f_device", "rmgr_ssim_hip_compute_msssim3f_host", "rmgr_ssim_hip_enqueue_msssim3f_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -344,6 +345,10 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssimf_win_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssimf_win_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
         "rmgr_ssim_hip_enqueue_ssimf_win_map_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, ctypes.POINTER(GradOutF), ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
+        "rmgr_ssim_hip_enqueue_msssim3f": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
+        "rmgr_ssim_hip_compute_msssim3f_device": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssim3f_host": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_msssim3f_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
         "rmgr_ssim_hip_enqueue_msssimf": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
         "rmgr_ssim_hip_compute_msssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
@@ -959,6 +964,29 @@ def compute_msssimf_batch(pairs, data_range, scales=5, weights=None, per_scale=F
     return _msssimf_call("rmgr_ssim_hip_compute_msssimf_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale)
 
 
+def compute_msssim3f(a, b, data_range, scales=5, weights=None, per_scale=False, ctx=None):
+    """Multi-scale SSIM of two D x H x W float32 host volumes at `data_range` (any strides numpy can express, negative ones included)
+    through rmgr_ssim_hip_compute_msssim3f_host: the 11-tap window on all three axes, all three axes halved from scale to scale.  weights
+    None: Wang's five (scales must be 5).  Returns a float32, and with per_scale=True also a (scales, 2) float64 array of
+    [scale]{mcs, mssim}."""
+    a, b = _f32_volume(a), _f32_volume(b)
+    assert a.shape == b.shape
+    params = (Params3F * 1)()
+    params[0] = _params3f_of(a, b)
+    r = _msssimf_call("rmgr_ssim_hip_compute_msssim3f_host", ctx.handle if ctx is not None else None, params, 1, data_range, scales, weights, per_scale)
+    return (r[0][0], r[1][0]) if per_scale else r[0]
+
+
+def compute_msssim3f_batch(pairs, data_range, scales=5, weights=None, per_scale=False, ctx=None):
+    """compute_msssim3f() of many host pairs of one size in one call: a float32 array (and a (count, scales, 2) array with per_scale)."""
+    pairs = [(_f32_volume(a), _f32_volume(b)) for a, b in pairs]
+    n = len(pairs)
+    params = (Params3F * max(n, 1))()
+    for i, (a, b) in enumerate(pairs):
+        params[i] = _params3f_of(a, b)
+    return _msssimf_call("rmgr_ssim_hip_compute_msssim3f_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale)
+
+
 def _msssimh_call(fn_name, handle, params, count, code, data_range, scales, weights, per_scale):
     out = (ctypes.c_float * max(count, 1))()
     means = (ctypes.c_double * max(count * scales * 2, 1))() if per_scale else None
@@ -1297,6 +1325,23 @@ class Context(object):
         """rmgr_ssim_hip_enqueue_msssimf_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs, from the forward's means
         (device memory), into the planes the GradF arrays describe; asynchronous on the context's stream, no host synchronisation."""
         _check("rmgr_ssim_hip_enqueue_msssimf_grad", self.lib.rmgr_ssim_hip_enqueue_msssimf_grad(
+            self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
+
+    def msssim3f_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False):
+        """MS-SSIM of `count` device-resident pairs of float32 volumes (a Params3F array) through rmgr_ssim_hip_compute_msssim3f_device: a
+        float32 array, and with per_scale=True also a (count, scales, 2) float64 array of [pair][scale]{mcs, mssim}."""
+        return _msssimf_call("rmgr_ssim_hip_compute_msssim3f_device", self.handle, params_array, count, data_range, scales, weights, per_scale)
+
+    def enqueue_msssim3f(self, params_array, count, data_range, values_dev_ptr, means_dev_ptr, scales=5, weights=None):
+        """rmgr_ssim_hip_enqueue_msssim3f: per-pair fp64 values and count x scales x 2 fp64 means into device memory, asynchronously on the
+        context's stream."""
+        _check("rmgr_ssim_hip_enqueue_msssim3f", self.lib.rmgr_ssim_hip_enqueue_msssim3f(
+            self.handle, count, params_array, data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+
+    def enqueue_msssim3f_grad(self, params_array, count, data_range, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5, weights=None):
+        """rmgr_ssim_hip_enqueue_msssim3f_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes, from the forward's
+        means (device memory), into the volumes the Grad3F arrays describe; asynchronous on the context's stream, no host synchronisation."""
+        _check("rmgr_ssim_hip_enqueue_msssim3f_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3f_grad(
             self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
 
     def msssimh_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False):

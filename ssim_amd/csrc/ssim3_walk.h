@@ -1,11 +1,11 @@
-// ssim3_walk.h -- the slice walk of SSIM on VOLUMES and its adjoint, written once for the five kernel files of the family
-// (ssim3f / ssim3w / ssim3h / ssim3k / ssim3hk _kernels.hip).  Not installed, and included by those five files only: each of them
+// ssim3_walk.h -- the slice walk of SSIM on VOLUMES and its adjoint, written once for the kernel files of the family
+// (ssim3f / ssim3w / ssim3h / ssim3k / ssim3hk / msssim3f _kernels.hip).  Not installed, and included by those six files only: each of them
 // keeps its __global__ kernels -- their names, template parameters and launch bounds, which its tests count and budget -- as one-line
 // calls of walk_body and adjoint_body, and its launch_* functions.  Everything here has internal linkage, so an instantiation and its
 // LDS planes belong to the one kernel of the including file that calls it.  The definition the kernels implement is in
 // include/rmgr/ssim-hip.h; tests/ssim3f_model.py and tests/ssim3k_model.py restate it in float64 and restate the arithmetic below in fp32.
 //
-// The bodies are templates on three things, and on nothing else:
+// The bodies are templates on these things, and on nothing else:
 //  * Sample: how a sample gets into a register and how a gradient voxel leaves one.  SampleF32 is a float load / store.  SampleH<TYPE>
 //    is a 2-byte load and an exact widening (bfloat16 is the upper half of a float32, a shift; float16 goes through the hardware
 //    convert, which keeps subnormals and maps NaN and Inf to NaN and Inf), and one rounding to nearest-even before a 2-byte store
@@ -22,9 +22,19 @@
 //    (double(W) double(H) double(D))) for the whole volume.  kKPerVoxel: k(p) = gMap(p), read per voxel through the pair's GradOut3FDesc.
 //    kKEither: a branch on a kernel argument between the two (g_out != NULL: uniform).  The form is a compile-time choice of each kernel
 //    because the run-time branch costs registers.  The product k d is the same instruction in all three, so a constant volume gMap
-//    gives the uniform form's bits.
+//    gives the uniform form's bits.  kKScale (the multi-scale form, msssim3f_kernels.hip): k = g_out[volume] as it stands, the k_s of that
+//    volume at the launch's scale, computed on the device; a volume whose k is 0 is not walked at all (its adjoint writes +0 without
+//    reading a coefficient).
+//  * FORM (walk_body, a defaulted parameter: the five single-scale files do not name it).  kFormSsim: SSIM.  kFormMulti: a scale of
+//    MS-SSIM that is not the last -- MODE 0 keeps TWO fp64 column sums, cs = A2 / B2 and ssim, and flushes two partials per cell,
+//    [cell]{cs, ssim}, the ssim one with the bits of kFormSsim; MODE 1 / 2 / 3 writes the partial derivatives of cs alone, d_ab = 2 / B2,
+//    d_aa = -cs / B2, d_mu = -2 mu_a' d_aa - mu_b' d_ab (no luminance part in the centred variables).
+//  * MS (adjoint_body, defaulted likewise).  kMsNone.  kMsLast: the coarsest scale of MS-SSIM -- k = g_out[volume] is read, and a volume
+//    whose k is 0 gets +0 in every gradient voxel, whatever its samples are.  kMsUp: a finer scale -- the same, and every voxel adds the
+//    adjoint of the clamped 2 x 2 x 2 mean, fp32(0.125 c g_{s+1}(x >> 1, y >> 1, z >> 1)), before its single store; the coarser scale's
+//    dense gradient volumes come through args.up, a member only the multi-scale file's argument struct has.
 //
-// walk_body<Sample, R, MODE, KFORM>.  One 256-lane workgroup owns a 16 x 16 tile of (x, y) at an absolute position and walks a chunk of
+// walk_body<Sample, R, MODE, KFORM, FORM>.  One 256-lane workgroup owns a 16 x 16 tile of (x, y) at an absolute position and walks a chunk of
 // z.  Per source slice (edge-clamped on every axis, any step / stride / sliceStride, 64-bit offsets) the workgroup loads the tile + R
 // of A and B one slice ahead into registers, centres them, writes (a', b') and (a'^2 + b'^2, a'b') into LDS, runs the x pass (LDS to
 // LDS) and the y pass on its own column (one lane = one column of z), and scatters the four blurred values into the register rings (the
@@ -34,7 +44,7 @@
 // scratch.  The lane that owns column (qx, qy) reads a per-voxel k of output slice z = s - R at the top of the slice iteration, before
 // the two barriers: its latency sits under the LDS passes.  A lane outside the volume, or a warm-up iteration (z < z0), issues no load.
 //
-// adjoint_body<Sample, R, WHICH>.  The same walk over the coefficient volumes, zero outside the volume: adjoint x pass and y pass in
+// adjoint_body<Sample, R, WHICH, MS>.  The same walk over the coefficient volumes, zero outside the volume: adjoint x pass and y pass in
 // LDS as weighted gathers, the adjoint z pass in register rings, then dLoss/da = Gt(k d_mu_a) + 2 a' Gt(k d_aa) + b' Gt(k d_ab).
 //
 // Chunks.  A chunk of z starts R slices early and runs R slices late (2R warm-up slices); every output voxel receives the 2R + 1 slice
@@ -152,11 +162,13 @@ __device__ __forceinline__ f2 centre_of(const typename Sample::Pair& pd, int W, 
     return f2{__builtin_fabsf(sa) <= range ? sa : 0.0f, __builtin_fabsf(sb) <= range ? sb : 0.0f};
 }
 
-enum { kKUniform, kKPerVoxel, kKEither };
+enum { kKUniform, kKPerVoxel, kKEither, kKScale };
+enum { kFormSsim, kFormMulti };
+enum { kMsNone, kMsLast, kMsUp };
 
 // MODE 0: value, map, sums.  MODE 1 / 2 / 3: the coefficient volumes of dLoss/dA, dLoss/dB, both.  The statistics are computed in the
 // same order in all four.
-template <class Sample, int R, int MODE, int KFORM>
+template <class Sample, int R, int MODE, int KFORM, int FORM = kFormSsim>
 __device__ __forceinline__ void walk_body(const ArgsOf<Sample>& args)
 {
     typedef Shape<R> S;
@@ -166,7 +178,7 @@ __device__ __forceinline__ void walk_body(const ArgsOf<Sample>& args)
     __shared__ __attribute__((aligned(16))) f2 inQ[NIN];      // (a'^2 + b'^2, a'b')
     __shared__ __attribute__((aligned(16))) f2 Hab[NROW];     // x pass, 16 + 2R rows x 16 columns
     __shared__ __attribute__((aligned(16))) f2 Hq[NROW];
-    __shared__ double red[4];
+    __shared__ double red[MODE == 0 && FORM == kFormMulti ? 8 : 4];
 
     const int tid = threadIdx.x, lx = tid & (T - 1), ly = tid >> 4;
     const int W = (int)args.width, H = (int)args.height, D = (int)args.depth;
@@ -207,7 +219,10 @@ __device__ __forceinline__ void walk_body(const ArgsOf<Sample>& args)
     float k_vol = 0.0f;
     gptr_cf32 pg = nullptr;
     int64_t offG = 0, g_slice = 0;
-    if constexpr (MODE != 0) {
+    if constexpr (MODE != 0 && KFORM == kKScale) {
+        k_vol = ((gptr_cf32)args.g_out)[pl.vol];
+        if (k_vol == 0.0f) return;                 // the whole workgroup: the adjoint of such a volume reads no coefficient
+    } else if constexpr (MODE != 0) {
         if (KFORM == kKUniform || (KFORM == kKEither && args.g_out)) {
             k_vol = (float)((double)((gptr_cf32)args.g_out)[pl.vol] / ((double)W * (double)H * (double)D));
         } else {
@@ -221,7 +236,7 @@ __device__ __forceinline__ void walk_body(const ArgsOf<Sample>& args)
     f2 accAB[NT], accQ[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) accAB[i] = accQ[i] = f2{0.0f, 0.0f};
-    double colsum = 0.0;
+    double colsum = 0.0, colsum_cs = 0.0;
 
     fetch(pl.z0 - R);
 #pragma unroll 1
@@ -229,7 +244,7 @@ __device__ __forceinline__ void walk_body(const ArgsOf<Sample>& args)
         // 0. k of the slice this iteration finishes, z = s - R < z_end; no address is formed outside the volume or during the warm-up
         const int z = s - R;
         float k = k_vol;
-        if constexpr (MODE != 0 && KFORM != kKUniform) {
+        if constexpr (MODE != 0 && KFORM != kKUniform && KFORM != kKScale) {
             if ((KFORM == kKPerVoxel || pg) && inside && z >= pl.z0)
                 k = pg[offG + (int64_t)z * g_slice];
         }
@@ -295,6 +310,10 @@ __device__ __forceinline__ void walk_body(const ArgsOf<Sample>& args)
         const float B1 = tm + args.c1, B2 = sS + args.c2;
         if constexpr (MODE == 0) {
             const float v = opaque(A1 * A2) * __builtin_amdgcn_rcpf(opaque(B1 * B2));
+            if constexpr (FORM == kFormMulti) {
+                const float cs = A2 * __builtin_amdgcn_rcpf(B2);
+                if (inside) colsum_cs += (double)cs;
+            }
             if (inside) {
                 colsum += (double)v;
                 if (pd.map)
@@ -306,21 +325,43 @@ __device__ __forceinline__ void walk_body(const ArgsOf<Sample>& args)
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
                 if ((tid & 63) == 0) red[tid >> 6] = t;
+                if constexpr (FORM == kFormMulti) {
+                    double u = colsum_cs;
+                    colsum_cs = 0.0;
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) u += __shfl_xor(u, off, 64);
+                    if ((tid & 63) == 0) red[4 + (tid >> 6)] = u;
+                }
                 __syncthreads();
                 if (tid == 0) {
                     const uint64_t cell = (((uint64_t)pl.vol * args.cells_z + (uint32_t)z / kS3CellZ) * args.tiles_y + pl.ty) * args.tiles_x + pl.tx;
-                    ((gptr_f64)args.partials)[cell] = (red[0] + red[1]) + (red[2] + red[3]);
+                    if constexpr (FORM == kFormMulti) {
+                        ((gptr_f64)args.partials)[2 * cell] = (red[4] + red[5]) + (red[6] + red[7]);
+                        ((gptr_f64)args.partials)[2 * cell + 1] = (red[0] + red[1]) + (red[2] + red[3]);
+                    } else {
+                        ((gptr_f64)args.partials)[cell] = (red[0] + red[1]) + (red[2] + red[3]);
+                    }
                 }
             }
         } else {
-            const float r1 = __builtin_amdgcn_rcpf(B1), r2 = __builtin_amdgcn_rcpf(B2);
-            const float r12 = opaque(r1 * r2);
-            const float ssim = opaque(opaque(A1 * A2) * r12);
-            const float dab = opaque(opaque(2.0f * A1) * r12);
-            const float daa = -opaque(ssim * r2);
-            const float f1 = opaque(A2 * r12), f2_ = opaque(ssim * r1);
-            const float dmA = opaque(opaque(opaque(opaque(2.0f * uB) * f1) - opaque(opaque(2.0f * uA) * f2_)) - opaque(opaque(2.0f * mm.x) * daa)) - opaque(mm.y * dab);
-            const float dmB = opaque(opaque(opaque(opaque(2.0f * uA) * f1) - opaque(opaque(2.0f * uB) * f2_)) - opaque(opaque(2.0f * mm.y) * daa)) - opaque(mm.x * dab);
+            float dab, daa, dmA, dmB;
+            if constexpr (FORM == kFormMulti) {
+                const float r2 = __builtin_amdgcn_rcpf(B2);
+                const float cs = opaque(A2 * r2);
+                dab = opaque(2.0f * r2);
+                daa = -opaque(cs * r2);
+                dmA = -opaque(opaque(2.0f * mm.x) * daa) - opaque(mm.y * dab);
+                dmB = -opaque(opaque(2.0f * mm.y) * daa) - opaque(mm.x * dab);
+            } else {
+                const float r1 = __builtin_amdgcn_rcpf(B1), r2 = __builtin_amdgcn_rcpf(B2);
+                const float r12 = opaque(r1 * r2);
+                const float ssim = opaque(opaque(A1 * A2) * r12);
+                dab = opaque(opaque(2.0f * A1) * r12);
+                daa = -opaque(ssim * r2);
+                const float f1 = opaque(A2 * r12), f2_ = opaque(ssim * r1);
+                dmA = opaque(opaque(opaque(opaque(2.0f * uB) * f1) - opaque(opaque(2.0f * uA) * f2_)) - opaque(opaque(2.0f * mm.x) * daa)) - opaque(mm.y * dab);
+                dmB = opaque(opaque(opaque(opaque(2.0f * uA) * f1) - opaque(opaque(2.0f * uB) * f2_)) - opaque(opaque(2.0f * mm.y) * daa)) - opaque(mm.x * dab);
+            }
             if (inside) {
                 const gptr_f32 out = (gptr_f32)args.coef + (uint64_t)pl.vol * NP * voxels + ((uint64_t)z * H + qy) * W + qx;
                 out[0] = k * (MODE == 2 ? dmB : dmA);
@@ -347,8 +388,8 @@ __device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float
 
 // WHICH: 1 dLoss/dA, 2 dLoss/dB, 3 both.  Every pass is a gather in the order j = -R .. R, the first product plain, the others fused; a
 // coefficient outside the volume is 0 (the clamp is in the weights).  A 16-bit gradient voxel is rounded once on its way out.
-template <class Sample, int R, int WHICH>
-__device__ __forceinline__ void adjoint_body(const ArgsOf<Sample>& args)
+template <class Sample, int R, int WHICH, int MS = kMsNone, class Args = ArgsOf<Sample>>
+__device__ __forceinline__ void adjoint_body(const Args& args)
 {
     typedef Shape<R> S;
     constexpr int TIN = S::TIN, NIN = S::NIN, NROW = S::NROW, NLOAD = S::NLOAD, NT = S::NT;
@@ -396,6 +437,38 @@ __device__ __forceinline__ void adjoint_body(const ArgsOf<Sample>& args)
 
     const int qx = pl.x0 + lx, qy = pl.y0 + ly;
     const bool inside = qx < W && qy < H;
+
+    // The multi-scale forms: what the voxel adds from the coarser scale, and the volumes whose k is 0.
+    typename Sample::Grad ud = typename Sample::Grad();
+    float cxy = 0.125f;
+    if constexpr (MS == kMsUp) {
+        ud = args.up[pl.vol];
+        cxy = 0.125f * ((((W & 1) && qx == W - 1) ? 2.0f : 1.0f) * (((H & 1) && qy == H - 1) ? 2.0f : 1.0f));
+    }
+    // fp32(0.125 c g_{s+1}(x >> 1, y >> 1, z >> 1)); 0.125 c is a power of two: the product is exact
+    // the coarser volumes are dense: ceil(W / 2) x ceil(H / 2) x ceil(D / 2), x fastest
+    auto upstream = [&](const float* gup, int z) -> float {
+        const float c = cxy * (((D & 1) && z == D - 1) ? 2.0f : 1.0f);
+        return c * ((gptr_cf32)gup)[((int64_t)(z >> 1) * ((H + 1) >> 1) + (qy >> 1)) * ((W + 1) >> 1) + (qx >> 1)];
+    };
+    if constexpr (MS != kMsNone) {
+        if (((gptr_cf32)args.g_out)[pl.vol] == 0.0f) {       // the whole workgroup: this scale contributes +0 whatever the samples are
+            if (!inside) return;
+            for (int z = pl.z0; z < pl.z_end; ++z) {
+                if constexpr (WHICH != 2) {
+                    float g = 0.0f;
+                    if constexpr (MS == kMsUp) g += upstream(ud.ga, z);
+                    Sample::store(gd.ga, (int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride + (int64_t)z * gd.ga_slice, g);
+                }
+                if constexpr (WHICH != 1) {
+                    float g = 0.0f;
+                    if constexpr (MS == kMsUp) g += upstream(ud.gb, z);
+                    Sample::store(gd.gb, (int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride + (int64_t)z * gd.gb_slice, g);
+                }
+            }
+            return;
+        }
+    }
     float wx[NT], wy[NT];
 #pragma unroll
     for (int j = -R; j <= R; ++j) {
@@ -454,11 +527,13 @@ __device__ __forceinline__ void adjoint_body(const ArgsOf<Sample>& args)
         const float a = Sample::load(pd.a, (int64_t)qx * pd.a_step + (int64_t)qy * pd.a_stride + (int64_t)z * pd.a_slice) - cen.x;
         const float b = Sample::load(pd.b, (int64_t)qx * pd.b_step + (int64_t)qy * pd.b_stride + (int64_t)z * pd.b_slice) - cen.y;
         if constexpr (WHICH != 2) {
-            const float g = opaque(acc[0][0] + opaque(opaque(2.0f * a) * acc[1][0])) + opaque(b * acc[2][0]);
+            float g = opaque(acc[0][0] + opaque(opaque(2.0f * a) * acc[1][0])) + opaque(b * acc[2][0]);
+            if constexpr (MS == kMsUp) g = opaque(g) + upstream(ud.ga, z);
             Sample::store(gd.ga, (int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride + (int64_t)z * gd.ga_slice, g);
         }
         if constexpr (WHICH != 1) {
-            const float g = opaque(acc[WHICH == 3 ? 3 : 0][0] + opaque(opaque(2.0f * b) * acc[1][0])) + opaque(a * acc[2][0]);
+            float g = opaque(acc[WHICH == 3 ? 3 : 0][0] + opaque(opaque(2.0f * b) * acc[1][0])) + opaque(a * acc[2][0]);
+            if constexpr (MS == kMsUp) g = opaque(g) + upstream(ud.gb, z);
             Sample::store(gd.gb, (int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride + (int64_t)z * gd.gb_slice, g);
         }
     }

@@ -77,6 +77,14 @@ and SSIM3DLoss.
         loss = SSIM3DLoss()(net(x), y.bfloat16())                   # read as bfloat16; the gradient is bfloat16
         loss = SSIM3DLoss(win_size=7, window="uniform")(net(x), y.bfloat16())      # MONAI's / skimage's 7-tap box, still 2 B/voxel
 
+Multi-scale SSIM of volumes.  ms_ssim3d(x, y, data_range, scales, weights) and MSSSIM3DLoss take (..., D, H, W) float32 tensors
+(rmgr_ssim_hip_enqueue_msssim3f, _msssim3f_grad): ms_ssim's product over a pyramid that halves all three axes, as pytorch-msssim's
+MS_SSIM(spatial_dims=3) does with avg_pool3d.  That one uses a valid window and zero-padded pooling and refuses small sides; this one
+clamps the window and the pooling at the borders and runs down to 1 x 1 x 1, so the values are close, not equal.  float32 and the
+11-tap window only for now: 16-bit tensors are a TypeError.
+
+    loss = 0.16 * (x - y).abs().mean() + 0.84 * MSSSIM3DLoss()(x, y)       # x, y: (N, C, D, H, W) float32 on the GPU
+
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
 import ctypes
@@ -375,22 +383,23 @@ class SSIMLoss(object):
         return loss.mean() if self.reduction == "mean" else loss
 
 
-def _check_scales(scales, weights):
-    """The documented errors of ms_ssim's scales and weights, before any GPU call.  Returns (scales, weights as a tuple of floats or None)."""
+def _check_scales(scales, weights, name="ms_ssim"):
+    """The documented errors of ms_ssim's scales and weights (`name`: the function the message names), before any GPU call.  Returns
+    (scales, weights as a tuple of floats or None)."""
     if isinstance(scales, bool) or not isinstance(scales, int):
-        raise TypeError("ms_ssim: scales must be an int, got %r" % (scales,))
+        raise TypeError("%s: scales must be an int, got %r" % (name, scales))
     if not 1 <= scales <= api.MSSSIM_MAX_SCALES:
-        raise ValueError("ms_ssim: scales must be 1 .. %d, got %d" % (api.MSSSIM_MAX_SCALES, scales))
+        raise ValueError("%s: scales must be 1 .. %d, got %d" % (name, api.MSSSIM_MAX_SCALES, scales))
     if weights is None:
         if scales != 5:
-            raise ValueError("ms_ssim: the default weights are Wang's five: pass %d weights for scales=%d" % (scales, scales))
+            raise ValueError("%s: the default weights are Wang's five: pass %d weights for scales=%d" % (name, scales, scales))
         return scales, None
     w = tuple(float(v) for v in weights)
     if len(w) != scales:
-        raise ValueError("ms_ssim: %d weights for %d scales" % (len(w), scales))
+        raise ValueError("%s: %d weights for %d scales" % (name, len(w), scales))
     for v in w:
         if not (v >= 0.0) or math.isinf(v):
-            raise ValueError("ms_ssim: weights must be finite and >= 0, got %r" % (weights,))
+            raise ValueError("%s: weights must be finite and >= 0, got %r" % (name, weights))
     return scales, w
 
 
@@ -516,7 +525,8 @@ class MSSSIMLoss(object):
 # (the rmgr_ssim_hip_*_ssim3f_win* entries; what MONAI, torchmetrics and pytorch-msssim call win_size / kernel_size / sigma with
 # spatial_dims=3, and skimage's 7-tap box).  The defaults are the engine's window and take exactly the path without these arguments; any
 # other window is stored on the autograd context and the backward runs under it -- for float16 / bfloat16 volumes too, on the
-# rmgr_ssim_hip_*_ssim3h_win* entries.  A multi-scale form is a follow-up.
+# rmgr_ssim_hip_*_ssim3h_win* entries.  The multi-scale form, ms_ssim3d and MSSSIM3DLoss, is at the end of the file: float32 and the
+# engine's window only.
 
 _function3d = None
 
@@ -804,3 +814,93 @@ def ssim3d_map_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gau
         loss = 1 - (mask * m).sum() / mask.sum()"""
     win = _window(x, y, win_size, win_sigma, window, "ssim3d_map_amp", fixed16=False)
     return _ssim3d_map(x, y, _check3d(x, y, data_range, "ssim3d_map_amp", half=True), win)
+
+
+# ---- volumes: multi-scale SSIM ----------------------------------------------------------------------------------------------------------------
+# ms_ssim3d(x, y, data_range, scales, weights) is the definition in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_msssim3f): ms_ssim's
+# weighted product with ssim3d's per-voxel terms over a pyramid that halves x, y and z.  The backward is
+# rmgr_ssim_hip_enqueue_msssim3f_grad, from x, y and the (volumes, scales, 2) float64 per-scale means the forward keeps.  float32 and the
+# engine's 11-tap window only; float16 / bfloat16 volumes, a window and a multi-scale map gradient are follow-ups.
+
+_ms_function3d = None
+
+
+def _make_ms_function3d():
+    import torch
+
+    class _MSSSIM3D(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, data_range, scales, weights):
+            lead = x.shape[:-3]
+            params, n = _params3d(x, y)
+            values = torch.empty(n, dtype=torch.float64, device=x.device)
+            means = torch.empty((n, scales, 2), dtype=torch.float64, device=x.device)
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                _context(x.device, work).enqueue_msssim3f(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights)
+                if work is not cur:
+                    cur.wait_stream(work)
+            ctx.save_for_backward(x, y, means)
+            ctx.data_range, ctx.scales, ctx.weights = data_range, scales, weights
+            return values.to(torch.float32).reshape(lead)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            x, y, means = ctx.saved_tensors
+            d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
+            want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_x or want_y):
+                return None, None, None, None, None
+            params, n = _params3d(x, y)
+            g = grad_out.to(torch.float32).reshape(-1).contiguous()
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None
+            gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
+            if n:
+                cur, work = _working_stream(torch, x.device)
+                if work is not cur:
+                    work.wait_stream(cur)
+                ga = _grad_volumes(gx, n, d, h, w) if want_x else None
+                gb = _grad_volumes(gy, n, d, h, w) if want_y else None
+                _context(x.device, work).enqueue_msssim3f_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales, ctx.weights)
+                if work is not cur:
+                    cur.wait_stream(work)
+            return gx, gy, None, None, None
+
+    return _MSSSIM3D
+
+
+def ms_ssim3d(x, y, data_range=1.0, scales=5, weights=None):
+    """Per-volume multi-scale SSIM of two float32 GPU tensors of identical shape (..., D, H, W), any strides (each volume is addressed in
+    place, no copy): a float32 tensor of shape x.shape[:-3].  The 11-tap Gaussian window (sigma 1.5, clamped edges) on all three axes at
+    every scale; all three axes are halved from scale to scale, down to 1 x 1 x 1 if need be.  weights None: Wang's five (scales must be
+    5); else `scales` finite weights >= 0.  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that
+    need it, from x, y and the (volumes, scales, 2) float64 per-scale means the forward keeps.  It runs on torch's current stream through
+    the cached context, as ssim() does.  TypeError / ValueError as ssim3d() and ms_ssim(), under this function's name; float16 and
+    bfloat16 tensors are a TypeError: the 3-D multi-scale path is float32 for now."""
+    import torch
+    if isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and (x.dtype in (torch.float16, torch.bfloat16) or y.dtype in (torch.float16, torch.bfloat16)):
+        raise TypeError("ms_ssim3d: the 3-D multi-scale path is float32 for now, got %s and %s" % (x.dtype, y.dtype))
+    global _ms_function3d
+    r = _check3d(x, y, data_range, "ms_ssim3d")
+    scales, w = _check_scales(scales, weights, "ms_ssim3d")
+    if _ms_function3d is None:
+        _ms_function3d = _make_ms_function3d()
+    return _ms_function3d.apply(x, y, r, scales, w)
+
+
+class MSSSIM3DLoss(object):
+    """1 - ms_ssim3d(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per volume).  A plain callable:
+    it has no parameters.  float32 tensors, as ms_ssim3d()."""
+
+    def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean"):
+        if reduction not in ("mean", "none"):
+            raise ValueError("MSSSIM3DLoss: reduction must be 'mean' or 'none', got %r" % (reduction,))
+        _check_scales(scales, weights, "MSSSIM3DLoss")
+        self.data_range, self.scales, self.weights, self.reduction = data_range, scales, weights, reduction
+
+    def __call__(self, x, y):
+        loss = 1.0 - ms_ssim3d(x, y, self.data_range, self.scales, self.weights)
+        return loss.mean() if self.reduction == "mean" else loss
