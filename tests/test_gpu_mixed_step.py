@@ -166,12 +166,13 @@ class PlaneOut(Out):
 
 
 class VolOut(Out):
-    """A D x H x W output volume: samples `step` floats apart with sentinels between them."""
+    """A D x H x W output volume: samples `step` elements apart with sentinels between them; float32, or uint16 (a 16-bit gradient)."""
 
-    def __init__(self, mem, name, d, h, w, step=1):
+    def __init__(self, mem, name, d, h, w, step=1, dtype=np.float32):
+        fill = FILL32 if dtype == np.float32 else FILL16
         owned = np.zeros((d, h, w, step), bool)
         owned[..., step - 1] = True
-        Out.__init__(self, mem, name, np.full((d, h, w, step), FILL32, np.float32), owned, ptr_offset=4 * (step - 1))
+        Out.__init__(self, mem, name, np.full((d, h, w, step), fill, dtype), owned, ptr_offset=np.dtype(dtype).itemsize * (step - 1))
         self.strides = (step, step * w, step * w * h)            # step, stride, sliceStride
 
     def plane(self, host):
@@ -541,9 +542,15 @@ def order_of(ops, how, seed=SHUFFLE_SEED, twins=(), phases=False):
     return out
 
 
+def extent(op):
+    """(H, W) of an op on planes, (H, W, D) of one on volumes."""
+    return tuple(op.shape) + ((op.depth,) if hasattr(op, "depth") else ())
+
+
 def check_order(order, seq):
     """What every order must keep: each op after the ops it names; between a multi-scale forward and its backward the forwards that
-    overwrite the pyramid; the twins first and last."""
+    overwrite the pyramid (the same entry on other pairs of the same shape and count, the same entry at another shape, another
+    multi-scale entry -- of the forward's shape and count where it has the forward's dimensions); the twins first and last."""
     pos = dict((op.at, i) for i, op in enumerate(order))
     for op in order:
         for a in op.after:
@@ -559,8 +566,9 @@ def check_order(order, seq):
         for op in order:
             if hasattr(op, "between"):
                 f, (s, d, o) = op.of, op.between
-                assert (s.entry, s.shape, s.n, s.config) == (f.entry, f.shape, f.n, f.config) and (d.entry, d.config) == (f.entry, f.config)
-                assert d.shape != f.shape and o.entry != f.entry and (o.shape, o.n) == (f.shape, f.n)
+                assert (s.entry, extent(s), s.n, s.config) == (f.entry, extent(f), f.n, f.config) and (d.entry, d.config) == (f.entry, f.config)
+                assert extent(d) != extent(f) and o.entry != f.entry
+                assert (extent(o), o.n) == (extent(f), f.n) or len(extent(o)) != len(extent(f))
 
 
 def show(title, order):
@@ -597,16 +605,16 @@ def assert_same_bytes(seq, lone, what):
 # ---- the module's fixtures ----------------------------------------------------------------------------------------------------------------
 
 class Meter(object):
-    def __init__(self, ctx):
-        self.ctx, self.t0 = ctx, time.time()
+    def __init__(self, ctx, what="mixed step"):
+        self.ctx, self.t0, self.what = ctx, time.time(), what
         self.free0 = self.min_free = ssim_amd.memory_info(ctx)[0]
 
     def sample(self):
         self.min_free = min(self.min_free, ssim_amd.memory_info(self.ctx)[0])
 
     def close(self):
-        print("\nmixed step: module wall time %.1f s; peak device memory in use by the module %.1f MiB" % (
-            time.time() - self.t0, (self.free0 - self.min_free) / 2.0 ** 20))
+        print("\n%s: module wall time %.1f s; peak device memory in use by the module %.1f MiB" % (
+            self.what, time.time() - self.t0, (self.free0 - self.min_free) / 2.0 ** 20))
 
 
 @pytest.fixture(scope="module")
@@ -616,13 +624,12 @@ def meter(gpu_ctx):
     m.close()
 
 
-@pytest.fixture(scope="module")
-def lone(gpu_ctx, manifest, meter):
-    """{op name: {output name: bytes}} of every op issued ALONE on a context created for that purpose, synchronised after every op and
-    closed at the end; computed once and shared.  What the lone results themselves fail -- a sentinel changed, a model missed -- is kept
-    under "" for test_lone_results_keep_their_sentinels_and_meet_the_models; the other tests compare with these bytes either way."""
+def lone_results(seq, meter, hold):
+    """{op name: {output name: bytes}} of every op of `seq` issued ALONE on a context created for that purpose, synchronised after every
+    op and closed at the end; `seq` is freed.  What the lone results themselves fail -- a sentinel changed, a model missed (hold(ctx, seq,
+    results)) -- is kept under "" for test_lone_results_keep_their_sentinels_and_meet_the_models; the other tests compare with these bytes
+    either way."""
     assert not _device_error, "an earlier call left a device error: %r" % _device_error
-    seq = Sequence(gpu_ctx, manifest)
     ctx = ssim_amd.Context(0)
     try:
         out = {}
@@ -638,7 +645,7 @@ def lone(gpu_ctx, manifest, meter):
                     assert np.array_equal(got[~o.owned], o.init[~o.owned]), (op.name, o.name, "a sentinel changed")
                     # (a 16-bit gradient may equal the 16-bit sentinel by coincidence: 203.25 in float16)
                     assert np.count_nonzero(got[o.owned] == o.init[o.owned]) <= (2 if o.init.itemsize == 2 else 0), (op.name, o.name, "elements the op owns were not written")
-            hold_to_the_models(ctx, seq, out)
+            hold(ctx, seq, out)
             out[""] = None
         except (AssertionError, ssim_amd.SsimError):
             out[""] = traceback.format_exc()
@@ -646,6 +653,13 @@ def lone(gpu_ctx, manifest, meter):
         ctx.close()
         seq.free()
     return out
+
+
+@pytest.fixture(scope="module")
+def lone(gpu_ctx, manifest, meter):
+    """lone_results of the sequence: computed once and shared."""
+    assert not _device_error, "an earlier call left a device error: %r" % _device_error
+    return lone_results(Sequence(gpu_ctx, manifest), meter, hold_to_the_models)
 
 
 @pytest.fixture

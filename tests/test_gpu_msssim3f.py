@@ -20,6 +20,7 @@ import pytest
 import content_classes as C
 import msssim3f_model as M
 import msssim3f_plan as MP
+import ssim3f_chunks_inputs as CH
 import ssim3f_model as S
 import ssim3f_plan as P
 import ssim_amd
@@ -218,23 +219,38 @@ def test_seven_pairs_in_one_call_and_the_same_call_twice(gpu_ctx):
 
 @pytest.mark.parametrize("size,scales", [((17, 17, 131), 3), ((5, 3, 1000), 4)], ids=lambda s: str(s))
 def test_chunk_depths_of_every_scale_change_no_bit(gpu_ctx, size, scales):
-    """Launches of 1 and of 40 volumes: plan3f picks other chunk depths (asserted through tests/ssim3f_plan.py, per scale); every value,
-    mean and gradient of the 40 has the lone launch's bits."""
+    """Launches of 1 and of 40 volumes: plan3f picks other chunk depths (asserted through tests/ssim3f_plan.py, per scale).  The 40 are
+    drawn from seven distinct pairs and five dLoss/dS values (ssim3f_chunks_inputs.picks: neighbours differ), so that a volume-index
+    mix-up in the pyramid, the coarse gradient pyramids, k_s or the coefficient scratch of any scale shows: every value, mean and
+    gradient has the bits of ITS OWN (pair, dLoss/dS) combination launched alone.  One lone value and gradient against the float64
+    model."""
+    n = 40
     cus = int(re.search(r"(\d+) CUs", gpu_ctx.describe()).group(1))
-    depths = {n: [P.plan3f(*(MP.dims(*size, s) + (n, cus))).chunk_slices for s in range(scales)] for n in (1, 40)}
+    depths = {k: [P.plan3f(*(MP.dims(*size, s) + (k, cus))).chunk_slices for s in range(scales)] for k in (1, n)}
     print("chunk depths per scale on %d CUs: %r" % (cus, depths))
-    assert depths[1][0] != depths[40][0] and len(set(depths[40])) > 1, depths
-    a, b = C.random_pair(size[::-1], 1)
-    va, vb = Vol(gpu_ctx, a.shape, "dense", a), Vol(gpu_ctx, a.shape, "dense", b)
-    lone = run(gpu_ctx, None, 1.0, scales, uniform(scales), [-0.75], inputs=[(va, vb)])
-    check = M.Model(a, b, 1.0).msssim(scales, uniform(scales))
-    assert abs(lone[0][0] - check[0]) <= VALUE_TOL
-    v, m, gr = run(gpu_ctx, None, 1.0, scales, uniform(scales), [-0.75] * 40, inputs=[(va, vb)] * 40)
-    for i in range(40):
-        assert same(v[i:i + 1], lone[0]) and same(m[i], lone[1][0]), i
-        assert same(gr[i][0], lone[2][0][0]) and same(gr[i][1], lone[2][0][1]), i
-    va.free()
-    vb.free()
+    assert depths[1][0] != depths[n][0] and len(set(depths[n])) > 1, depths
+    pairs = CH.pairs(size)
+    which, g_of = CH.picks(n, 3)
+    combos = list(zip(which.tolist(), g_of.tolist()))
+    assert len(set(which.tolist())) == CH.PAIRS and len(set(combos)) >= 30 and all(x != y for x, y in zip(combos, combos[1:])), combos
+    vols = [(Vol(gpu_ctx, a.shape, "dense", a), Vol(gpu_ctx, a.shape, "dense", b)) for a, b in pairs]
+    lone = {c: run(gpu_ctx, None, 1.0, scales, uniform(scales), [CH.G_OUTS[c[1]]], inputs=[vols[c[0]]]) for c in sorted(set(combos))}
+    k, g = combos[0]
+    model = M.Model(pairs[k][0], pairs[k][1], 1.0)
+    value, means = model.msssim(scales, uniform(scales))
+    assert min(float(means[s][1] if s == scales - 1 else means[s][0]) for s in range(scales)) >= 0.2, means      # the bounds' input condition
+    assert abs(lone[(k, g)][0][0] - value) <= VALUE_TOL
+    errs = [float(np.abs(got - want).max() / np.abs(want).max()) for got, want in zip(lone[(k, g)][2][0], model.grad(CH.G_OUTS[g], scales, uniform(scales)))]
+    print("pair %d at dLoss/dS %g alone: value %.3g (bound %.3g), gradients %.3g %.3g (bound %.3g)" % (
+        k, CH.G_OUTS[g], abs(lone[(k, g)][0][0] - value), VALUE_TOL, errs[0], errs[1], GRAD_TOL))
+    assert max(errs) <= GRAD_TOL, errs
+    v, m, gr = run(gpu_ctx, None, 1.0, scales, uniform(scales), [CH.G_OUTS[c[1]] for c in combos], inputs=[vols[c[0]] for c in combos])
+    for i, c in enumerate(combos):
+        assert same(v[i:i + 1], lone[c][0]) and same(m[i], lone[c][1][0]), (i, c)
+        assert same(gr[i][0], lone[c][2][0][0]) and same(gr[i][1], lone[c][2][0][1]), (i, c)
+    for va, vb in vols:
+        va.free()
+        vb.free()
 
 
 @pytest.mark.parametrize("layout", [k for k in LAYOUTS if k != "dense"])
@@ -272,20 +288,34 @@ def test_device_host_and_enqueue_entries_agree(gpu_ctx):
 
 def test_sub_batches_of_the_backward_scratch(gpu_ctx):
     """One more volume of 96^3 at two scales than a sub-batch of the backward for both gradients holds (tests/msssim3f_plan.py): two
-    sub-batches.  Every pair reads the same two device volumes; every value, mean and gradient has the bits of the lone call."""
+    sub-batches.  The volumes are drawn (ssim3f_chunks_inputs.picks) from three distinct pairs, 21 MB of inputs, and three dLoss/dS
+    values; the volumes around the sub-batch boundary differ from their neighbours in pair and in dLoss/dS, so that an offset into the
+    means, the dLoss/dS vector, the descriptors or the scratch that forgets the sub-batch's first volume shows.  Every value, mean and
+    gradient has the bits of its own (pair, dLoss/dS) combination launched alone."""
     size, scales = (96, 96, 96), 2
     n = MP.per_sub_batch(*size, scales, 2) + 1
     assert n == 68 and MP.sub_batches(*size, scales, 2, n) == [(0, 67), (67, 1)]
-    a, b = random_pair(size, 3)
-    va, vb = Vol(gpu_ctx, a.shape, "dense", a), Vol(gpu_ctx, a.shape, "dense", b)
-    lone = run(gpu_ctx, None, 1.0, scales, uniform(scales), [-0.75], inputs=[(va, vb)])
-    assert np.abs(lone[2][0][0]).max() > 0 and np.abs(lone[2][0][1]).max() > 0
-    v, m, gr = run(gpu_ctx, None, 1.0, scales, uniform(scales), [-0.75] * n, inputs=[(va, vb)] * n)
-    for i in range(n):
-        assert same(v[i:i + 1], lone[0]) and same(m[i], lone[1][0]), i
-        assert same(gr[i][0], lone[2][0][0]) and same(gr[i][1], lone[2][0][1]), i
-    va.free()
-    vb.free()
+    pairs = [random_pair(size, 3 + k) for k in range(3)]
+    g_outs = CH.G_OUTS[:3]
+    which, g_of = CH.picks(n, 5)
+    combos = [(k % len(pairs), g % len(g_outs)) for k, g in zip(which.tolist(), g_of.tolist())]
+    for i in (65, 66):                                           # the last two volumes of the first sub-batch, the only one of the second
+        assert combos[i][0] != combos[i + 1][0] and combos[i][1] != combos[i + 1][1], combos[65:]
+    assert len(set(combos)) == len(pairs) * len(g_outs)
+    vols = [(Vol(gpu_ctx, a.shape, "dense", a), Vol(gpu_ctx, a.shape, "dense", b)) for a, b in pairs]
+    lone = {c: run(gpu_ctx, None, 1.0, scales, uniform(scales), [g_outs[c[1]]], inputs=[vols[c[0]]]) for c in sorted(set(combos))}
+    for c in lone:
+        assert np.abs(lone[c][2][0][0]).max() > 0 and np.abs(lone[c][2][0][1]).max() > 0
+    for c in lone:                                               # distinct pairs and distinct dLoss/dS give distinct results
+        for o in lone:
+            assert c == o or not same(lone[c][2][0][0], lone[o][2][0][0]), (c, o)
+    v, m, gr = run(gpu_ctx, None, 1.0, scales, uniform(scales), [g_outs[c[1]] for c in combos], inputs=[vols[c[0]] for c in combos])
+    for i, c in enumerate(combos):
+        assert same(v[i:i + 1], lone[c][0]) and same(m[i], lone[c][1][0]), (i, c)
+        assert same(gr[i][0], lone[c][2][0][0]) and same(gr[i][1], lone[c][2][0][1]), (i, c)
+    for va, vb in vols:
+        va.free()
+        vb.free()
 
 
 def test_a_dozen_enqueues_share_the_scratch_in_stream_order(gpu_ctx):
