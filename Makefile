@@ -72,38 +72,19 @@ $(OBJ)/ssim16_kernels.o: $(SRC)/ssim16_kernels.hip $(SRC)/ssim16_kernels.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_ssimf*): its own file for the same reason.
-$(OBJ)/ssimf_kernels.o: $(SRC)/ssimf_kernels.hip $(SRC)/ssimf_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# Multi-scale SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_msssimf*): its own file for the same reason.
-$(OBJ)/msssimf_kernels.o: $(SRC)/msssimf_kernels.hip $(SRC)/msssimf_kernels.h $(SRC)/ssimf_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# SSIM of float16 / bfloat16 samples and its gradient (rmgr_ssim_hip_*_ssimh*): its own file for the same reason, and the same flags as
-# ssimf_kernels.o -- its results are held to that object's, bit for bit.
-$(OBJ)/ssimh_kernels.o: $(SRC)/ssimh_kernels.hip $(SRC)/ssimh_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# Multi-scale SSIM of float16 / bfloat16 samples and its gradient (rmgr_ssim_hip_*_msssimh*): scale 0's kernels; its own file for the same
-# reason, and the rule and flags of msssimf_kernels.o -- its results are held to that object's, bit for bit.
-$(OBJ)/msssimh_kernels.o: $(SRC)/msssimh_kernels.hip $(SRC)/msssimh_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# Gradient of the SSIM map for a per-pixel upstream gradient (rmgr_ssim_hip_enqueue_ssimf_map_grad / _ssimh_map_grad): its own file --
-# the tests of ssimf_kernels.hip and ssimh_kernels.hip count those files' kernels -- and the same flags: its results are held to those
-# objects', bit for bit.
-$(OBJ)/ssimw_kernels.o: $(SRC)/ssimw_kernels.hip $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# SSIM of float32 samples under a window of 3, 5, 7 or 9 taps, its gradient for both upstream forms, and the taps of every window
-# (rmgr_ssim_hip_*_ssimf_win*): its own file for the same reason, and the same flags as ssimf_kernels.o, whose flow it copies.
-$(OBJ)/ssimk_kernels.o: $(SRC)/ssimk_kernels.hip $(SRC)/ssimk_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
+# The 2-D float-sample family: six kernel files, one per group of entry points, whose tests count and budget their kernels.  The strip
+# walk, the reduction and the gradient tile are written once, in ssim2_walk.h, which every one of the six includes; each is its own
+# object for the reason above, and all are built with the same flags -- the 16-bit, windowed and multi-scale results are held to
+# ssimf_kernels.o's, bit for bit (-ffp-contract=off: tests/ssimf_model.py and tests/ssimk_model.py restate the arithmetic operation by
+# operation).
+#   ssimf    float32 samples under the 11-tap window and its gradient (rmgr_ssim_hip_*_ssimf*); the constants, the planner, the launch bound
+#   ssimh    float16 / bfloat16 samples and its gradient (rmgr_ssim_hip_*_ssimh*)
+#   ssimw    gradient of the map for a per-pixel upstream gradient (rmgr_ssim_hip_enqueue_ssimf_map_grad / _ssimh_map_grad)
+#   ssimk    float32 samples under a window of 3, 5, 7 or 9 taps, both upstream forms, and the taps of every window (rmgr_ssim_hip_*_ssimf_win*)
+#   msssimf  multi-scale SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_msssimf*); the pyramid, the product, k_s
+#   msssimh  multi-scale SSIM of float16 / bfloat16 samples (rmgr_ssim_hip_*_msssimh*): scale 0's kernels
+SSIM2_HDRS := $(SRC)/ssim2_walk.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/msssimh_kernels.h
+$(OBJ)/ssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/msssimh_kernels.o: $(OBJ)/%.o: $(SRC)/%.hip $(SSIM2_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -181,8 +162,12 @@ sanitize: lib oracle
 	$(CC) -O1 -g -std=c99 -D_GNU_SOURCE -ffp-contract=off -fno-math-errno -fopenmp -mavx2 -mfma -fsanitize=address,undefined -fno-omit-frame-pointer -Wall -shared -fPIC -o build/sanitize/libssim_oracle_asan.so oracle/ssim_oracle.c -lm
 	LD_PRELOAD=$$($(CC) -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 python3 tests/tools/sanitize_oracle.py $(abspath build/sanitize/libssim_oracle_asan.so) $(abspath .)
 
+# The objects of librmgr-ssim-hip.so but ssim_kernels.o, for tools/build_ab.sh (a second library with another build of those kernels).
+ab-objs:
+	@echo $(filter-out $(OBJ)/ssim_kernels.o,$(ABI_OBJS)) $(OBJ)/ssim_context.o $(OBJ)/ssim_openmp.o
+
 clean:
 	rm -rf build $(OUT) $(BIN)
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle clean install sanitize
+.PHONY: all lib oracle clean install sanitize ab-objs

@@ -1,412 +1,32 @@
 // msssimf_kernels.hip -- gfx950 kernels of multi-scale SSIM on float32 samples and of its gradient, behind
 // rmgr_ssim_hip_enqueue_msssimf, rmgr_ssim_hip_compute_msssimf_device / _host and rmgr_ssim_hip_enqueue_msssimf_grad.  The definition
-// they implement is in include/rmgr/ssim-hip.h; tests/msssimf_model.py restates it in float64 and restates the arithmetic below in fp32.
+// they implement is in include/rmgr/ssim-hip.h; tests/msssimf_model.py restates it in float64 and restates the arithmetic in fp32.
 //
 // Kept apart from ssimf_kernels.hip and msssim_kernels.hip on purpose: tests count and budget the kernels of those files, and the
-// uint8 multi-scale path's bits are pinned.  The strip and gradient choreographies are those of ssimf_kernels.hip, copied here, not
-// included.
+// uint8 multi-scale path's bits are pinned.  The strip walk and the gradient tile are those of ssimf_kernels.hip in their multi-scale
+// forms; see ssim2_walk.h.
 //
 //  * msssimf_down_kernel: one step of the pyramid, a launch of its own: scale s + 1 = ((P(2x,2y) + P(2x+1,2y)) + (P(2x,2y+1) +
 //    P(2x+1,2y+1))) * 0.25f of scale s, coordinates clamped, every operation rounded to fp32 in that order; A and B of a pair in one
 //    work-item.  Scale 0 is read at the caller's steps and strides, every coarser scale is a dense plane of the context's scratch.
-//  * msssimf_strip_kernel: the strip flow of ssimf_strip_kernel (one 64-lane wavefront = one strip of 128 output columns, LDS ring for
-//    the row pass, register rings for the column pass, n * rcp(d)) without a map and with TWO fp64 sums per cell: cs = A2 / B2 and
+//  * msssimf_strip_kernel: strip_body in the form kFormMulti: no map, TWO fp64 sums per cell, cs = A2 / B2 and
 //    ssim = A1 A2 / (B1 B2).  One launch per scale over that scale's descriptors.
 //  * msssimf_reduce_kernel: every (pair, scale, kind) sum of cell partials in a fixed order, divided by double(W_s) * double(H_s).
 //  * msssimf_finalise_kernel: the ReLU'd weighted product of a pair's means, in double.
 //  * msssimf_coef_kernel: k_s = gOut w_s MS / m_s / (double(W_s) * double(H_s)) per pair and scale, all 0 when MS = 0.
-//  * msssimf_grad_kernel: the fused recomputing gradient kernel of ssimf_kernels.hip (32 x 32 tiles at absolute positions) in a cs form
-//    and an ssim form, whose epilogue adds the coarser scale's gradient through the adjoint of the clamped box filter.
+//  * msssimf_grad_kernel: grad_body with k_s read from device memory (kKCoef), in a cs form (kMsUp), whose epilogue adds the coarser
+//    scale's gradient through the adjoint of the clamped box filter, and an ssim form (kMsLast).
 //
-// Centring, at every scale as in ssimf_kernels.hip ON THAT SCALE'S PLANES: the centre of the 128 columns from x0 = 128 k on is A's and
-// B's sample of scale s at (min(x0 + 64, W_s - 1), (H_s - 1) / 2) when its magnitude is at most dataRange, else 0.  The position is
-// fixed by the image and the pyramid is a fixed function of the image, so every strip height, tile, batch, split and entry point
-// sees the same centre.
-//
-// Per-pixel values and cells are formed exactly as in ssimf_kernels.hip (source-row order, fixed trees), so the sums are bit-identical
-// for any strip height, batch or split.
-#include "msssimf_kernels.h"
-#include <algorithm>
-#include <cmath>
-#include <type_traits>
+// Centring, per-pixel values and cells: see the top of ssim2_walk.h; the rules hold at every scale on that scale's planes.
+#include "ssim2_walk.h"
 
 namespace ssim_hip {
 namespace {
 
-typedef float  f2 __attribute__((ext_vector_type(2)));
-typedef float  f4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-typedef const uint8_t __attribute__((address_space(1)))*    gptr_u8;
-typedef const float __attribute__((address_space(1)))*      gptr_cf32;
-typedef float __attribute__((address_space(1)))*            gptr_f32;
-typedef double __attribute__((address_space(1)))*           gptr_f64;
-typedef const PairFDesc __attribute__((address_space(1)))* gptr_descf;
-
-__device__ __forceinline__ f2 fma_(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ float opaque(float v) { asm("" : "+v"(v)); return v; }
-
-__device__ __forceinline__ int64_t uniform64(int64_t v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// Row pass of the lane's two columns, centre tap first, the two dependent chains interleaved.
-__device__ __forceinline__ void rows_pair(f2& hA, f2& hB, const f2 (&a)[6], const f2 (&b)[6], const float (&g)[6])
-{
-    hA = a[0] * f2{g[0], g[0]};
-    hB = b[0] * f2{g[0], g[0]};
-#pragma unroll
-    for (int k = 1; k < 6; ++k) {
-        hA = fma_(a[k], f2{g[k], g[k]}, hA);
-        hB = fma_(b[k], f2{g[k], g[k]}, hB);
-    }
-}
-// Column pass: the ring scatter.  acc[k] is the running sum of output row (r - 5 + k) while source row r is processed.
-// KMIN (warm-up rows only): ring entries below KMIN stand for rows above the strip and are never read.
-template <int KMIN = 0>
-__device__ __forceinline__ void columns_pair(f2 (&accA)[11], f2 (&accB)[11], f2 hA, f2 hB, const float (&g)[6])
-{
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        const int t = k < 5 ? 5 - k : k - 5;
-        if (k >= KMIN) {
-            accA[k] = fma_(hA, f2{g[t], g[t]}, accA[k + 1]);
-            accB[k] = fma_(hB, f2{g[t], g[t]}, accB[k + 1]);
-        }
-    }
-    accA[10] = hA * f2{g[5], g[5]};
-    accB[10] = hB * f2{g[5], g[5]};
-}
-template <int KMIN = 0>
-__device__ __forceinline__ void blur_pair(f2 (&accA)[11], f2 (&accB)[11], const f2 (&a)[6], const f2 (&b)[6], const float (&g)[6])
-{
-    f2 hA, hB;
-    rows_pair(hA, hB, a, b, g);
-    columns_pair<KMIN>(accA, accB, hA, hB, g);
-}
-
-// cs and SSIM of the lane's two columns from the centred moments (ssim_px2 of ssimf_kernels.hip, plus cs = A2 * rcp(B2)): m0, m1 =
-// (mu_a', mu_b') of each column, e0, e1 = (E[a'^2 + b'^2], E[a'b']); cen = (cA, cB).
-__device__ __forceinline__ f2 msssim_px2(f2 m0, f2 m1, f2 e0, f2 e1, f2 cen, float c1, float c2, f2& cs)
-{
-    const f2 q0 = m0 * m0, q1 = m1 * m1;
-    const f2 pc = {opaque(m0.x * m0.y), opaque(m1.x * m1.y)};
-    const f2 tc = {opaque(q0.x + q0.y), opaque(q1.x + q1.y)};
-    const f2 sS = {opaque(e0.x - tc.x), opaque(e1.x - tc.y)};
-    const f2 sAB = {opaque(e0.y - pc.x), opaque(e1.y - pc.y)};
-    const f2 u0 = m0 + cen, u1 = m1 + cen;
-    const f2 v0 = u0 * u0, v1 = u1 * u1;
-    const f2 muAB = {opaque(u0.x * u0.y), opaque(u1.x * u1.y)};
-    const f2 tm = {opaque(v0.x + v0.y), opaque(v1.x + v1.y)};
-    const f2 two = {2.0f, 2.0f}, C1 = {c1, c1}, C2 = {c2, c2};
-    const f2 A2 = fma_(two, sAB, C2), B2 = sS + C2;
-    const f2 n = fma_(two, muAB, C1) * A2;
-    const f2 den = (tm + C1) * B2;
-    const f2 r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-    const f2 r2 = {__builtin_amdgcn_rcpf(B2.x), __builtin_amdgcn_rcpf(B2.y)};
-    cs = A2 * r2;
-    return n * r;
-}
-
-// One scale of one launch: that scale's descriptors, size and cell partials.
-struct KMArgs {
-    const PairFDesc* descs;
-    uint32_t width, height, strip_rows, strips_x, strips_y;
-    uint32_t cells_x, cells_y, cell_shift;
-    uint32_t count, xcds;
-    double*  partials;            // [image][cell_y][cell_x]{cs, ssim}
-    float    c1, c2, range;
-    float    gf[6];
-};
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// Workgroup g of `total` -> its place in the strip list when each XCD is to walk one contiguous share of it (neighbouring strips
-// share halo cache lines; consecutive workgroup ids go to the XCDs round robin).  A bijection for any total.
-__device__ __forceinline__ uint32_t xcd_order(uint32_t g, uint32_t total, uint32_t xcds)
-{
-    uint32_t xcd, slot, q, rem;
-    if (xcds == 8) { xcd = g & 7u; slot = g >> 3; q = total >> 3; rem = total & 7u; }
-    else           { slot = g / xcds; xcd = g - slot * xcds; q = total / xcds; rem = total - q * xcds; }
-    return xcd * q + (xcd < rem ? xcd : rem) + slot;
-}
-
-// Cells are reduced eight at a time (ssim_kernels.hip has the long form): each lane parks its leaf of a cell in LDS, and a
-// batch of eight cells is summed as fixed trees -- eight leaves per lane as ((x0+x1)+(x2+x3))+((x4+x5)+(x6+x7)), then two DPP
-// levels over the four lanes of a 32-leaf tree.
-enum { CELL_BATCH = 8 };
-struct CellBatch { double leaf[CELL_BATCH][64]; };
-
-#define MSF_DPP_ADD(t, CTRL) do {                                                                             \
-        const int lo_ = __builtin_amdgcn_update_dpp(0, __double2loint(t), (CTRL), 0xF, 0xF, false);           \
-        const int hi_ = __builtin_amdgcn_update_dpp(0, __double2hiint(t), (CTRL), 0xF, 0xF, false);           \
-        (t) += __hiloint2double(hi_, lo_);                                                                    \
-    } while (0)
-enum { DPP_QUAD_XOR1 = 0xB1, DPP_QUAD_XOR2 = 0x4E };
-
-__device__ __forceinline__ double cell_batch_local(const CellBatch& cb, int lane)
-{
-    const d2* p = reinterpret_cast<const d2*>(&cb.leaf[0][0]) + 4 * lane;
-    d2 v = p[0];
-    double a = v.x + v.y;
-    __builtin_amdgcn_sched_barrier(0);
-    v = p[1];
-    a = a + (v.x + v.y);
-    __builtin_amdgcn_sched_barrier(0);
-    v = p[2];
-    double b = v.x + v.y;
-    __builtin_amdgcn_sched_barrier(0);
-    v = p[3];
-    b = b + (v.x + v.y);
-    return a + b;
-}
-
-// A leaf is the lane's column pair; leaves 0-31 of a batch row are cell 2 sx, leaves 32-63 cell 2 sx + 1.  which: 0 the cs sum, 1 the
-// ssim sum of the cell (adjacent doubles).
-__device__ __forceinline__ void cell_batch_flush(const KMArgs& args, uint32_t img, uint32_t sx, const CellBatch& cb, uint32_t cell_y_first, uint32_t n, uint32_t which)
-{
-    int lane = threadIdx.x;
-    asm volatile("" : "+v"(lane));
-    double t = cell_batch_local(cb, lane);
-    MSF_DPP_ADD(t, DPP_QUAD_XOR1);
-    MSF_DPP_ADD(t, DPP_QUAD_XOR2);
-    const uint32_t c = (uint32_t)lane >> 3, cx = 2u * sx + (((uint32_t)lane >> 2) & 1u);
-    if ((lane & 3) == 0 && c < n && cx < args.cells_x)
-        ((gptr_f64)args.partials)[(((size_t)img * args.cells_y + cell_y_first + c) * args.cells_x + cx) * 2 + which] = t;
-}
-
-// LDS slot = one source row of 144 pixels starting seven columns left of the strip: a lane's twelve window pixels (columns x-5 ..
-// x+6 of its first column x) start on an even slot pixel and are six aligned 16-byte reads per plane.
-struct Slot {
-    static constexpr int STRIP_W = kSFStripW, PAD = 7, ROW_PX = 144;
-    f2 ab[ROW_PX];   // (a', b')
-    f2 q[ROW_PX];    // (a'^2 + b'^2, a'b')
-};
-
-enum { ROW_WARMUP = 0, ROW_MAIN = 1, ROW_LAST = 2 };
-
 // WIDE: 64-bit lane offsets for the samples (scale-0 pairs that fail fitsf_narrow()).
 template <bool WIDE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
-void msssimf_strip_kernel(const KMArgs args)
-{
-    constexpr int PAD = Slot::PAD, ROW_PX = Slot::ROW_PX;
-    constexpr int NLOAD = 3;                         // samples each lane stages per row and image
-    typedef typename std::conditional<WIDE, int64_t, uint32_t>::type Off;
-
-    __shared__ __attribute__((aligned(16))) Slot ring[2];
-    __shared__ __attribute__((aligned(16))) CellBatch cells[2];      // cs, ssim
-
-    const int lane = threadIdx.x;
-    const float gf[6] = {args.gf[0], args.gf[1], args.gf[2], args.gf[3], args.gf[4], args.gf[5]};
-
-    // the strip: image-major, then strip row, then strip column, each XCD walking a contiguous share of that list
-    const uint32_t per_img = args.strips_x * args.strips_y;
-    const uint32_t id = xcd_order(blockIdx.x, per_img * args.count, args.xcds);
-    const uint32_t img = id / per_img, lin = id - img * per_img;
-    const uint32_t sy = lin / args.strips_x, sx = lin - sy * args.strips_x;
-    PairFDesc pd;
-    {
-        const gptr_descf gd = (gptr_descf)args.descs + img;
-        pd.a = (const float*)uniform64((int64_t)gd->a); pd.a_step = uniform64(gd->a_step); pd.a_stride = uniform64(gd->a_stride);
-        pd.b = (const float*)uniform64((int64_t)gd->b); pd.b_step = uniform64(gd->b_step); pd.b_stride = uniform64(gd->b_stride);
-    }
-    const int W = (int)args.width, H = (int)args.height;
-    const int x0 = (int)(sx * Slot::STRIP_W), y0 = (int)(sy * args.strip_rows);
-    const int y_end = y0 + (int)args.strip_rows < H ? y0 + (int)args.strip_rows : H;
-
-    // the strip column's centre (see the top of the file), per image
-    f2 cen;
-    {
-        const int64_t cx = x0 + 64 < W ? x0 + 64 : W - 1, cy = (H - 1) / 2;
-        const float sa = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, ((gptr_cf32)pd.a)[cx * pd.a_step + cy * pd.a_stride])));
-        const float sb = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, ((gptr_cf32)pd.b)[cx * pd.b_step + cy * pd.b_stride])));
-        cen = f2{__builtin_fabsf(sa) <= args.range ? sa : 0.0f, __builtin_fabsf(sb) <= args.range ? sb : 0.0f};
-    }
-
-    // Per-lane staging columns: pixel p of the slot is image column clamp(x0 - PAD + p).  Addresses: a wave-uniform row base plus
-    // a non-negative lane offset in bytes from the strip's lowest-addressed column.
-    auto clampx = [&](int x) { return x < 0 ? 0 : (x > W - 1 ? W - 1 : x); };
-    const int x_lo = clampx(x0 - PAD), x_hi = clampx(x0 - PAD + ROW_PX - 1);
-    const int refA = pd.a_step >= 0 ? x_lo : x_hi, refB = pd.b_step >= 0 ? x_lo : x_hi;
-    const gptr_u8 baseA = (gptr_u8)(pd.a + (int64_t)refA * pd.a_step);
-    const gptr_u8 baseB = (gptr_u8)(pd.b + (int64_t)refB * pd.b_step);
-    int sp[NLOAD];
-    Off offA[NLOAD], offB[NLOAD];
-#pragma unroll
-    for (int t = 0; t < NLOAD; ++t) {
-        int p = lane + 64 * t;
-        p = p < ROW_PX ? p : ROW_PX - 1;
-        const int xg = clampx(x0 - PAD + p);
-        sp[t] = p;
-        offA[t] = (Off)((int64_t)(xg - refA) * pd.a_step * 4);
-        offB[t] = (Off)((int64_t)(xg - refB) * pd.b_step * 4);
-    }
-
-    float va[NLOAD], vb[NLOAD];
-    auto fetch_to = [&](int r, float (&oa)[NLOAD], float (&ob)[NLOAD]) {     // row r (clamped) -> registers
-        const int ry = r < 0 ? 0 : (r > H - 1 ? H - 1 : r);
-        const gptr_u8 ra = baseA + (int64_t)ry * pd.a_stride * 4;
-        const gptr_u8 rb = baseB + (int64_t)ry * pd.b_stride * 4;
-#pragma unroll
-        for (int t = 0; t < NLOAD; ++t) {
-            if constexpr (!WIDE) asm volatile("" : "+v"(offA[t]), "+v"(offB[t]));   // keeps the zero-extension foldable into the load
-            oa[t] = *(gptr_cf32)(ra + offA[t]);
-            ob[t] = *(gptr_cf32)(rb + offB[t]);
-        }
-    };
-    auto fetch = [&](int r) { fetch_to(r, va, vb); };
-    auto stage_from = [&](Slot& s, const float (&ia)[NLOAD], const float (&ib)[NLOAD]) {   // registers -> the two planes of a slot
-#pragma unroll
-        for (int t = 0; t < NLOAD; ++t) {
-            const f2 ab = f2{ia[t], ib[t]} - cen;         // (a', b')
-            const float a = ab.x, b = ab.y;
-            const int p = sp[t];
-            s.ab[p] = ab;
-            s.q[p] = f2{__builtin_fmaf(b, b, a * a), a * b};
-        }
-    };
-    auto stage = [&](Slot& s) { stage_from(s, va, vb); };
-
-    f2 accAB[2][11], accQ[2][11];
-#pragma unroll
-    for (int k = 0; k < 11; ++k) accAB[0][k] = accAB[1][k] = accQ[0][k] = accQ[1][k] = f2{0.0f, 0.0f};
-    double colsum[2] = {0.0, 0.0}, colcs[2] = {0.0, 0.0};
-
-    const int r_begin = y0 - 5;
-    {
-        float a0[NLOAD], b0[NLOAD], a1[NLOAD], b1[NLOAD];
-        fetch_to(r_begin, a0, b0);
-        fetch_to(r_begin + 1, a1, b1);
-        fetch(r_begin + 2);
-        stage_from(ring[0], a0, b0);
-        stage_from(ring[1], a1, b1);
-    }
-    wave_sync();
-
-    const bool col_ok[2] = {x0 + 2 * lane < W, x0 + 2 * lane + 1 < W};
-
-    f2 wab[12], wq[12];
-    const int e = 2 * lane + PAD - 5;                     // even: the 16-byte reads are aligned
-    auto load_ab = [&](const Slot& s) {
-#pragma unroll
-        for (int t = 0; t < 6; ++t) {
-            const f4 v = *reinterpret_cast<const f4*>(&s.ab[e + 2 * t]);
-            wab[2 * t] = v.xy; wab[2 * t + 1] = v.zw;
-        }
-    };
-    // The (a', b') row pass of the row about to be blurred: computed at the end of the previous iteration and carried over.
-    f2 hab[2];
-    auto fold_ab = [&]() {
-        f2 s[2][6];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int m = 5 + c;
-            s[c][0] = wab[m];
-#pragma unroll
-            for (int i = 1; i <= 5; ++i) s[c][i] = wab[m + i] + wab[m - i];
-        }
-        rows_pair(hab[0], hab[1], s[0], s[1], gf);
-    };
-    load_ab(ring[0]);
-    fold_ab();
-
-    auto row = [&](const int r, auto slot, auto phase_tag, auto kmin_tag) {
-        constexpr int cur = decltype(slot)::value;
-        constexpr int phase = decltype(phase_tag)::value;
-        constexpr int KMIN = decltype(kmin_tag)::value;
-        const Slot& s = ring[cur];
-        __builtin_amdgcn_s_setprio(2);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < 6; ++t) {
-            const f4 u = *reinterpret_cast<const f4*>(&s.q[e + 2 * t]);
-            wq[2 * t] = u.xy;  wq[2 * t + 1] = u.zw;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        columns_pair<KMIN>(accAB[0], accAB[1], hab[0], hab[1], gf);
-        __builtin_amdgcn_sched_barrier(0);
-        {
-            const f2 s0[6] = {wq[5], wq[6] + wq[4], wq[7] + wq[3], wq[8] + wq[2], wq[9] + wq[1], wq[10] + wq[0]};
-            const f2 s1[6] = {wq[6], wq[7] + wq[5], wq[8] + wq[4], wq[9] + wq[3], wq[10] + wq[2], wq[11] + wq[1]};
-            blur_pair<KMIN>(accQ[0], accQ[1], s0, s1, gf);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // ring entry 0 is now the finished output row r - 5
-        if constexpr (phase != ROW_WARMUP) {
-            f2 cs;
-            const f2 v = msssim_px2(accAB[0][0], accAB[1][0], accQ[0][0], accQ[1][0], cen, args.c1, args.c2, cs);
-            colsum[0] += (double)v.x;
-            colsum[1] += (double)v.y;
-            colcs[0] += (double)cs.x;
-            colcs[1] += (double)cs.y;
-        }
-        __builtin_amdgcn_s_setprio(0);
-        if constexpr (phase != ROW_LAST) {
-            __builtin_amdgcn_sched_barrier(0);
-            load_ab(ring[cur ^ 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            wave_sync();
-            stage(ring[cur]);                             // row r+2 replaces row r
-            fetch(r + 3);
-            wave_sync();
-            __builtin_amdgcn_sched_barrier(0);
-            fold_ab();                                    // row r+1
-        }
-    };
-    typedef std::integral_constant<int, 0> S0;
-    typedef std::integral_constant<int, 1> S1;
-    typedef std::integral_constant<int, ROW_WARMUP> Warm;
-    typedef std::integral_constant<int, 0> K0;
-    int r = r_begin;
-    // the ten warm-up rows in pairs (the two LDS slots); warm-up row i only feeds ring entries k >= 10 - i
-    row(r, S0(), Warm(), std::integral_constant<int, 9>());     row(r + 1, S1(), Warm(), std::integral_constant<int, 9>());
-    row(r + 2, S0(), Warm(), std::integral_constant<int, 7>()); row(r + 3, S1(), Warm(), std::integral_constant<int, 7>());
-    row(r + 4, S0(), Warm(), std::integral_constant<int, 5>()); row(r + 5, S1(), Warm(), std::integral_constant<int, 5>());
-    r += 6;
-#pragma unroll 1
-    for (int i = 0; i < 2; ++i, r += 2) {
-        row(r, S0(), Warm(), K0());
-        row(r + 1, S1(), Warm(), K0());
-    }
-    // main rows, one reduction cell at a time; only the image's last cell can be shorter (or odd)
-    const int cell_rows = 1 << args.cell_shift;
-    uint32_t cell_y = (uint32_t)y0 >> args.cell_shift, parked = 0;
-#pragma unroll 1
-    for (int left = y_end - y0; left > 0; left -= cell_rows) {
-        const int rows = left < cell_rows ? left : cell_rows;
-#pragma unroll 1
-        for (int i = rows >> 1; i > 0; --i, r += 2) {
-            row(r, S0(), std::integral_constant<int, ROW_MAIN>(), K0());
-            row(r + 1, S1(), std::integral_constant<int, ROW_MAIN>(), K0());
-        }
-        if (rows & 1)
-            row(r, S0(), std::integral_constant<int, ROW_LAST>(), K0());
-        cells[0].leaf[parked][lane] = (col_ok[0] ? colcs[0] : 0.0) + (col_ok[1] ? colcs[1] : 0.0);
-        cells[1].leaf[parked][lane] = (col_ok[0] ? colsum[0] : 0.0) + (col_ok[1] ? colsum[1] : 0.0);
-        colsum[0] = colsum[1] = colcs[0] = colcs[1] = 0.0;
-        if (++parked == CELL_BATCH) {
-            wave_sync();
-            cell_batch_flush(args, img, sx, cells[0], cell_y, parked, 0);
-            cell_batch_flush(args, img, sx, cells[1], cell_y, parked, 1);
-            wave_sync();
-            cell_y += parked;
-            parked = 0;
-        }
-    }
-    if (parked) {
-        wave_sync();
-        cell_batch_flush(args, img, sx, cells[0], cell_y, parked, 0);
-        cell_batch_flush(args, img, sx, cells[1], cell_y, parked, 1);
-    }
-}
+void msssimf_strip_kernel(const Strip2Args<PairFDesc> args) { strip_body<SampleF32, 5, kFormMulti, 0, WIDE>(args); }
 
 // ---- pyramid, reduction, product, coefficients ---------------------------------------------------------------------------------
 
@@ -520,244 +140,10 @@ __global__ __launch_bounds__(64) void msssimf_coef_kernel(const KWArgs args, con
     }
 }
 
-const uint64_t kMaxBlocks = (uint64_t(1) << 26) - 1;      // x 64 work-items stays below 2^32
-const uint64_t kMaxGradBlocks = (uint64_t(1) << 24) - 1;  // x 256 work-items stays below 2^32
-
-uint32_t cell_rows_of(uint32_t height) { return height >= 2048 ? 32u : 8u; }
-
-// ---- the gradient ------------------------------------------------------------------------------------------------------------
-// msssimf_grad_kernel: ssimf_grad_kernel (its steps 1 to 6 are described there and repeated in the comments below) with the
-// coefficient k_s read from device memory, a cs form for every scale but the coarsest, and the coarser scale's gradient added in
-// the epilogue.  One 256-lane workgroup = one 32 x 32 tile of gradient pixels of one scale at an absolute position; every gradient
-// pixel is written by one work-item in a fixed order: no atomics, the same bits in any batch.
-enum { GT = kSFTile, GIN = GT + 20, GST = GT + 10 };
-
-struct KGArgs {
-    const PairFDesc* descs;       // this scale's planes
-    const GradFDesc* grads;       // this scale's gradient planes
-    const GradFDesc* up;          // the next coarser scale's gradient planes (dense); unused by the LAST form
-    const float*     coef;        // k_s of pair i at coef[i * coef_stride]
-    uint32_t coef_stride;
-    uint32_t width, height, tiles_x, tiles_y;
-    float    c1, c2, range;
-    float    gf[6], tail[6], total;
-};
-
-// w(q, j) above for an axis of n pixels.
-__device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float (&g)[6], const float (&tail)[6], float total)
-{
-    const int aj = j < 0 ? -j : j;
-    float w = g[aj];
-    if (q == 0) w = j >= 0 ? tail[aj] : 0.0f;
-    if (q == n - 1) w = j <= 0 ? tail[aj] : 0.0f;
-    if (n == 1) w = j == 0 ? total : 0.0f;
-    return w;
-}
-
-// WHICH: 1 dLoss/dA, 2 dLoss/dB, 3 both.  The statistics are computed in the same (a, b) order in all three, so a gradient has
-// the same bits alone and together with the other.
-// LAST: the coarsest scale (the ssim form, no coarser gradient to add); otherwise the cs form, whose epilogue adds the adjoint of
-// the clamped 2 x 2 box filter applied to the next coarser scale's gradient: 0.25 c g_{s+1}(x >> 1, y >> 1).
+// LAST: the coarsest scale (the ssim form, no coarser gradient to add); otherwise the cs form.
 template <int WHICH, bool LAST>
 __global__ __launch_bounds__(256)
-void msssimf_grad_kernel(const KGArgs args)
-{
-    constexpr int NP = WHICH == 3 ? 4 : 3;                       // partial planes: d_mu (of A, or of the one wanted), d_aa, d_ab, d_mu of B
-    constexpr int XN = 2 * GIN * GIN > NP * GST * GST ? 2 * GIN * GIN : NP * GST * GST;
-    constexpr int YN = 4 * GIN * GST;                            // >= NP * GST * GT
-    __shared__ __attribute__((aligned(16))) float lds[XN + YN];
-    f2*    in  = reinterpret_cast<f2*>(lds);                     // [GIN][GIN] (a', b')
-    float* P   = lds;                                            // [NP][GST][GST], after the row pass has consumed `in`
-    f2*    Hab = reinterpret_cast<f2*>(lds + XN);                // [GIN][GST] row pass of (a', b')
-    f2*    Hq  = Hab + GIN * GST;                                // [GIN][GST] row pass of (a'^2 + b'^2, a'b')
-    float* Q   = lds + XN;                                       // [NP][GST][GT], after the column pass has consumed Hab, Hq
-
-    const int tid = threadIdx.x;
-    const int W = (int)args.width, H = (int)args.height;
-    const uint32_t per_img = args.tiles_x * args.tiles_y;
-    const uint32_t img = blockIdx.x / per_img, lin = blockIdx.x - img * per_img;
-    const uint32_t ty = lin / args.tiles_x, tx = lin - ty * args.tiles_x;
-    const int x0 = (int)(tx * GT), y0 = (int)(ty * GT);
-    const PairFDesc pd = args.descs[img];
-    const GradFDesc gd = args.grads[img];
-    const gptr_cf32 pa = (gptr_cf32)pd.a, pb = (gptr_cf32)pd.b;
-    const float gf[6] = {args.gf[0], args.gf[1], args.gf[2], args.gf[3], args.gf[4], args.gf[5]};
-    const float tail[6] = {args.tail[0], args.tail[1], args.tail[2], args.tail[3], args.tail[4], args.tail[5]};
-    const float k = ((gptr_cf32)args.coef)[(size_t)img * args.coef_stride];
-
-    // The coarser scale's gradient at this pixel, through the adjoint of the clamped box filter: the last column (row) of an odd
-    // width (height) was read twice by the clamp.  0.25 c is a power of two: the product is exact.
-    auto upstream = [&](const float* gup, int64_t ustep, int64_t ustride, int qx, int qy) -> float {
-        if constexpr (LAST) return 0.0f;
-        const float cx = ((W & 1) && qx == W - 1) ? 2.0f : 1.0f, cy = ((H & 1) && qy == H - 1) ? 2.0f : 1.0f;
-        return (0.25f * (cx * cy)) * ((gptr_cf32)gup)[(int64_t)(qx >> 1) * ustep + (int64_t)(qy >> 1) * ustride];
-    };
-    GradFDesc ud = {nullptr, 0, 0, nullptr, 0, 0};
-    if constexpr (!LAST) ud = args.up[img];
-
-    // k == 0 (a zero weight, gOut == 0, or MS == 0): this scale contributes +0 everywhere, whatever the samples are.
-    if (k == 0.0f) {
-        for (int idx = tid; idx < GT * GT; idx += 256) {
-            const int y = idx / GT, x = idx - y * GT;
-            const int qx = x0 + x, qy = y0 + y;
-            if (qx >= W || qy >= H) continue;
-            if constexpr (WHICH != 2)
-                ((gptr_f32)gd.ga)[(int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride] = 0.0f + upstream(ud.ga, ud.ga_step, ud.ga_stride, qx, qy);
-            if constexpr (WHICH != 1)
-                ((gptr_f32)gd.gb)[(int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride] = 0.0f + upstream(ud.gb, ud.gb_step, ud.gb_stride, qx, qy);
-        }
-        return;
-    }
-
-    f2 cen;                                                      // the strip column's centre (top of the file)
-    {
-        const int xs = x0 & ~(kSFStripW - 1);
-        const int64_t cx = xs + 64 < W ? xs + 64 : W - 1, cy = (H - 1) / 2;
-        const float sa = pa[cx * pd.a_step + cy * pd.a_stride], sb = pb[cx * pd.b_step + cy * pd.b_stride];
-        cen = f2{__builtin_fabsf(sa) <= args.range ? sa : 0.0f, __builtin_fabsf(sb) <= args.range ? sb : 0.0f};
-    }
-
-    // 1. samples
-    for (int idx = tid; idx < GIN * GIN; idx += 256) {
-        const int j = idx / GIN, i = idx - j * GIN;
-        int x = x0 - 10 + i, y = y0 - 10 + j;
-        x = x < 0 ? 0 : (x > W - 1 ? W - 1 : x);
-        y = y < 0 ? 0 : (y > H - 1 ? H - 1 : y);
-        const f2 v = {pa[(int64_t)x * pd.a_step + (int64_t)y * pd.a_stride], pb[(int64_t)x * pd.b_step + (int64_t)y * pd.b_stride]};
-        in[idx] = v - cen;
-    }
-    __syncthreads();
-
-    // 2. row pass: H*[j][u] is the blur along x at image column x0 - 5 + u of source row y0 - 10 + j
-    for (int idx = tid; idx < GIN * GST; idx += 256) {
-        const int j = idx / GST, u = idx - j * GST;
-        const f2* row = in + j * GIN + u;
-        f2 ab[11], q[11];
-#pragma unroll
-        for (int t = 0; t < 11; ++t) {
-            ab[t] = row[t];
-            q[t] = f2{__builtin_fmaf(ab[t].y, ab[t].y, ab[t].x * ab[t].x), ab[t].x * ab[t].y};
-        }
-        const f2 sab[6] = {ab[5], ab[6] + ab[4], ab[7] + ab[3], ab[8] + ab[2], ab[9] + ab[1], ab[10] + ab[0]};
-        const f2 sq[6] = {q[5], q[6] + q[4], q[7] + q[3], q[8] + q[2], q[9] + q[1], q[10] + q[0]};
-        f2 hab, hq;
-        rows_pair(hab, hq, sab, sq, gf);
-        Hab[idx] = hab;
-        Hq[idx] = hq;
-    }
-    __syncthreads();
-
-    // 3. column pass, SSIM terms, weighted partials
-    for (int idx = tid; idx < GST * GST; idx += 256) {
-        const int v = idx / GST, u = idx - v * GST;
-        const int px = x0 - 5 + u, py = y0 - 5 + v;
-        float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (px >= 0 && px < W && py >= 0 && py < H) {
-            const f2* cab = Hab + v * GST + u;
-            const f2* cq = Hq + v * GST + u;
-            f2 m = cab[0] * f2{gf[5], gf[5]}, e = cq[0] * f2{gf[5], gf[5]};
-#pragma unroll
-            for (int t = 1; t < 11; ++t) {
-                const float w = gf[t < 5 ? 5 - t : t - 5];
-                m = fma_(cab[t * GST], f2{w, w}, m);
-                e = fma_(cq[t * GST], f2{w, w}, e);
-            }
-            // the forward kernel's terms (ssim_px2), then the derivative
-            const float pc = opaque(m.x * m.y), tc = opaque(opaque(m.x * m.x) + opaque(m.y * m.y));
-            const float sS = opaque(e.x - tc), sAB = opaque(e.y - pc);
-            const float uA = m.x + cen.x, uB = m.y + cen.y;
-            const float muAB = opaque(uA * uB), tm = opaque(opaque(uA * uA) + opaque(uB * uB));
-            const float A2 = __builtin_fmaf(2.0f, sAB, args.c2), B2 = sS + args.c2;
-            const float r2 = __builtin_amdgcn_rcpf(B2);
-            float dab, daa, dmA, dmB;
-            if constexpr (LAST) {
-                const float A1 = __builtin_fmaf(2.0f, muAB, args.c1), B1 = tm + args.c1;
-                const float r1 = __builtin_amdgcn_rcpf(B1);
-                const float r12 = opaque(r1 * r2);
-                const float ssim = opaque(opaque(A1 * A2) * r12);
-                dab = opaque(opaque(2.0f * A1) * r12);
-                daa = -opaque(ssim * r2);
-                const float f1 = opaque(A2 * r12), f2_ = opaque(ssim * r1);
-                dmA = opaque(opaque(opaque(opaque(2.0f * uB) * f1) - opaque(opaque(2.0f * uA) * f2_)) - opaque(opaque(2.0f * m.x) * daa)) - opaque(m.y * dab);
-                dmB = opaque(opaque(opaque(opaque(2.0f * uA) * f1) - opaque(opaque(2.0f * uB) * f2_)) - opaque(opaque(2.0f * m.y) * daa)) - opaque(m.x * dab);
-            } else {
-                // cs = A2 / B2 alone: d_ab = 2 / B2, d_aa = -cs / B2, and d_mu in the centred variables has no luminance part
-                const float cs = opaque(A2 * r2);
-                dab = opaque(2.0f * r2);
-                daa = -opaque(cs * r2);
-                dmA = -opaque(opaque(2.0f * m.x) * daa) - opaque(m.y * dab);
-                dmB = -opaque(opaque(2.0f * m.y) * daa) - opaque(m.x * dab);
-            }
-            d[0] = k * (WHICH == 2 ? dmB : dmA);
-            d[1] = k * daa;
-            d[2] = k * dab;
-            d[3] = k * dmB;
-        }
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) P[pl * GST * GST + idx] = d[pl];      // `in` is dead: every lane is past the barrier above
-    }
-    __syncthreads();
-
-    // 4. adjoint row pass: Q[pl][v][x], x = tid % 32 for every position of this lane
-    {
-        const int x = tid & (GT - 1), qx = x0 + x;
-        float wx[11];
-#pragma unroll
-        for (int j = -5; j <= 5; ++j) wx[j + 5] = adjoint_weight(qx, W, j, gf, tail, args.total);
-        for (int idx = tid; idx < GST * GT; idx += 256) {
-            const int v = idx / GT;
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-                const float* src = P + pl * GST * GST + v * GST + x;
-                float acc = src[0] * wx[0];
-#pragma unroll
-                for (int t = 1; t < 11; ++t) acc = __builtin_fmaf(src[t], wx[t], acc);
-                Q[pl * GST * GT + idx] = acc;
-            }
-        }
-    }
-    __syncthreads();
-
-    // 5. adjoint column pass, 6. the gradient
-    for (int idx = tid; idx < GT * GT; idx += 256) {
-        const int y = idx / GT, x = idx - y * GT;
-        const int qx = x0 + x, qy = y0 + y;
-        if (qx >= W || qy >= H) continue;
-        float wy[11];
-#pragma unroll
-        for (int j = -5; j <= 5; ++j) wy[j + 5] = adjoint_weight(qy, H, j, gf, tail, args.total);
-        float r[NP];
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) {
-            const float* src = Q + pl * GST * GT + y * GT + x;
-            float acc = src[0] * wy[0];
-#pragma unroll
-            for (int t = 1; t < 11; ++t) acc = __builtin_fmaf(src[t * GT], wy[t], acc);
-            r[pl] = acc;
-        }
-        const float a = pa[(int64_t)qx * pd.a_step + (int64_t)qy * pd.a_stride] - cen.x;
-        const float b = pb[(int64_t)qx * pd.b_step + (int64_t)qy * pd.b_stride] - cen.y;
-        if constexpr (WHICH != 2) {
-            const float g = opaque(r[0] + opaque(opaque(2.0f * a) * r[1])) + opaque(b * r[2]);
-            ((gptr_f32)gd.ga)[(int64_t)qx * gd.ga_step + (int64_t)qy * gd.ga_stride] = LAST ? g : opaque(g) + upstream(ud.ga, ud.ga_step, ud.ga_stride, qx, qy);
-        }
-        if constexpr (WHICH != 1) {
-            const float g = opaque(r[WHICH == 3 ? 3 : 0] + opaque(opaque(2.0f * b) * r[1])) + opaque(a * r[2]);
-            ((gptr_f32)gd.gb)[(int64_t)qx * gd.gb_step + (int64_t)qy * gd.gb_stride] = LAST ? g : opaque(g) + upstream(ud.gb, ud.gb_step, ud.gb_stride, qx, qy);
-        }
-    }
-}
-
-// the true 1-D Gaussian, sigma 1.5, normalised over the 11 taps, rounded to float: the engine's taps, centre first
-void gaussian_taps(float (&gf)[6])
-{
-    double g[6], norm = 0.0;
-    for (int i = 0; i <= 5; ++i) {
-        g[i] = exp(-(double)(i * i) / (2.0 * 1.5 * 1.5));
-        norm += (i == 0) ? g[i] : 2.0 * g[i];
-    }
-    for (int i = 0; i <= 5; ++i) gf[i] = (float)(g[i] / norm);
-}
+void msssimf_grad_kernel(const Grad2Args<PairFDesc, GradFDesc> args) { grad_body<SampleF32, 5, WHICH, kKCoef, LAST ? kMsLast : kMsUp>(args); }
 
 bool valid_call(uint32_t count, uint32_t width, uint32_t height, uint32_t scales, float data_range, const double* weights)
 {
@@ -794,24 +180,8 @@ hipError_t launch_pyramid(uint32_t first, const PairFDesc* descs_dev, uint32_t c
 
 } // namespace
 
-// Strip height of one scale's launch (whole cells, at most 2048 rows): the one that finishes the launch's strips in the fewest
-// row-times at three waves per SIMD, 10 warm-up rows included -- planf() of ssimf_kernels.hip.  Results do not depend on it.
-uint32_t strip_rows_of(uint32_t width, uint32_t height, uint32_t count, int cu_count)
-{
-    const uint32_t cell_rows = cell_rows_of(height);
-    const uint64_t slots = (uint64_t)(cu_count > 0 ? cu_count : 256) * 4 * 3;
-    const uint64_t cols = (uint64_t)((width + kSFStripW - 1) / kSFStripW) * count;
-    uint64_t best = ~uint64_t(0);
-    uint32_t best_rows = cell_rows;
-    for (uint32_t rows = cell_rows; rows <= std::max<uint32_t>(cell_rows, 2048); rows += cell_rows) {
-        const uint64_t per_col = (height + rows - 1) / rows;
-        const uint64_t rounds = (cols * per_col + slots - 1) / slots;
-        const uint64_t cost = rounds * (std::min<uint64_t>(rows, height) + 10);
-        if (cost <= best) { best = cost; best_rows = rows; }
-        if (rows >= height) break;
-    }
-    return best_rows;
-}
+// Strip height of one scale's launch: planf()'s.  Results do not depend on it.
+uint32_t strip_rows_of(uint32_t width, uint32_t height, uint32_t count, int cu_count) { return planf(width, height, count, cu_count).strip_rows; }
 
 uint64_t msf_cells(uint32_t W, uint32_t H, uint32_t s)
 {
@@ -821,12 +191,8 @@ uint64_t msf_cells(uint32_t W, uint32_t H, uint32_t s)
 
 uint32_t msssimf_max_count(uint32_t width, uint32_t height)
 {
-    if (width == 0 || height == 0 || width > kSFMaxDim || height > kSFMaxDim) return 0;
     // scale 0 has the largest grids: strips of the smallest height, gradient tiles; a pyramid step has a quarter of the tiles' lanes
-    const uint64_t cr = cell_rows_of(height);
-    const uint64_t per = (uint64_t)((width + kSFStripW - 1) / kSFStripW) * ((height + cr - 1) / cr);
-    const uint64_t tiles = (uint64_t)((width + kSFTile - 1) / kSFTile) * ((height + kSFTile - 1) / kSFTile);
-    return (uint32_t)std::min<uint64_t>(std::min(kMaxBlocks / per, kMaxGradBlocks / tiles), 65535);
+    return ssimf_max_count(width, height);
 }
 
 hipError_t launch_msssimf(const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales, bool wide,
@@ -848,29 +214,15 @@ hipError_t launch_msssimf_from(uint32_t first, const PairFDesc* descs_dev, uint3
     kr.partials = partials; kr.means = means; kr.count = count; kr.scales = scales;
     uint64_t offset = 0;
     for (uint32_t s = 0; s < kMSFMaxScales; ++s) { kr.offset[s] = 0; kr.cells[s] = 0; kr.pixels[s] = 1.0; }
+    float taps[MAXR + 1];
+    default_taps(taps);
     for (uint32_t s = 0; s < scales; ++s) {
-        const uint32_t w = msf_dim(width, s), h = msf_dim(height, s);
-        KMArgs ka;
-        ka.descs = descs_dev + (size_t)s * count;
-        ka.width = w; ka.height = h;
-        ka.strip_rows = strip_rows_of(w, h, count, cu_count);
-        ka.strips_x = (w + kSFStripW - 1) / kSFStripW;
-        ka.strips_y = (h + ka.strip_rows - 1) / ka.strip_rows;
-        const uint32_t cr = cell_rows_of(h);
-        ka.cells_x = (w + 63) / 64; ka.cells_y = (h + cr - 1) / cr;
-        ka.cell_shift = cr == 32 ? 5 : 3;
-        ka.count = count;
-        ka.xcds = xcd_count >= 1 ? (uint32_t)xcd_count : 8u;
-        ka.partials = partials + offset;
-        ka.range = data_range;
-        ssimf_constants(data_range, ka.c1, ka.c2);
-        gaussian_taps(ka.gf);
-        kr.offset[s] = offset; kr.cells[s] = (uint64_t)ka.cells_x * ka.cells_y; kr.pixels[s] = (double)w * (double)h;
+        const GeometryF geo = planf(msf_dim(width, s), msf_dim(height, s), count, cu_count);
+        const Strip2Args<PairFDesc> ka = fill_strip(geo, descs_dev + (size_t)s * count, data_range, taps, xcd_count, partials + offset);
+        kr.offset[s] = offset; kr.cells[s] = geo.cells_per_image(); kr.pixels[s] = (double)geo.width * (double)geo.height;
         offset += kr.cells[s] * 2 * count;
         if (s < first) continue;                  // the caller's own strip kernel fills this scale's partials
-        const dim3 grid((uint32_t)((uint64_t)ka.strips_x * ka.strips_y * count)), block(64);
-        if (wide && s == 0) hipLaunchKernelGGL((msssimf_strip_kernel<true>), grid, block, 0, stream, ka);
-        else                hipLaunchKernelGGL((msssimf_strip_kernel<false>), grid, block, 0, stream, ka);
+        pick_bool(wide && s == 0, [&](auto w) { hipLaunchKernelGGL((msssimf_strip_kernel<decltype(w)::value>), strip_grid(geo), dim3(64), 0, stream, ka); });
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -898,33 +250,19 @@ hipError_t launch_msssimf_grad_from(uint32_t first, const PairFDesc* descs_dev, 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if ((e = launch_pyramid(first, descs_dev, count, width, height, scales, stream)) != hipSuccess) return e;
-    KGArgs ka;
-    ka.range = data_range;
-    ssimf_constants(data_range, ka.c1, ka.c2);
-    gaussian_taps(ka.gf);
-    // tail[d] = g_d + ... + g_5 and the sum of all eleven taps: sums of the float taps in double, rounded once
-    double t = 0.0;
-    for (int i = 5; i >= 0; --i) { t += (double)ka.gf[i]; ka.tail[i] = (float)t; }
-    ka.total = (float)(2.0 * t - (double)ka.gf[0]);
-    ka.coef_stride = scales;
+    float taps[MAXR + 1];
+    default_taps(taps);
     for (uint32_t s = scales; s-- > first;) {
         const bool last = s + 1 == scales;
-        ka.descs = descs_dev + (size_t)s * count;
-        ka.grads = grads_dev + (size_t)s * count;
+        Grad2Args<PairFDesc, GradFDesc> ka = fill_grad(msf_dim(width, s), msf_dim(height, s), descs_dev + (size_t)s * count, grads_dev + (size_t)s * count,
+                                                       data_range, 5, taps);
         ka.up = last ? nullptr : grads_dev + (size_t)(s + 1) * count;
-        ka.coef = coef + s;
-        ka.width = msf_dim(width, s); ka.height = msf_dim(height, s);
-        ka.tiles_x = (ka.width + kSFTile - 1) / kSFTile; ka.tiles_y = (ka.height + kSFTile - 1) / kSFTile;
-        const dim3 grid((uint32_t)((uint64_t)ka.tiles_x * ka.tiles_y * count)), block(256);
-        if (last) {
-            if (which == 1)      hipLaunchKernelGGL((msssimf_grad_kernel<1, true>), grid, block, 0, stream, ka);
-            else if (which == 2) hipLaunchKernelGGL((msssimf_grad_kernel<2, true>), grid, block, 0, stream, ka);
-            else                 hipLaunchKernelGGL((msssimf_grad_kernel<3, true>), grid, block, 0, stream, ka);
-        } else {
-            if (which == 1)      hipLaunchKernelGGL((msssimf_grad_kernel<1, false>), grid, block, 0, stream, ka);
-            else if (which == 2) hipLaunchKernelGGL((msssimf_grad_kernel<2, false>), grid, block, 0, stream, ka);
-            else                 hipLaunchKernelGGL((msssimf_grad_kernel<3, false>), grid, block, 0, stream, ka);
-        }
+        ka.g_out = coef + s; ka.g_out_stride = scales;      // k_s of pair i at coef[i * scales + s]
+        pick_bool(last, [&](auto l) {
+            pick_which(which, [&](auto wh) {
+                hipLaunchKernelGGL((msssimf_grad_kernel<decltype(wh)::value, decltype(l)::value>), grad_grid(ka, count), dim3(256), 0, stream, ka);
+            });
+        });
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;

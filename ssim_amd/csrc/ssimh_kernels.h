@@ -4,8 +4,7 @@
 #ifndef SSIM_AMD_SSIMH_KERNELS_H
 #define SSIM_AMD_SSIMH_KERNELS_H
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "ssimf_kernels.h"      // GeometryF, kSFStripW, kSFTile, kSFMaxDim, ssimf_max_count
 
 namespace ssim_hip {
 
@@ -28,15 +27,10 @@ struct GradHDesc {
 };
 
 // Strips, cells and gradient tiles are those of ssimf_kernels.h: the sums and gradients have the bits of the float32 path.
-enum { kSHStripW = 128 };
-enum { kSHTile = 32 };
+enum { kSHStripW = kSFStripW };
+enum { kSHTile = kSFTile };
 
-struct GeometryH {
-    uint32_t width, height, count;
-    uint32_t strip_rows, strips_x, strips_y;
-    uint32_t cell_rows, cells_x, cells_y;
-    uint64_t cells_per_image() const { return (uint64_t)cells_x * cells_y; }
-};
+typedef GeometryF GeometryH;
 
 // The strip kernel addresses a strip's samples as (64-bit row base) + (32-bit lane offset in bytes); a pair whose steps are too
 // large for that runs on the form with 64-bit lane offsets.
@@ -49,10 +43,9 @@ inline bool fitsh_narrow(const PairHDesc& d)
 }
 
 // Largest width / height the kernels take (32-bit coordinates with room for the halo and the strip round-up).
-enum : uint32_t { kSHMaxDim = 0x7FFF0000u };
+enum : uint32_t { kSHMaxDim = kSFMaxDim };
 
-// Most pairs of this size one launch may take (its grid stays below 2^32 work-items, forward and gradient); 0 when one pair is
-// already too large.
+// Most pairs of this size one launch may take: ssimf_max_count (the grids are the same).
 uint32_t ssimh_max_count(uint32_t width, uint32_t height);
 
 // The strips of `count` pairs, chosen as ssimf_kernels.h's planf chooses them.  Results do not depend on the strip height.

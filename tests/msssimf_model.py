@@ -10,7 +10,7 @@ clamped box filter.  Plain numpy, no reference to the GPU code.
 Model(a, b, R) caches what does not depend on the number of scales or the weights (pyramid, per-scale maps, the unit local gradients
 Gt(d_mu) + 2 a Gt(d_aa) + b Gt(d_ab) of both forms: the local gradient is linear in k_s), so that a test can walk scales 1 .. 8 cheaply.
 
-Emulation(a, b, R) restates the KERNELS' arithmetic (msssimf_kernels.hip): the fp32 pyramid in its defined order, the centre of every
+Emulation(a, b, R) restates the KERNELS' arithmetic (msssimf_kernels.hip; the strip and gradient bodies are ssim2_walk.h's multi-scale forms): the fp32 pyramid in its defined order, the centre of every
 128-column strip column of EVERY scale taken from that scale's plane, the fp32 statistics and gradient of ssimf_model.emulate_fp32
 with the cs form added, k_s rounded to float once, and g_s = fp32(local_s + fp32(0.25 c g_{s+1})).  What the GPU should produce up to
 the order of the fp64 sums, the 1-ulp reciprocal, fma contraction and the device's pow.
@@ -200,7 +200,7 @@ def grad(a, b, data_range, g_out, scales=5, weights=None, c1=None, c2=None, g=No
     return Model(a, b, data_range, c1, c2, g).grad(g_out, scales, weights)
 
 
-# ---- fp32 emulation of msssimf_kernels.hip --------------------------------------------------------------------------------------------
+# ---- fp32 emulation of msssimf_kernels.hip (ssim2_walk.h) --------------------------------------------------------------------------------------------
 
 class _ScaleEmu(object):
     """One scale of one pair as the kernels compute it: the cs and ssim maps (float32), and per strip column the unscaled partials of

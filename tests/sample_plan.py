@@ -1,5 +1,6 @@
 """The strip planner of the five sample families, restated in plain Python: plan16 (ssim16_kernels.hip), planf (ssimf_kernels.hip), planh
-(ssimh_kernels.hip), plank (ssimk_kernels.hip) and strip_rows_of (msssimf_kernels.hip).  No GPU, no library call.
+(ssimh_kernels.hip), plank (ssimk_kernels.hip) and strip_rows_of (msssimf_kernels.hip); the last four are one-line calls of one planner,
+plan_strips of ssim2_walk.h, with the warm-up rows as a parameter.  No GPU, no library call.
 
 All five use one rule.  The reduction cells are 64 columns x cell_rows rows at absolute positions (32 rows for images of 2048 rows or
 more, else 8).  A strip is STRIP_W columns wide and a whole number of cells tall, at most 2048 rows; among those heights the planner takes

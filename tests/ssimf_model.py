@@ -117,7 +117,7 @@ def grad(a, b, data_range, g_out, c1=None, c2=None, g=None):
     return blur_t(k * d_mu_a, g) + 2.0 * a * t_aa + b * t_ab, blur_t(k * d_mu_b, g) + 2.0 * b * t_aa + a * t_ab
 
 
-# ---- fp32 emulation of ssimf_kernels.hip -------------------------------------------------------------------------------
+# ---- fp32 emulation of ssimf_kernels.hip (ssim2_walk.h) -------------------------------------------------------------------------------
 
 F = np.float32
 

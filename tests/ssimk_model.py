@@ -8,8 +8,8 @@ window's radius R = (size - 1) / 2 -- the clamped separable window G, the per-pi
 the exact derivative with Gt, the ADJOINT of the clamped window, built as defined: a scatter-add of w_t v(p) onto clamp(p + t).  At the
 default window (11, 1.5, "gaussian") every function returns exactly what ssimf_model / ssimw_model return.
 
-emulate_fp32() restates the KERNELS' arithmetic (ssimk_kernels.hip for R = 1 .. 4; ssimf_kernels.hip / ssimw_kernels.hip with the window's
-taps for R = 5): ssimf_model.emulate_fp32 and ssimw_model.emulate_fp32_map_grad with 5 replaced by R.
+emulate_fp32() restates the KERNELS' arithmetic (strip_body and grad_body of ssim2_walk.h: instantiated by ssimk_kernels.hip for R = 1 .. 4, by
+ssimf_kernels.hip / ssimw_kernels.hip with the window's taps for R = 5): ssimf_model.emulate_fp32 and ssimw_model.emulate_fp32_map_grad with 5 replaced by R.
 """
 import numpy as np
 

@@ -4,7 +4,7 @@ rmgr_ssim_hip_enqueue_ssimf_map_grad / _ssimh_map_grad), on top of tests/ssimf_m
 The yardstick of tests/test_ssimw_cpu.py and tests/test_gpu_ssimw.py: grad_map() is ssimf_model.grad() with the uniform k = gOut / (W H)
 replaced by the plane k(p) = gMap(p), INSIDE the adjoint Gt: the derivative of sum_p gMap(p) ssim(p).
 
-emulate_fp32_map_grad() restates the KERNEL's arithmetic (ssimw_kernels.hip): the gradient half of ssimf_model.emulate_fp32, statement for
+emulate_fp32_map_grad() restates the KERNEL's arithmetic (ssimw_kernels.hip: grad_body of ssim2_walk.h with the per-pixel k): the gradient half of ssimf_model.emulate_fp32, statement for
 statement, with the plane k.  With the constant plane float(gOut / (W H)) it reproduces emulate_fp32's gradients bit for bit.
 """
 import numpy as np
