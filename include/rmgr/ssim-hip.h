@@ -46,6 +46,8 @@
  *                                      counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_msssim3f, rmgr_ssim_hip_compute_msssim3f_device / _host, rmgr_ssim_hip_enqueue_msssim3f_grad   multi-scale
  *                                      SSIM of float32 VOLUMES and its gradient: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_msssim3h, rmgr_ssim_hip_compute_msssim3h_device / _host, rmgr_ssim_hip_enqueue_msssim3h_grad   multi-scale
+ *                                      SSIM of float16 / bfloat16 VOLUMES and its gradient: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -1115,8 +1117,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win_map_grad(rmgr_ssim_hip_Context* ct
  * Against pytorch-msssim's MS_SSIM(spatial_dims=3): that one uses a valid window and zero-padded pooling and refuses small sides; this
  * one clamps the window at the borders, pools with clamped coordinates and runs down to 1 x 1 x 1, so values are close, not equal.
  *
- * Follow-ups, not in this interface: float16 / bfloat16 volumes, a caller-chosen window for the multi-scale form, and a multi-scale map
- * gradient.
+ * float16 / bfloat16 volumes: the msssim3h entries below.  Follow-ups, not in this interface: a caller-chosen window for the multi-scale
+ * form, and a multi-scale map gradient.
  */
 rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                             float dataRange, rmgr_uint32_t scales, const double* weights, double* valuesDevice,
@@ -1131,6 +1133,57 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f_grad(rmgr_ssim_hip_Context* ctx, rmg
                                                  float dataRange, rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice,
                                                  const float* gradOutDevice, const rmgr_ssim_hip_Grad3F* gradA,
                                                  const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
+
+/*
+ * Multi-scale SSIM of `count` pairs of float16 or bfloat16 VOLUMES of one size, and its gradient (1 - MS-SSIM of volumes as a training
+ * loss under mixed precision, without a float32 copy of the volumes or of the gradient).  No reference counterpart: msssim3h is msssim3f
+ * applied to the samples widened to float32, so tests/msssim3f_model.py restates it as well; tests/halfmodel.py restates the two
+ * encodings.  Additions only: RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ *   Samples  as rmgr_ssim_hip_enqueue_ssim3h: 16-bit, ONE encoding per call (sampleType RMGR_SSIM_HIP_SAMPLE_F16 or _BF16), each widened
+ *            to float32 EXACTLY (float16 subnormals are kept; bfloat16 is the upper half of a float32; NaN and Inf stay NaN and Inf).
+ *            Only scale 0 holds 16-bit samples: the pyramid is float32 from scale 1 on.
+ *   Inputs   params[0 .. count-1] (rmgr_ssim_hip_Params3H): width, height, depth (the same for every pair), imgA / imgB with any step /
+ *            stride / sliceStride in SAMPLES, negative and interleaved views included, 64-bit offsets; params[i].ssimMap must be NULL.
+ *            Alignment: 2 bytes.
+ *   Data range, scales, weights, pyramid, per scale, value, arithmetic  as rmgr_ssim_hip_enqueue_msssim3f, word for word, on the widened
+ *            volumes.
+ *   Forward  the value and every per-scale mean {mcs_s, mssim_s} have the BITS rmgr_ssim_hip_enqueue_msssim3f gives on the widened
+ *            volumes, at every `scales` 1 .. 8 and with any weights.
+ *   Gradient  the float32 value rmgr_ssim_hip_enqueue_msssim3f_grad would store at scale 0 for the widened volumes -- fp32(local_0 +
+ *            fp32(0.125 c g_1)) when a coarser scale exists, local_0 when scales == 1 --, rounded ONCE, to nearest-even, into the inputs'
+ *            encoding.  float16 keeps subnormals and overflows to +-Inf; a NaN stays a (quiet) NaN.  gradOutDevice, the per-scale means,
+ *            the coefficients k_s, the pyramid, the gradient volumes of scales >= 1 and the coefficient volumes stay float32 / float64
+ *            as they are; a loss scale that arrives in gOut is applied before the single rounding: round(scale g), not scale round(g).
+ *            A volume whose k_0 is 0 (a zero weight, MS = 0 or gOut = 0) stores the rounded upstream share fp32(0.125 c g_1) at scale 0:
+ *            +0 when scales == 1.
+ *   Determinism  every promise of msssim3f: the same bits -- value, means, gradient -- alone or anywhere in a batch, at any z-chunk depth
+ *            of any scale, after any sub-batch split, through every entry point, with one gradient or both, and for any view against
+ *            the dense volume.  One writer per gradient voxel, no floating-point atomics.
+ *
+ * _enqueue_msssim3h, _compute_msssim3h_device, _compute_msssim3h_host: as the msssim3f entries of the same names (valuesDevice,
+ *            scaleMeansDevice, msssim, scaleMeans as there); the _host form stages 2 bytes per voxel.
+ * _enqueue_msssim3h_grad: as _enqueue_msssim3f_grad; gradA / gradB: arrays of count rmgr_ssim_hip_Grad3H as for _enqueue_ssim3h_grad
+ *            (16-bit device volumes in the inputs' encoding, step / stride / sliceStride in samples; either may be NULL, not both;
+ *            written, not accumulated).
+ * Scratch  msssim3f's, byte for byte: the pyramids, the coarse gradient volumes and the coefficient volumes are the same float32 volumes,
+ *            in the same sub-batches under about 1 GB.
+ * EINVAL, before any device is touched: every EINVAL of the msssim3f entries, with 2-byte alignment for samples and gradient volumes in
+ *         place of 4; a sampleType that is neither of the two constants.  ENODEV: no device.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                            rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                            double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3h_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                   rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                   float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3h_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                 rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                 float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                 rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
+                                                 const double* scaleMeansDevice, const float* gradOutDevice,
+                                                 const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

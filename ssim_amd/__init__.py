@@ -13,7 +13,7 @@ from .api import (  # noqa: F401
     ImgF, ParamsF, GradF, compute_ssimf, compute_ssimf_batch, make_params_f,
     Img3F, Params3F, Grad3F, GradOut3F, compute_ssim3f, compute_ssim3f_batch, make_params3f,
     Img3H, Params3H, Grad3H, compute_ssim3h, compute_ssim3h_batch, make_params3h,
-    compute_msssimf, compute_msssimf_batch, compute_msssimh, compute_msssimh_batch, compute_msssim3f, compute_msssim3f_batch,
+    compute_msssimf, compute_msssimf_batch, compute_msssimh, compute_msssimh_batch, compute_msssim3f, compute_msssim3f_batch, compute_msssim3h, compute_msssim3h_batch,
     Window, WINDOW_GAUSSIAN, WINDOW_UNIFORM, WINDOW_SIZES, make_window,
     GradH, GradOutF, SAMPLE_F16, SAMPLE_BF16, compute_ssimh, compute_ssimh_batch, sample_type_code,
 )

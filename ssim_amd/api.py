@@ -233,6 +233,7 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssim3h_win", "rmgr_ssim_hip_compute_ssim3h_win_device", "rmgr_ssim_hip_compute_ssim3h_win_host",
     "rmgr_ssim_hip_enqueue_ssim3h_win_grad", "rmgr_ssim_hip_enqueue_ssim3h_win_map_grad",
     "rmgr_ssim_hip_enqueue_msssim3f", "rmgr_ssim_hip_compute_msssim3f_device", "rmgr_ssim_hip_compute_msssim3f_host", "rmgr_ssim_hip_enqueue_msssim3f_grad",
+    "rmgr_ssim_hip_enqueue_msssim3h", "rmgr_ssim_hip_compute_msssim3h_device", "rmgr_ssim_hip_compute_msssim3h_host", "rmgr_ssim_hip_enqueue_msssim3h_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -353,6 +354,10 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_msssimf_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimf_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_enqueue_msssimf_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
+        "rmgr_ssim_hip_enqueue_msssim3h": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
+        "rmgr_ssim_hip_compute_msssim3h_device": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssim3h_host": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_msssim3h_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
         "rmgr_ssim_hip_enqueue_msssimh": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
         "rmgr_ssim_hip_compute_msssimh_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimh_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
@@ -1024,6 +1029,33 @@ def compute_msssimh_batch(pairs, data_range, sample_type=None, scales=5, weights
     return _msssimh_call("rmgr_ssim_hip_compute_msssimh_host", ctx.handle if ctx is not None else None, params, n, code, data_range, scales, weights, per_scale)
 
 
+def compute_msssim3h(a, b, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
+    """Multi-scale SSIM of two D x H x W host volumes of float16 or bfloat16 samples at `data_range` (any strides numpy can express,
+    negative ones included) through rmgr_ssim_hip_compute_msssim3h_host.  Arrays and sample_type: as compute_ssim3h (np.float16 arrays
+    select float16; np.uint16 arrays carry bit patterns and need sample_type), with its errors.  weights None: Wang's five (scales must be
+    5).  Returns a float32, and with per_scale=True also a (scales, 2) float64 array of [scale]{mcs, mssim}."""
+    a, b, code = _h_volume_pair(a, b, sample_type)
+    params = (Params3H * 1)()
+    params[0] = _params3h_of(a, b)
+    r = _msssimh_call("rmgr_ssim_hip_compute_msssim3h_host", ctx.handle if ctx is not None else None, params, 1, code, data_range, scales, weights, per_scale)
+    return (r[0][0], r[1][0]) if per_scale else r[0]
+
+
+def compute_msssim3h_batch(pairs, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
+    """compute_msssim3h() of many host pairs of one size and one sample type in one call: a float32 array (and a (count, scales, 2) array
+    with per_scale)."""
+    pairs = [_h_volume_pair(a, b, sample_type) for a, b in pairs]
+    n = len(pairs)
+    codes = set(t for _, _, t in pairs)
+    if len(codes) > 1:
+        raise TypeError("the pairs differ in sample type")
+    code = codes.pop() if codes else sample_type_code("float16" if sample_type is None else sample_type)
+    params = (Params3H * max(n, 1))()
+    for i, (a, b, _) in enumerate(pairs):
+        params[i] = _params3h_of(a, b)
+    return _msssimh_call("rmgr_ssim_hip_compute_msssim3h_host", ctx.handle if ctx is not None else None, params, n, code, data_range, scales, weights, per_scale)
+
+
 class DeviceBuffer(object):
     def __init__(self, ctx, nbytes):
         self.ctx, self.nbytes = ctx, nbytes
@@ -1362,6 +1394,27 @@ class Context(object):
         memory), into the 16-bit planes the GradH arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values;
         asynchronous on the context's stream, no host synchronisation."""
         _check("rmgr_ssim_hip_enqueue_msssimh_grad", self.lib.rmgr_ssim_hip_enqueue_msssimh_grad(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), means_dev_ptr,
+            grad_out_dev_ptr, grad_a, grad_b))
+
+    def msssim3h_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False):
+        """MS-SSIM of `count` device-resident pairs of float16 / bfloat16 volumes (a Params3H array) through
+        rmgr_ssim_hip_compute_msssim3h_device: a float32 array, and with per_scale=True also a (count, scales, 2) float64 array."""
+        return _msssimh_call("rmgr_ssim_hip_compute_msssim3h_device", self.handle, params_array, count, sample_type_code(sample_type), data_range,
+                             scales, weights, per_scale)
+
+    def enqueue_msssim3h(self, params_array, count, data_range, sample_type, values_dev_ptr, means_dev_ptr, scales=5, weights=None):
+        """rmgr_ssim_hip_enqueue_msssim3h: per-pair fp64 values and count x scales x 2 fp64 means into device memory, asynchronously on the
+        context's stream."""
+        _check("rmgr_ssim_hip_enqueue_msssim3h", self.lib.rmgr_ssim_hip_enqueue_msssim3h(
+            self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+
+    def enqueue_msssim3h_grad(self, params_array, count, data_range, sample_type, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5,
+                              weights=None):
+        """rmgr_ssim_hip_enqueue_msssim3h_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes, from the forward's
+        means (device memory), into the 16-bit volumes the Grad3H arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32
+        values; asynchronous on the context's stream, no host synchronisation."""
+        _check("rmgr_ssim_hip_enqueue_msssim3h_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3h_grad(
             self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), means_dev_ptr,
             grad_out_dev_ptr, grad_a, grad_b))
 

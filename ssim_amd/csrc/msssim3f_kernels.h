@@ -78,6 +78,18 @@ hipError_t launch_msssim3f_grad(const Pair3FDesc* descs_dev, const Grad3FDesc* g
                                 uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count, const double* means,
                                 const float* g_out, float* ks, float* coef, int which, hipStream_t stream);
 
+// The two launchers above are the first_scale = 0 form of these.  first_scale = 1 is for a caller that runs scale 0 itself
+// (msssim3h_kernels.hip: only scale 0 holds 16-bit samples): the pyramid steps from scale 1 down, the walks of scales >= 1, the reduction
+// over ALL scales -- scale 0's cell partials first, at offset 0, laid out by plan3f(width, height, depth, count, cu_count) --, the product
+// and k_s; in the backward the coefficient and adjoint walks from the coarsest scale down to scale 1.  Row 0 of descs_dev and of
+// grads_dev is not read; the caller has written scale 1's volumes (forward: and scale 0's partials) earlier on `stream`.
+hipError_t launch_msssim3f_from(uint32_t first_scale, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth,
+                                uint32_t scales, float data_range, const double* weights, int cu_count, double* partials, double* means,
+                                double* values, hipStream_t stream);
+hipError_t launch_msssim3f_grad_from(uint32_t first_scale, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, uint32_t count, uint32_t width,
+                                     uint32_t height, uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count,
+                                     const double* means, const float* g_out, float* ks, float* coef, int which, hipStream_t stream);
+
 } // namespace ssim_hip
 
 #endif

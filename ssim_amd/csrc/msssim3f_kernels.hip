@@ -183,10 +183,11 @@ KW3Args weight_args(uint32_t count, uint32_t width, uint32_t height, uint32_t de
     return a;
 }
 
-// The pyramid of `count` pairs: one launch per step, finest first.
-hipError_t launch_pyramid(const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, hipStream_t stream)
+// The pyramid of `count` pairs from scale `first` down: one launch per step, finest first.
+hipError_t launch_pyramid(uint32_t first, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales,
+                          hipStream_t stream)
 {
-    for (uint32_t s = 0; s + 1 < scales; ++s) {
+    for (uint32_t s = first; s + 1 < scales; ++s) {
         const uint32_t sw = ms3_dim(width, s), sh = ms3_dim(height, s), sd = ms3_dim(depth, s);
         const uint32_t dw = ms3_dim(width, s + 1), dh = ms3_dim(height, s + 1), dd = ms3_dim(depth, s + 1);
         const uint64_t per = ((uint64_t)dw * dh * dd + 255) / 256;
@@ -225,13 +226,15 @@ uint32_t msssim3f_per_sub_batch(uint32_t width, uint32_t height, uint32_t depth,
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fit, msssim3f_max_count(width, height, depth)));
 }
 
-hipError_t launch_msssim3f(const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales,
-                           float data_range, const double* weights, int cu_count, double* partials, double* means, double* values,
-                           hipStream_t stream)
+// first_scale 1 (msssim3h_kernels.hip): scale 0 is the caller's -- its pyramid step and its walk, whose partials lie first -- and row 0
+// of descs_dev is not read.  The layout of the partials, the reduction and the product are the same.
+hipError_t launch_msssim3f_from(uint32_t first_scale, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth,
+                                uint32_t scales, float data_range, const double* weights, int cu_count, double* partials, double* means,
+                                double* values, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_call(count, width, height, depth, scales, data_range, weights)) return hipErrorInvalidValue;
-    hipError_t e = launch_pyramid(descs_dev, count, width, height, depth, scales, stream);
+    if (first_scale > 1 || !valid_call(count, width, height, depth, scales, data_range, weights)) return hipErrorInvalidValue;
+    hipError_t e = launch_pyramid(first_scale, descs_dev, count, width, height, depth, scales, stream);
     if (e != hipSuccess) return e;
     KR3Args kr;
     kr.partials = partials; kr.means = means; kr.count = count; kr.scales = scales;
@@ -246,6 +249,7 @@ hipError_t launch_msssim3f(const Pair3FDesc* descs_dev, uint32_t count, uint32_t
         ka.partials = partials + offset;
         kr.offset[s] = offset; kr.cells[s] = geo.cells_per_volume(); kr.voxels[s] = (double)w * (double)h * (double)d;
         offset += kr.cells[s] * 2 * count;
+        if (s < first_scale) continue;
         hipLaunchKernelGGL((msssim3f_walk_kernel<0, kFormMulti>), grid_of(geo), dim3(256), 0, stream, ka);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
@@ -256,18 +260,27 @@ hipError_t launch_msssim3f(const Pair3FDesc* descs_dev, uint32_t count, uint32_t
     return hipGetLastError();
 }
 
-hipError_t launch_msssim3f_grad(const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, uint32_t count, uint32_t width, uint32_t height,
-                                uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count, const double* means,
-                                const float* g_out, float* ks, float* coef, int which, hipStream_t stream)
+hipError_t launch_msssim3f(const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales,
+                           float data_range, const double* weights, int cu_count, double* partials, double* means, double* values,
+                           hipStream_t stream)
+{
+    return launch_msssim3f_from(0, descs_dev, count, width, height, depth, scales, data_range, weights, cu_count, partials, means, values, stream);
+}
+
+// first_scale 1: the k_s of every scale, the pyramid from scale 1 down, the walks from the coarsest scale down to scale 1; rows 0 of
+// descs_dev and grads_dev are not read.
+hipError_t launch_msssim3f_grad_from(uint32_t first_scale, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, uint32_t count, uint32_t width,
+                                     uint32_t height, uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count,
+                                     const double* means, const float* g_out, float* ks, float* coef, int which, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_call(count, width, height, depth, scales, data_range, weights) || which < 1 || which > 3) return hipErrorInvalidValue;
+    if (first_scale > 1 || !valid_call(count, width, height, depth, scales, data_range, weights) || which < 1 || which > 3) return hipErrorInvalidValue;
     hipLaunchKernelGGL(msssim3f_coef_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, depth, scales, weights),
                        means, g_out, ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if ((e = launch_pyramid(descs_dev, count, width, height, depth, scales, stream)) != hipSuccess) return e;
-    for (uint32_t s = scales; s-- > 0;) {
+    if ((e = launch_pyramid(first_scale, descs_dev, count, width, height, depth, scales, stream)) != hipSuccess) return e;
+    for (uint32_t s = scales; s-- > first_scale;) {
         const bool last = s + 1 == scales;
         const Geometry3F geo = plan3f(ms3_dim(width, s), ms3_dim(height, s), ms3_dim(depth, s), count, cu_count);
         KM3Args ka;
@@ -290,6 +303,14 @@ hipError_t launch_msssim3f_grad(const Pair3FDesc* descs_dev, const Grad3FDesc* g
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_msssim3f_grad(const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, uint32_t count, uint32_t width, uint32_t height,
+                                uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count, const double* means,
+                                const float* g_out, float* ks, float* coef, int which, hipStream_t stream)
+{
+    return launch_msssim3f_grad_from(0, descs_dev, grads_dev, count, width, height, depth, scales, data_range, weights, cu_count, means, g_out, ks,
+                                     coef, which, stream);
 }
 
 } // namespace ssim_hip

@@ -1,5 +1,5 @@
 // ssim3_flow.h -- what the host flows of the volume families share (ssim3f_abi.cpp: float32 volumes; ssim3h_abi.cpp: float16 /
-// bfloat16 volumes; msssim3f_abi.cpp: multi-scale SSIM of float32 volumes), written once over the sample type: the sub-batch rule, the bytes of a staged volume, the launch through the
+// bfloat16 volumes; msssim3f_abi.cpp and msssim3h_abi.cpp: multi-scale SSIM of float32 and of 16-bit volumes), written once over the sample type: the sub-batch rule, the bytes of a staged volume, the launch through the
 // context's ring of descriptor tables, the strided copy-back of a map, and the parsed window of a launch.  Not installed.
 #ifndef SSIM_AMD_SSIM3_FLOW_H
 #define SSIM_AMD_SSIM3_FLOW_H

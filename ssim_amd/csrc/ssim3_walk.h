@@ -1,9 +1,10 @@
 // ssim3_walk.h -- the slice walk of SSIM on VOLUMES and its adjoint, written once for the kernel files of the family
-// (ssim3f / ssim3w / ssim3h / ssim3k / ssim3hk / msssim3f _kernels.hip).  Not installed, and included by those six files only: each of them
-// keeps its __global__ kernels -- their names, template parameters and launch bounds, which its tests count and budget -- as one-line
-// calls of walk_body and adjoint_body, and its launch_* functions.  Everything here has internal linkage, so an instantiation and its
-// LDS planes belong to the one kernel of the including file that calls it.  The definition the kernels implement is in
-// include/rmgr/ssim-hip.h; tests/ssim3f_model.py and tests/ssim3k_model.py restate it in float64 and restate the arithmetic below in fp32.
+// (ssim3f / ssim3w / ssim3h / ssim3k / ssim3hk / msssim3f / msssim3h _kernels.hip).  Not installed, and included by those seven files
+// only: each of them keeps its __global__ kernels -- their names, template parameters and launch bounds, which its tests count and
+// budget -- as one-line calls of walk_body and adjoint_body, and its launch_* functions.  Everything here has internal linkage, so an
+// instantiation and its LDS planes belong to the one kernel of the including file that calls it.  The definition the kernels implement
+// is in include/rmgr/ssim-hip.h; tests/ssim3f_model.py and tests/ssim3k_model.py restate it in float64 and restate the arithmetic below
+// in fp32.
 //
 // The bodies are templates on these things, and on nothing else:
 //  * Sample: how a sample gets into a register and how a gradient voxel leaves one.  SampleF32 is a float load / store.  SampleH<TYPE>
@@ -32,7 +33,8 @@
 //  * MS (adjoint_body, defaulted likewise).  kMsNone.  kMsLast: the coarsest scale of MS-SSIM -- k = g_out[volume] is read, and a volume
 //    whose k is 0 gets +0 in every gradient voxel, whatever its samples are.  kMsUp: a finer scale -- the same, and every voxel adds the
 //    adjoint of the clamped 2 x 2 x 2 mean, fp32(0.125 c g_{s+1}(x >> 1, y >> 1, z >> 1)), before its single store; the coarser scale's
-//    dense gradient volumes come through args.up, a member only the multi-scale file's argument struct has.
+//    dense gradient volumes come through args.up, a member only the multi-scale files' argument structs have; its type is the
+//    descriptor of those volumes, float32 (Grad3FDesc) under either sample policy.
 //
 // walk_body<Sample, R, MODE, KFORM, FORM>.  One 256-lane workgroup owns a 16 x 16 tile of (x, y) at an absolute position and walks a chunk of
 // z.  Per source slice (edge-clamped on every axis, any step / stride / sliceStride, 64-bit offsets) the workgroup loads the tile + R
@@ -386,6 +388,12 @@ __device__ __forceinline__ float adjoint_weight(int q, int n, int j, const float
     return w;
 }
 
+// The descriptor of the coarser scale's gradient volumes: what args.up points to (kMsUp); no coarser scale, no member.
+template <class Args, class Sample, bool UP> struct UpDescOf { typedef typename Sample::Grad type; };
+template <class Args, class Sample> struct UpDescOf<Args, Sample, true> {
+    typedef std::remove_cv_t<std::remove_pointer_t<decltype(Args::up)>> type;
+};
+
 // WHICH: 1 dLoss/dA, 2 dLoss/dB, 3 both.  Every pass is a gather in the order j = -R .. R, the first product plain, the others fused; a
 // coefficient outside the volume is 0 (the clamp is in the weights).  A 16-bit gradient voxel is rounded once on its way out.
 template <class Sample, int R, int WHICH, int MS = kMsNone, class Args = ArgsOf<Sample>>
@@ -439,7 +447,8 @@ __device__ __forceinline__ void adjoint_body(const Args& args)
     const bool inside = qx < W && qy < H;
 
     // The multi-scale forms: what the voxel adds from the coarser scale, and the volumes whose k is 0.
-    typename Sample::Grad ud = typename Sample::Grad();
+    typedef typename UpDescOf<Args, Sample, MS == kMsUp>::type UpDesc;
+    UpDesc ud = UpDesc();
     float cxy = 0.125f;
     if constexpr (MS == kMsUp) {
         ud = args.up[pl.vol];

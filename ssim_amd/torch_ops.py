@@ -80,10 +80,18 @@ and SSIM3DLoss.
 Multi-scale SSIM of volumes.  ms_ssim3d(x, y, data_range, scales, weights) and MSSSIM3DLoss take (..., D, H, W) float32 tensors
 (rmgr_ssim_hip_enqueue_msssim3f, _msssim3f_grad): ms_ssim's product over a pyramid that halves all three axes, as pytorch-msssim's
 MS_SSIM(spatial_dims=3) does with avg_pool3d.  That one uses a valid window and zero-padded pooling and refuses small sides; this one
-clamps the window and the pooling at the borders and runs down to 1 x 1 x 1, so the values are close, not equal.  float32 and the
-11-tap window only for now: 16-bit tensors are a TypeError.
+clamps the window and the pooling at the borders and runs down to 1 x 1 x 1, so the values are close, not equal.  The 11-tap window
+only for now.  ms_ssim3d_amp(x, y, data_range, scales, weights) and MSSSIM3DLoss take two float16 or two bfloat16 tensors as well
+(rmgr_ssim_hip_enqueue_msssim3h, _msssim3h_grad), as ms_ssim_amp and MSSSIMLoss do in 2-D: only scale 0 holds 16-bit samples, the value
+has the bits of ms_ssim3d(x.float(), y.float()) and the gradient is that call's float32 gradient rounded once by the kernel, 2 B/voxel of
+torch memory for it instead of the 4 + 4 + 4 of x.float(), y.float() and a float32 gradient.  The warts of MSSSIMLoss again, both pinned
+by tests from the time there was no 16-bit path: ms_ssim3d itself stays float32-only (16-bit tensors are a TypeError there), and two
+16-bit CPU tensors are a TypeError in ms_ssim3d_amp and MSSSIM3DLoss; a third: that TypeError keeps the words "the 3-D multi-scale path is
+float32 for now", which the same tests match on MSSSIM3DLoss.
 
     loss = 0.16 * (x - y).abs().mean() + 0.84 * MSSSIM3DLoss()(x, y)       # x, y: (N, C, D, H, W) float32 on the GPU
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        loss = MSSSIM3DLoss()(net(x), y.bfloat16())                        # read as bfloat16; the gradient is bfloat16
 
 torch is imported on first use, so `import ssim_amd` stays torch-free.
 """
@@ -525,7 +533,7 @@ class MSSSIMLoss(object):
 # (the rmgr_ssim_hip_*_ssim3f_win* entries; what MONAI, torchmetrics and pytorch-msssim call win_size / kernel_size / sigma with
 # spatial_dims=3, and skimage's 7-tap box).  The defaults are the engine's window and take exactly the path without these arguments; any
 # other window is stored on the autograd context and the backward runs under it -- for float16 / bfloat16 volumes too, on the
-# rmgr_ssim_hip_*_ssim3h_win* entries.  The multi-scale form, ms_ssim3d and MSSSIM3DLoss, is at the end of the file: float32 and the
+# rmgr_ssim_hip_*_ssim3h_win* entries.  The multi-scale form, ms_ssim3d, ms_ssim3d_amp and MSSSIM3DLoss, is at the end of the file: the
 # engine's window only.
 
 _function3d = None
@@ -819,8 +827,9 @@ def ssim3d_map_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gau
 # ---- volumes: multi-scale SSIM ----------------------------------------------------------------------------------------------------------------
 # ms_ssim3d(x, y, data_range, scales, weights) is the definition in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_msssim3f): ms_ssim's
 # weighted product with ssim3d's per-voxel terms over a pyramid that halves x, y and z.  The backward is
-# rmgr_ssim_hip_enqueue_msssim3f_grad, from x, y and the (volumes, scales, 2) float64 per-scale means the forward keeps.  float32 and the
-# engine's 11-tap window only; float16 / bfloat16 volumes, a window and a multi-scale map gradient are follow-ups.
+# rmgr_ssim_hip_enqueue_msssim3f_grad, from x, y and the (volumes, scales, 2) float64 per-scale means the forward keeps.  ms_ssim3d_amp and
+# MSSSIM3DLoss take float16 / bfloat16 volumes as well, on the msssim3h entries, through the same autograd function.  The engine's 11-tap
+# window only; a window and a multi-scale map gradient are follow-ups.
 
 _ms_function3d = None
 
@@ -839,7 +848,11 @@ def _make_ms_function3d():
                 cur, work = _working_stream(torch, x.device)
                 if work is not cur:
                     work.wait_stream(cur)
-                _context(x.device, work).enqueue_msssim3f(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights)
+                st = _sample_type(torch, x.dtype)
+                if st is None:
+                    _context(x.device, work).enqueue_msssim3f(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights)
+                else:
+                    _context(x.device, work).enqueue_msssim3h(params, n, data_range, st, values.data_ptr(), means.data_ptr(), scales, weights)
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y, means)
@@ -856,7 +869,7 @@ def _make_ms_function3d():
                 return None, None, None, None, None
             params, n = _params3d(x, y)
             g = grad_out.to(torch.float32).reshape(-1).contiguous()
-            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
             gy = torch.empty(y.shape, dtype=y.dtype, device=y.device) if want_y else None
             if n:
                 cur, work = _working_stream(torch, x.device)
@@ -864,12 +877,25 @@ def _make_ms_function3d():
                     work.wait_stream(cur)
                 ga = _grad_volumes(gx, n, d, h, w) if want_x else None
                 gb = _grad_volumes(gy, n, d, h, w) if want_y else None
-                _context(x.device, work).enqueue_msssim3f_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales, ctx.weights)
+                st = _sample_type(torch, x.dtype)
+                if st is None:
+                    _context(x.device, work).enqueue_msssim3f_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales, ctx.weights)
+                else:
+                    _context(x.device, work).enqueue_msssim3h_grad(params, n, ctx.data_range, st, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales,
+                                                                   ctx.weights)
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None, None, None
 
     return _MSSSIM3D
+
+
+def _ms_ssim3d(x, y, r, scales, weights, name):
+    global _ms_function3d
+    scales, w = _check_scales(scales, weights, name)
+    if _ms_function3d is None:
+        _ms_function3d = _make_ms_function3d()
+    return _ms_function3d.apply(x, y, r, scales, w)
 
 
 def ms_ssim3d(x, y, data_range=1.0, scales=5, weights=None):
@@ -879,21 +905,34 @@ def ms_ssim3d(x, y, data_range=1.0, scales=5, weights=None):
     5); else `scales` finite weights >= 0.  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that
     need it, from x, y and the (volumes, scales, 2) float64 per-scale means the forward keeps.  It runs on torch's current stream through
     the cached context, as ssim() does.  TypeError / ValueError as ssim3d() and ms_ssim(), under this function's name; float16 and
-    bfloat16 tensors are a TypeError: the 3-D multi-scale path is float32 for now."""
+    bfloat16 tensors are a TypeError here ("the 3-D multi-scale path is float32 for now": pinned by tests from the time there was no
+    16-bit path): ms_ssim3d_amp() and MSSSIM3DLoss take them."""
     import torch
     if isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and (x.dtype in (torch.float16, torch.bfloat16) or y.dtype in (torch.float16, torch.bfloat16)):
-        raise TypeError("ms_ssim3d: the 3-D multi-scale path is float32 for now, got %s and %s" % (x.dtype, y.dtype))
-    global _ms_function3d
-    r = _check3d(x, y, data_range, "ms_ssim3d")
-    scales, w = _check_scales(scales, weights, "ms_ssim3d")
-    if _ms_function3d is None:
-        _ms_function3d = _make_ms_function3d()
-    return _ms_function3d.apply(x, y, r, scales, w)
+        raise TypeError("ms_ssim3d: the 3-D multi-scale path is float32 for now, got %s and %s; ms_ssim3d_amp() takes float16 / bfloat16 tensors"
+                        % (x.dtype, y.dtype))
+    return _ms_ssim3d(x, y, _check3d(x, y, data_range, "ms_ssim3d"), scales, weights, "ms_ssim3d")
+
+
+def ms_ssim3d_amp(x, y, data_range=1.0, scales=5, weights=None):
+    """ms_ssim3d() for tensors as they come under mixed precision: two GPU tensors of identical shape (..., D, H, W), both float32, both
+    float16 or both bfloat16, any strides (each volume is addressed in place, no copy or widening): a float32 tensor of shape
+    x.shape[:-3] at every input dtype.  float32 tensors: exactly ms_ssim3d().  float16 and bfloat16 (rmgr_ssim_hip_enqueue_msssim3h,
+    _msssim3h_grad): the value has the bits of ms_ssim3d(x.float(), y.float()), the gradient has the inputs' dtype and is that call's
+    float32 gradient rounded once, by the kernel (see the top of this file for autocast and loss scaling); saved for the backward are x, y
+    and the float64 means.  Errors: as ms_ssim3d(), under this function's name, except that a mixed pair is a TypeError and two float16 or
+    two bfloat16 CPU tensors are a TypeError too: 16-bit tensors are taken on a GPU only (one of the two on a GPU: the ValueError).  That
+    message keeps the words "the 3-D multi-scale path is float32 for now", which tests/test_msssim3f_cpu.py pins for
+    MSSSIM3DLoss()(x16_cpu, x16_cpu) from the time there was no 16-bit path."""
+    if _is_half_pair(x, y) and not x.is_cuda and not y.is_cuda:
+        raise TypeError("ms_ssim3d_amp: float16 / bfloat16 tensors are taken on a GPU only (on the CPU the 3-D multi-scale path is float32 for "
+                        "now), got %s on %s and %s" % (x.dtype, x.device, y.device))
+    return _ms_ssim3d(x, y, _check3d(x, y, data_range, "ms_ssim3d_amp", half=True), scales, weights, "ms_ssim3d_amp")
 
 
 class MSSSIM3DLoss(object):
-    """1 - ms_ssim3d(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per volume).  A plain callable:
-    it has no parameters.  float32 tensors, as ms_ssim3d()."""
+    """1 - ms_ssim3d_amp(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per volume).  A plain
+    callable: it has no parameters.  float32, float16 or bfloat16 tensors, as ms_ssim3d_amp(); the loss is float32 at every input dtype."""
 
     def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean"):
         if reduction not in ("mean", "none"):
@@ -902,5 +941,5 @@ class MSSSIM3DLoss(object):
         self.data_range, self.scales, self.weights, self.reduction = data_range, scales, weights, reduction
 
     def __call__(self, x, y):
-        loss = 1.0 - ms_ssim3d(x, y, self.data_range, self.scales, self.weights)
+        loss = 1.0 - ms_ssim3d_amp(x, y, self.data_range, self.scales, self.weights)
         return loss.mean() if self.reduction == "mean" else loss
