@@ -21,8 +21,8 @@ lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr
 
 # The objects both flavours share: kernels, the C ABI's host layer apart from ssim_context (the only one that reads
 # RMGR_SSIM_USE_DOUBLE: $(OBJ)/ssim_context.o / ssim_context_double.o), the drop-in layer.
-ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/msssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o $(OBJ)/msssim3f_kernels.o $(OBJ)/msssim3h_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim3f_abi.o $(OBJ)/ssim3h_abi.o $(OBJ)/msssim3f_abi.o $(OBJ)/msssim3h_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
-HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim3_flow.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/msssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/msssim3f_kernels.h $(SRC)/msssim3h_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/msssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o $(OBJ)/msssim3f_kernels.o $(OBJ)/msssim3h_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_volumes_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
+HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_flow.h $(SRC)/ssim3_flow.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/msssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/msssim3f_kernels.h $(SRC)/msssim3h_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
 
 # Static flavour under the reference's archive name (CMakeLists.txt:205): the same objects, linked into ONE relocatable
 # object whose only global symbols are the API (the shared libraries' export list has no counterpart for archives: the
@@ -104,7 +104,7 @@ $(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/s
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # The C ABI's host layer.
-$(OBJ)/ssim_context.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim3f_abi.o $(OBJ)/ssim3h_abi.o $(OBJ)/msssim3f_abi.o $(OBJ)/msssim3h_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o: $(OBJ)/%.o: $(SRC)/%.cpp $(HOST_HDRS)
+$(OBJ)/ssim_context.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_volumes_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o: $(OBJ)/%.o: $(SRC)/%.cpp $(HOST_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 

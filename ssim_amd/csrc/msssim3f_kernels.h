@@ -1,4 +1,4 @@
-// msssim3f_kernels.h -- internal interface between the C ABI (msssim3f_abi.cpp, multi-scale SSIM of float32 VOLUMES and its gradient)
+// msssim3f_kernels.h -- internal interface between the C ABI (ssim_volumes_abi.cpp, multi-scale SSIM of float32 VOLUMES and its gradient)
 // and the kernels (msssim3f_kernels.hip).  Not installed.  The definition the kernels implement is written out in
 // include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_msssim3f, rmgr_ssim_hip_enqueue_msssim3f_grad).
 #ifndef SSIM_AMD_MSSSIM3F_KERNELS_H

@@ -1,4 +1,4 @@
-// msssim3h_kernels.h -- internal interface between the C ABI (msssim3h_abi.cpp, multi-scale SSIM of float16 / bfloat16 VOLUMES and its
+// msssim3h_kernels.h -- internal interface between the C ABI (ssim_volumes_abi.cpp, multi-scale SSIM of float16 / bfloat16 VOLUMES and its
 // gradient) and the kernels (msssim3h_kernels.hip).  Not installed.  The definition the kernels implement is written out in
 // include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_msssim3h, rmgr_ssim_hip_enqueue_msssim3h_grad).
 //

@@ -1,20 +1,15 @@
-// ssim3_flow.h -- what the host flows of the volume families share (ssim3f_abi.cpp: float32 volumes; ssim3h_abi.cpp: float16 /
-// bfloat16 volumes; msssim3f_abi.cpp and msssim3h_abi.cpp: multi-scale SSIM of float32 and of 16-bit volumes), written once over the sample type: the sub-batch rule, the bytes of a staged volume, the launch through the
-// context's ring of descriptor tables, the strided copy-back of a map, and the parsed window of a launch.  Not installed.
+// ssim3_flow.h -- the volume-only pieces of the host flow of the volume families (ssim_volumes_abi.cpp), written once over the sample
+// type: the bytes of a staged volume, the sub-batch rule, and the strided copy-back of a map.  What the image families use as well --
+// the scratch cap, the parsed window, the ring launch -- is in ssim_flow.h.  Not installed.
 #ifndef SSIM_AMD_SSIM3_FLOW_H
 #define SSIM_AMD_SSIM3_FLOW_H
 
-#include "ssim_context.h"
-#include "ssimk_kernels.h"      // kSKMaxRadius, window_taps
+#include "ssim_flow.h"
 
 #include <vector>
 
 namespace ssim_host {
 namespace volumes {
-
-const uint64_t kScratchCap = uint64_t(1) << 30;     // device scratch of one sub-batch
-
-inline uint64_t round64(uint64_t bytes) { return (bytes + 63) & ~uint64_t(63); }
 
 // The bytes of the sample range of a volume (Img: rmgr_ssim_hip_Img3F or _Img3H); lo: where the range starts, in samples relative to
 // topLeft (<= 0).
@@ -52,28 +47,6 @@ uint32_t take3f(const Params* params, uint32_t i0, uint32_t count, uint32_t nmax
     return n;
 }
 
-// One launch that reads a table of `bytes` from the next slot of the context's ring (ssim_samples_abi.cpp: ring_launch).
-template <typename Fill, typename Launch>
-int ring_launch(rmgr_ssim_hip_Context* c, size_t bytes, Fill fill, Launch launch)
-{
-    rmgr_ssim_hip_Context_::SfSlot& s = c->sf_slots[c->sf_next];
-    c->sf_next = (c->sf_next + 1) % rmgr_ssim_hip_Context_::kSfSlots;
-    if (s.pending) {
-        HIP_TRY(hipEventSynchronize(s.used));
-        s.pending = false;
-    }
-    HIP_TRY(s.used.ensure());
-    int rc;
-    if ((rc = s.pin.grow(bytes))) return rc;
-    if ((rc = s.dev.grow(bytes))) return rc;
-    fill(s.pin.get());
-    HIP_TRY(hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch(const_cast<const uint8_t*>(s.dev.get())));
-    HIP_TRY(hipEventRecord(s.used, c->stream));
-    s.pending = true;
-    return 0;
-}
-
 // Copies a dense W x H x D float32 map in device memory to the caller's map at its own step, stride and sliceStride (blocking).
 template <typename Params>
 int copy_map_back(const float* src, const Params& p, std::vector<float>& back)
@@ -93,34 +66,6 @@ int copy_map_back(const float* src, const Params& p, std::vector<float>& back)
             for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * p.ssimStep] = s[x];
         }
     return 0;
-}
-
-// The window of a launch: its radius and taps, centre first (ssimk_kernels.h: window_taps).  Radius 5 runs on the 11-tap kernels
-// (ssim3f_kernels.hip / ssim3w_kernels.hip; ssim3h_kernels.hip), the smaller ones on ssim3k_kernels.hip / ssim3hk_kernels.hip.
-struct Window3 {
-    uint32_t radius;
-    float    gf[ssim_hip::kSKMaxRadius + 1];
-};
-
-// The engine's window, that of every entry without _win: 11 taps, Gaussian, sigma 1.5.
-inline Window3 default_window()
-{
-    Window3 w;
-    w.radius = 5;
-    ssim_hip::window_taps(5, ssim_hip::kSKGaussian, 1.5f, w.gf);
-    return w;
-}
-
-// The window of a _win entry: NULL is the engine's; else size 3, 5, 7, 9 or 11, a known kind and -- Gaussian -- a finite sigma > 0.
-inline int window_validate(const rmgr_ssim_hip_Window* window, Window3& w)
-{
-    if (window == NULL) { w = default_window(); return 0; }
-    const uint32_t size = window->size;
-    if (size < 3 || size > 11 || (size & 1u) == 0) return EINVAL;
-    if (window->kind != RMGR_SSIM_HIP_WINDOW_GAUSSIAN && window->kind != RMGR_SSIM_HIP_WINDOW_UNIFORM) return EINVAL;
-    w.radius = (size - 1) / 2;
-    return ssim_hip::window_taps(w.radius, window->kind == RMGR_SSIM_HIP_WINDOW_UNIFORM ? ssim_hip::kSKUniform : ssim_hip::kSKGaussian, window->sigma, w.gf)
-               ? 0 : EINVAL;
 }
 
 } // namespace volumes

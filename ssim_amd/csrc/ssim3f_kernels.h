@@ -1,4 +1,4 @@
-// ssim3f_kernels.h -- internal interface between the C ABI (ssim3f_abi.cpp, SSIM of float32 VOLUMES and its gradient) and the kernels
+// ssim3f_kernels.h -- internal interface between the C ABI (ssim_volumes_abi.cpp, SSIM of float32 VOLUMES and its gradient) and the kernels
 // (ssim3f_kernels.hip).  Not installed.  The definition the kernels implement is written out in include/rmgr/ssim-hip.h
 // (rmgr_ssim_hip_enqueue_ssim3f, rmgr_ssim_hip_enqueue_ssim3f_grad).
 #ifndef SSIM_AMD_SSIM3F_KERNELS_H

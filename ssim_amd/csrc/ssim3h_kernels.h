@@ -1,4 +1,4 @@
-// ssim3h_kernels.h -- internal interface between the C ABI (ssim3h_abi.cpp, SSIM of float16 / bfloat16 VOLUMES, its gradient and the
+// ssim3h_kernels.h -- internal interface between the C ABI (ssim_volumes_abi.cpp, SSIM of float16 / bfloat16 VOLUMES, its gradient and the
 // gradient of its map) and the kernels (ssim3h_kernels.hip).  Not installed.  The definition the kernels implement is written out in
 // include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssim3h, _ssim3h_grad, _ssim3h_map_grad).
 #ifndef SSIM_AMD_SSIM3H_KERNELS_H

@@ -1,4 +1,4 @@
-// ssim3hk_kernels.h -- internal interface between the C ABI (ssim3h_abi.cpp, SSIM of float16 / bfloat16 VOLUMES under a caller-chosen
+// ssim3hk_kernels.h -- internal interface between the C ABI (ssim_volumes_abi.cpp, SSIM of float16 / bfloat16 VOLUMES under a caller-chosen
 // window) and the kernels of the windows of 3, 5, 7 and 9 taps (ssim3hk_kernels.hip).  Not installed.  The definition the kernels
 // implement is written out in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssim3h_win and its siblings).  Windows of 11 taps run on the
 // kernels of ssim3h_kernels.hip with the window's taps; the taps of every window are ssimk_kernels.h's (window_taps), the chunks are

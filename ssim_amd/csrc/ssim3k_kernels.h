@@ -1,4 +1,4 @@
-// ssim3k_kernels.h -- internal interface between the C ABI (ssim3f_abi.cpp, SSIM of float32 VOLUMES under a caller-chosen window) and the
+// ssim3k_kernels.h -- internal interface between the C ABI (ssim_volumes_abi.cpp, SSIM of float32 VOLUMES under a caller-chosen window) and the
 // kernels of the windows of 3, 5, 7 and 9 taps (ssim3k_kernels.hip).  Not installed.  The definition the kernels implement is written out
 // in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssim3f_win and its siblings).  Windows of 11 taps run on the kernels of
 // ssim3f_kernels.hip / ssim3w_kernels.hip with the window's taps; the taps of every window are ssimk_kernels.h's (window_taps).

@@ -1,4 +1,4 @@
-// ssim3w_kernels.h -- internal interface between the C ABI (ssim3f_abi.cpp, gradient of the 3-D SSIM map for a per-voxel upstream
+// ssim3w_kernels.h -- internal interface between the C ABI (ssim_volumes_abi.cpp, gradient of the 3-D SSIM map for a per-voxel upstream
 // gradient) and the kernels (ssim3w_kernels.hip).  Not installed.  The definition the kernels implement is written out in
 // include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_ssim3f_map_grad).
 #ifndef SSIM_AMD_SSIM3W_KERNELS_H

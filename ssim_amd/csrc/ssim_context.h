@@ -1,6 +1,7 @@
 // ssim_context.h -- internal to the C ABI (include/rmgr/ssim-hip.h): the context, the resources it owns, and what the host-layer
 // files share.  ssim_context.cpp creates and destroys contexts and keeps the default pool; ssim_hip_abi.cpp holds the entry points
-// of 8-bit samples, ssim_samples_abi.cpp those of 16-bit, float32 and float16 / bfloat16 samples, ssim3f_abi.cpp those of float32 volumes, msssim3f_abi.cpp those of multi-scale SSIM of float32 volumes; ssim_comm.cpp the RCCL all-reduce;
+// of 8-bit samples, ssim_samples_abi.cpp those of 16-bit, float32 and float16 / bfloat16 samples, ssim_volumes_abi.cpp those of
+// float32 and float16 / bfloat16 volumes, single- and multi-scale (the two share ssim_flow.h); ssim_comm.cpp the RCCL all-reduce;
 // ssim_tune.cpp profiling and tuning.  Not installed.
 #ifndef SSIM_AMD_CONTEXT_H
 #define SSIM_AMD_CONTEXT_H
@@ -197,12 +198,12 @@ struct rmgr_ssim_hip_Context_ {
     // multi-scale SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_msssimf*), reused in stream order: the pyramid planes
     // of scales >= 1, the backward's gradient planes of scales >= 1, cell partials, the backward's coefficients k_s, and the
     // blocking entry points' values and means (device, and pinned for the copy back).  Descriptor tables come from sf_slots.
-    // Multi-scale SSIM of float32 volumes (rmgr_ssim_hip_*_msssim3f*, msssim3f_abi.cpp) uses the same six for its pyramid volumes, coarse
+    // Multi-scale SSIM of volumes (rmgr_ssim_hip_*_msssim3f*, _msssim3h*; ssim_volumes_abi.cpp) uses the same six for its pyramid volumes, coarse
     // gradient volumes, k_s, cell partials and outputs, and s3_coef below for the coefficient volumes.
     DeviceBuffer<float>    msf_pyramid, msf_grads, msf_coef;
     DeviceBuffer<double>   msf_partials, msf_out;
     PinnedBuffer<double>   msf_out_pin;
-    // SSIM of float32 and of float16 / bfloat16 volumes (rmgr_ssim_hip_*_ssim3f*, ssim3f_abi.cpp; _ssim3h*, ssim3h_abi.cpp): the backward's
+    // SSIM of float32 and of float16 / bfloat16 volumes (rmgr_ssim_hip_*_ssim3f*, _ssim3h*; ssim_volumes_abi.cpp): the backward's
     // float32 coefficient volumes, rewritten by every sub-batch in stream order.  Descriptor tables, cell partials and pinned sums are
     // sf_slots, sf_partials and sf_sums_pin.
     DeviceBuffer<float>    s3_coef;

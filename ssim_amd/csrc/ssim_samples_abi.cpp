@@ -15,13 +15,9 @@
 // Every family runs on one ring of descriptor tables, one buffer of cell partials and one of pinned sums (sf_slots, sf_partials,
 // sf_sums_pin of the context): one stream, stream order.  An enqueue form therefore never waits for the host, except -- at most -- for
 // the launch that read its ring slot kSfSlots enqueues ago.
-#include "ssim_context.h"
-#include "ssimh_kernels.h"
+#include "ssim_flow.h"
 #include "msssimh_kernels.h"
 #include "ssimw_kernels.h"
-#include "ssimk_kernels.h"
-
-#include <cmath>
 
 using namespace ssim_host;
 
@@ -33,8 +29,6 @@ using ssim_hip::GradFDesc;
 using ssim_hip::PairHDesc;
 using ssim_hip::GradHDesc;
 using ssim_hip::GradOutFDesc;
-
-const uint64_t kScratchCap = uint64_t(1) << 30;     // device scratch (partials, pyramids, staged images and maps) of one sub-batch
 
 // ---- the families ------------------------------------------------------------------------------------------------------------------------------
 // Params / Desc / Sample: the public parameter block, the kernels' descriptor of a pair, the type of a sample.  launch() enqueues the
@@ -54,22 +48,6 @@ struct Family16 {
     { return ssim_hip::launch_ssim16(geo, dev, map, unit, wide, depth, c->xcd_count, c->sf_partials, sums, c->stream); }
 };
 
-// The window of a float32 launch: its radius and taps, centre first (ssimk_kernels.h: window_taps).  Radius 5 runs on the kernels of
-// ssimf_kernels.hip / ssimw_kernels.hip, the smaller ones on ssimk_kernels.hip.
-struct WindowF {
-    uint32_t radius;
-    float    gf[ssim_hip::kSKMaxRadius + 1];
-};
-
-// The engine's window, that of every entry without _win: 11 taps, Gaussian, sigma 1.5.
-WindowF default_window()
-{
-    WindowF w;
-    w.radius = 5;
-    ssim_hip::window_taps(5, ssim_hip::kSKGaussian, 1.5f, w.gf);
-    return w;
-}
-
 struct FamilyF {
     typedef rmgr_ssim_hip_ParamsF Params;
     typedef rmgr_ssim_hip_GradF Grad;
@@ -82,7 +60,7 @@ struct FamilyF {
     static Geometry plan(uint32_t W, uint32_t H, uint32_t n, int cus) { return ssim_hip::planf(W, H, n, cus); }
     static bool fits_narrow(const Desc& d) { return ssim_hip::fitsf_narrow(d); }
     float range;
-    WindowF win;
+    Window win;
     // geo is planf()'s: the cells (and with them the partials) are the same for every radius; a smaller window re-plans its strips, which
     // pay fewer warm-up rows
     hipError_t launch(rmgr_ssim_hip_Context* c, const Geometry& geo, const Desc* dev, bool map, bool unit, bool wide, double* sums) const
@@ -131,8 +109,6 @@ int validate_pairs(uint32_t count, const typename F::Params* params, const void*
     return 0;
 }
 
-bool valid_range(float r) { return r > 0.0f && std::isfinite(r); }
-
 int ssim16_validate(uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t bitDepth, const void* out)
 {
     if (bitDepth < RMGR_SSIM_HIP_SSIM16_MIN_DEPTH || bitDepth > RMGR_SSIM_HIP_SSIM16_MAX_DEPTH) return EINVAL;
@@ -145,26 +121,12 @@ int ssimf_validate(uint32_t count, const rmgr_ssim_hip_ParamsF* params, float da
     return validate_pairs<FamilyF>(count, params, out);
 }
 
-// The window of a _win entry: NULL is the engine's; else size 3, 5, 7, 9 or 11, a known kind and -- Gaussian -- a finite sigma > 0.
-int window_validate(const rmgr_ssim_hip_Window* window, WindowF& w)
-{
-    if (window == NULL) { w = default_window(); return 0; }
-    const uint32_t size = window->size;
-    if (size < 3 || size > 11 || (size & 1u) == 0) return EINVAL;
-    if (window->kind != RMGR_SSIM_HIP_WINDOW_GAUSSIAN && window->kind != RMGR_SSIM_HIP_WINDOW_UNIFORM) return EINVAL;
-    w.radius = (size - 1) / 2;
-    return ssim_hip::window_taps(w.radius, window->kind == RMGR_SSIM_HIP_WINDOW_UNIFORM ? ssim_hip::kSKUniform : ssim_hip::kSKGaussian, window->sigma, w.gf)
-               ? 0 : EINVAL;
-}
-
 int ssimh_validate(uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t sampleType, float dataRange, const void* out)
 {
     if (sampleType != RMGR_SSIM_HIP_SAMPLE_F16 && sampleType != RMGR_SSIM_HIP_SAMPLE_BF16) return EINVAL;
     if (!valid_range(dataRange)) return EINVAL;
     return validate_pairs<FamilyH>(count, params, out);
 }
-
-int ssimh_type(uint32_t sampleType) { return sampleType == RMGR_SSIM_HIP_SAMPLE_BF16 ? ssim_hip::kSHTypeBF16 : ssim_hip::kSHTypeF16; }
 
 // The planes of a gradient entry: gradA and / or gradB, every plane non-NULL and aligned to its samples.
 template <typename G>
@@ -222,8 +184,6 @@ GradOutFDesc make_gout(const rmgr_ssim_hip_GradOutF& m)
 }
 
 // ---- sub-batches and staging -------------------------------------------------------------------------------------------------------------------
-
-uint64_t round64(uint64_t bytes) { return (bytes + 63) & ~uint64_t(63); }
 
 // The bytes of the sample range of a width x height image; lo: where the range starts, in samples relative to topLeft (<= 0).
 template <typename F, typename Img>
@@ -292,31 +252,6 @@ int copy_map_back(const float* src, float* map, ptrdiff_t step, ptrdiff_t stride
         const float* s = &back[(size_t)y * W];
         for (uint32_t x = 0; x < W; ++x) row[(ptrdiff_t)x * step] = s[x];
     }
-    return 0;
-}
-
-// ---- the ring of descriptor tables -----------------------------------------------------------------------------------------------------------
-
-// One launch that reads a table of `bytes` from the next slot of the ring: waits, at most, for the launch that read the slot kSfSlots
-// enqueues ago; fill(pinned) writes the table, launch(device) enqueues its reader.
-template <typename Fill, typename Launch>
-int ring_launch(rmgr_ssim_hip_Context* c, size_t bytes, Fill fill, Launch launch)
-{
-    rmgr_ssim_hip_Context_::SfSlot& s = c->sf_slots[c->sf_next];
-    c->sf_next = (c->sf_next + 1) % rmgr_ssim_hip_Context_::kSfSlots;
-    if (s.pending) {
-        HIP_TRY(hipEventSynchronize(s.used));
-        s.pending = false;
-    }
-    HIP_TRY(s.used.ensure());
-    int rc;
-    if ((rc = s.pin.grow(bytes))) return rc;
-    if ((rc = s.dev.grow(bytes))) return rc;
-    fill(s.pin.get());
-    HIP_TRY(hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch(const_cast<const uint8_t*>(s.dev.get())));
-    HIP_TRY(hipEventRecord(s.used, c->stream));
-    s.pending = true;
     return 0;
 }
 
@@ -514,7 +449,7 @@ struct MultiH {
                        double* means, double* values) const
     {
         return ssim_hip::launch_msssimh(reinterpret_cast<const PairHDesc*>(pairs + (size_t)scales * n * sizeof(PairFDesc)),
-                                        reinterpret_cast<const PairFDesc*>(pairs), n, W, H, scales, ssimh_type(sampleType), wide, range, w, c->cu_count,
+                                        reinterpret_cast<const PairFDesc*>(pairs), n, W, H, scales, sample_type(sampleType), wide, range, w, c->cu_count,
                                         c->xcd_count, c->msf_partials, means, values, c->stream);
     }
     hipError_t backward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, const uint8_t* grads, uint32_t n, uint32_t W, uint32_t H, uint32_t scales,
@@ -523,7 +458,7 @@ struct MultiH {
         return ssim_hip::launch_msssimh_grad(reinterpret_cast<const PairHDesc*>(pairs + (size_t)scales * n * sizeof(PairFDesc)),
                                              reinterpret_cast<const PairFDesc*>(pairs),
                                              reinterpret_cast<const GradHDesc*>(grads + (size_t)scales * n * sizeof(GradFDesc)),
-                                             reinterpret_cast<const GradFDesc*>(grads), n, W, H, scales, ssimh_type(sampleType), range, w, means, g_out,
+                                             reinterpret_cast<const GradFDesc*>(grads), n, W, H, scales, sample_type(sampleType), range, w, means, g_out,
                                              c->msf_coef, which, c->stream);
     }
 };
@@ -733,7 +668,7 @@ int ms_grad_entry(rmgr_ssim_hip_Context* c, const M& fam, uint32_t count, const 
 
 // ---- SSIM of float32 samples: what an entry does once its arguments are valid; `win` is the engine's window or the caller's ------------------
 
-int ssimf_enqueue_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const WindowF& win,
+int ssimf_enqueue_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const Window& win,
                         double* sumsDevice)
 {
     if (!c) return EINVAL;
@@ -741,7 +676,7 @@ int ssimf_enqueue_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssi
     return enqueue_all(c, FamilyF{dataRange, win}, count, params, sumsDevice);
 }
 
-int ssimf_device_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const WindowF& win, float* ssim)
+int ssimf_device_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const Window& win, float* ssim)
 {
     if (!c) return EINVAL;
     USE_DEVICE(c);
@@ -749,7 +684,7 @@ int ssimf_device_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim
 }
 
 // gradOutDevice: the scalar upstream form; gradOutMaps: the per-pixel form.  Exactly one is given.
-int ssimf_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const WindowF& win,
+int ssimf_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const Window& win,
                      const float* gradOutDevice, const rmgr_ssim_hip_GradOutF* gradOutMaps, const rmgr_ssim_hip_GradF* gradA,
                      const rmgr_ssim_hip_GradF* gradB)
 {
@@ -813,7 +748,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                              float dataRange, const rmgr_ssim_hip_Window* window, double* sumsDevice) RMGR_NOEXCEPT
 {
-    WindowF win;
+    Window win;
     int rc = ssimf_validate(count, params, dataRange, sumsDevice);
     if (rc || (rc = window_validate(window, win))) return rc;
     return ssimf_enqueue_entry(c, count, params, dataRange, win, sumsDevice);
@@ -829,7 +764,7 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssimf_device(rmgr_ssim_hip_Context* c, rmgr_u
 rmgr_int32_t rmgr_ssim_hip_compute_ssimf_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                                     float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT
 {
-    WindowF win;
+    Window win;
     int rc = ssimf_validate(count, params, dataRange, ssim);
     if (rc || (rc = window_validate(window, win))) return rc;
     return ssimf_device_entry(c, count, params, dataRange, win, ssim);
@@ -845,7 +780,7 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssimf_host(rmgr_ssim_hip_Context* c, rmgr_uin
 rmgr_int32_t rmgr_ssim_hip_compute_ssimf_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                                   float dataRange, const rmgr_ssim_hip_Window* window, float* ssim) RMGR_NOEXCEPT
 {
-    WindowF win;
+    Window win;
     int rc = ssimf_validate(count, params, dataRange, ssim);
     if (rc || (rc = window_validate(window, win))) return rc;
     return blocking_host(c, FamilyF{dataRange, win}, count, params, ssim);
@@ -865,7 +800,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_grad(rmgr_ssim_hip_Context* c, rmgr
                                                   float dataRange, const rmgr_ssim_hip_Window* window, const float* gradOutDevice,
                                                   const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
 {
-    WindowF win;
+    Window win;
     int rc = ssimf_validate(count, params, dataRange, gradOutDevice);
     if (rc || (rc = window_validate(window, win))) return rc;
     if ((rc = validate_grads(count, gradA, gradB))) return rc;
@@ -881,7 +816,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh(rmgr_ssim_hip_Context* c, rmgr_uint32_t
     if (rc) return rc;
     if (!c) return EINVAL;
     USE_DEVICE(c);
-    return enqueue_all(c, FamilyH{ssimh_type(sampleType), dataRange}, count, params, sumsDevice);
+    return enqueue_all(c, FamilyH{sample_type(sampleType), dataRange}, count, params, sumsDevice);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssimh_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
@@ -891,14 +826,14 @@ rmgr_int32_t rmgr_ssim_hip_compute_ssimh_device(rmgr_ssim_hip_Context* c, rmgr_u
     if (rc) return rc;
     if (!c) return EINVAL;
     USE_DEVICE(c);
-    return blocking(c, FamilyH{ssimh_type(sampleType), dataRange}, count, params, ssim, false);
+    return blocking(c, FamilyH{sample_type(sampleType), dataRange}, count, params, ssim, false);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssimh_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
                                               rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
 {
     const int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
-    return rc ? rc : blocking_host(c, FamilyH{ssimh_type(sampleType), dataRange}, count, params, ssim);
+    return rc ? rc : blocking_host(c, FamilyH{sample_type(sampleType), dataRange}, count, params, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
@@ -911,7 +846,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uin
     if (!c) return EINVAL;
     USE_DEVICE(c);
     const uint32_t W = params[0].width, H = params[0].height;
-    const int which = grad_which(gradA, gradB), type = ssimh_type(sampleType);
+    const int which = grad_which(gradA, gradB), type = sample_type(sampleType);
     return enqueue_grads<FamilyH>(c, count, params, gradA, gradB, NULL,
         [&](uint32_t n, uint32_t i0, const PairHDesc* pd, const GradHDesc* gd, const GradOutFDesc*) {
             return ssim_hip::launch_ssimh_grad(W, H, n, pd, gd, type, gradOutDevice + i0, dataRange, which, c->stream);
@@ -935,7 +870,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* c, 
                                                       float dataRange, const rmgr_ssim_hip_Window* window, const rmgr_ssim_hip_GradOutF* gradOutMaps,
                                                       const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
 {
-    WindowF win;
+    Window win;
     int rc = ssimf_validate(count, params, dataRange, gradOutMaps);
     if (rc || (rc = window_validate(window, win))) return rc;
     if ((rc = validate_grad_maps(count, gradOutMaps))) return rc;
@@ -954,7 +889,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* c, rmgr
     if (!c) return EINVAL;
     USE_DEVICE(c);
     const uint32_t W = params[0].width, H = params[0].height;
-    const int which = grad_which(gradA, gradB), type = ssimh_type(sampleType);
+    const int which = grad_which(gradA, gradB), type = sample_type(sampleType);
     return enqueue_grads<FamilyH>(c, count, params, gradA, gradB, gradOutMaps,
         [&](uint32_t n, uint32_t, const PairHDesc* pd, const GradHDesc* gd, const GradOutFDesc* od) {
             return ssim_hip::launch_ssimw_grad_h(W, H, n, pd, gd, type, od, dataRange, which, c->stream);

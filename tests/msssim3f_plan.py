@@ -1,5 +1,5 @@
 """The scratch and sub-batch rule of multi-scale SSIM of float32 volumes (msssim3f_kernels.hip: msssim3f_max_count,
-msssim3f_scratch_bytes, msssim3f_per_sub_batch; msssim3f_abi.cpp passes them to take3f), restated in plain Python.  No GPU, no library
+msssim3f_scratch_bytes, msssim3f_per_sub_batch; ssim_volumes_abi.cpp passes them to take3f), restated in plain Python.  No GPU, no library
 call.  Sizes are W x H x D.
 
 Per pair: the pyramid of both volumes (scales >= 1, float32), in the backward one or two coarse gradient pyramids, the coefficient volumes

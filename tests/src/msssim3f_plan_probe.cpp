@@ -2,7 +2,7 @@
 //
 // Reads rows "width height depth scales cap" from stdin and prints one row "max_count pyramid_floats partials forward_bytes one_grad_bytes
 // both_grads_bytes forward_per one_grad_per both_grads_per" each, from the functions of msssim3f_kernels.h in the project's kernel objects
-// that the host flow (msssim3f_abi.cpp) calls.  Host arithmetic only: no HIP call, no device.
+// that the host flow (ssim_volumes_abi.cpp) calls.  Host arithmetic only: no HIP call, no device.
 #include <cstdio>
 
 #include "msssim3f_kernels.h"

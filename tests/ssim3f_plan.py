@@ -1,4 +1,4 @@
-"""The planner of the volume family (ssim3f_kernels.hip: plan3f, ssim3f_max_count) and the sub-batches of its host flow (ssim3f_abi.cpp:
+"""The planner of the volume family (ssim3f_kernels.hip: plan3f, ssim3f_max_count) and the sub-batches of its host flow (ssim_volumes_abi.cpp:
 take3f for device-resident volumes), restated in plain Python.  No GPU, no library call.  Sizes are W x H x D.
 
 The walk cuts every 16 x 16 (x, y) tile of every volume into z-chunks, one workgroup each; the fp64 reduction cells are 16 x 16 x 8 voxels

@@ -318,6 +318,33 @@ def test_sub_batches_of_the_backward_scratch(gpu_ctx):
         vb.free()
 
 
+def test_sub_batches_of_the_forward(gpu_ctx):
+    """One more volume of 2 x 1 x 3 at two scales than a sub-batch of the forward holds (tests/msssim3f_plan.py: at this size the launch
+    limit ends it, long before the scratch does): sub-batches of 65535 volumes and of one, in one enqueue.  The volumes are drawn from five
+    distinct pairs; the only volume of the second sub-batch differs from its neighbour and from the first volume of the call, so that an
+    offset into the values, the means or the descriptors that forgets the sub-batch's first volume shows.  Every value and mean has the
+    bits of its pair launched alone."""
+    size, scales = (2, 1, 3), 2
+    n = MP.per_sub_batch(*size, scales, 0) + 1
+    assert n == 65536 and MP.sub_batches(*size, scales, 0, n) == [(0, 65535), (65535, 1)]
+    pairs = [random_pair(size, 90 + k) for k in range(5)]
+    which = np.random.default_rng([CH.SEED, n]).permutation(np.arange(n) % len(pairs)).tolist()
+    assert which[n - 1] != which[n - 2] and which[n - 1] != which[0]
+    vols = [(Vol(gpu_ctx, a.shape, "dense", a), Vol(gpu_ctx, a.shape, "dense", b)) for a, b in pairs]
+    lone = [run(gpu_ctx, None, 1.0, scales, uniform(scales), inputs=[vols[k]]) for k in range(len(pairs))]
+    for k in range(len(pairs)):                                  # distinct pairs give distinct values and means
+        for o in range(k):
+            assert not same(lone[k][0], lone[o][0]) and not same(lone[k][1][0, 0], lone[o][1][0, 0]), (k, o)
+    v, m, _ = run(gpu_ctx, None, 1.0, scales, uniform(scales), inputs=[vols[k] for k in which])
+    pick = np.asarray(which)
+    bad = np.flatnonzero((v.view(np.uint64) != np.concatenate([lone[k][0] for k in range(len(pairs))])[pick].view(np.uint64)) |
+                         np.any(m.view(np.uint64) != np.concatenate([lone[k][1] for k in range(len(pairs))])[pick].view(np.uint64), axis=(1, 2)))
+    assert len(bad) == 0, "%d of %d volumes differ from their pair launched alone; the first: volume %d" % (len(bad), n, bad[0])
+    for va, vb in vols:
+        va.free()
+        vb.free()
+
+
 def test_a_dozen_enqueues_share_the_scratch_in_stream_order(gpu_ctx):
     """msssim3f forward and backward of two shapes mixed with ssim3f_grad and msssimf on one context without a host wait: every output byte
     equals the same call issued alone on another context."""

@@ -12,8 +12,9 @@ Every 16-bit call keeps its inputs, its gradient volumes, its values and its mea
 after every call the gaps and every element of a strided buffer outside the volumes are asserted untouched.  After a return code that is
 neither success nor EINVAL the module starts nothing more on the GPU (test_gpu_ssimk's _device_error, through test_gpu_ssim3h.call).
 
-Cost, measured on an MI355X: the 95 tests take 8.3 s together, the PyTorch child process included; the device holds 1.5 GiB more than
-before the module at the peak (the sub-batch test's 1 GiB of scratch and its 68 gradient pairs).
+Cost, measured on an MI355X: the 95 tests other than test_sub_batches_of_the_forward (under 3 s per encoding) take 8.3 s together, the
+PyTorch child process included; the device holds 1.5 GiB more than before the module at the peak (the backward sub-batch test's 1 GiB of
+scratch and its 68 gradient pairs).
 """
 import json
 import os
@@ -318,6 +319,35 @@ def test_sub_batches_of_the_backward_scratch(device, enc):
         for i, c in enumerate(combos):
             assert same64(v[i:i + 1], lone[c][0]) and same64(m[i], lone[c][1][0]), (i, c)
             assert HM.same(gr[i][0], lone[c][2][0][0], enc) and HM.same(gr[i][1], lone[c][2][0][1], enc), (i, c)
+    finally:
+        ins.results()
+        ins.free()
+
+
+@ENC
+def test_sub_batches_of_the_forward(device, enc):
+    """test_gpu_msssim3f's test of the same name on 16-bit volumes: 65536 volumes of 2 x 1 x 3 at two scales, one more than a launch takes,
+    drawn from five pairs; the only volume of the second sub-batch differs from its neighbour and from the first volume of the call.  Every
+    value and mean has the bits of its pair launched alone, and every lone launch those of the float32 path."""
+    size, scales = (2, 1, 3), 2
+    n = MP.per_sub_batch(*size, scales, 0) + 1
+    assert n == 65536 and MP.sub_batches(*size, scales, 0, n) == [(0, 65535), (65535, 1)]
+    pairs = [IN.random_pair(size, 90 + k, enc) for k in range(5)]
+    which = np.random.default_rng([CH.SEED, n]).permutation(np.arange(n) % len(pairs)).tolist()
+    assert which[n - 1] != which[n - 2] and which[n - 1] != which[0]
+    ins = upload_inputs(device, pairs)
+    try:
+        lone = [run(device, enc, None, 1.0, scales, uniform(scales), inputs=(ins, [k])) for k in range(len(pairs))]
+        for k in range(len(pairs)):
+            ref = reference(device, enc, [pairs[k]], 1.0, scales, uniform(scales))
+            assert same64(lone[k][0], ref[0]) and same64(lone[k][1], ref[1])
+            for o in range(k):                                   # distinct pairs give distinct values and means
+                assert not same64(lone[k][0], lone[o][0]) and not same64(lone[k][1][0, 0], lone[o][1][0, 0]), (k, o)
+        v, m, _ = run(device, enc, None, 1.0, scales, uniform(scales), inputs=(ins, which))
+        pick = np.asarray(which)
+        bad = np.flatnonzero((v.view(np.uint64) != np.concatenate([x[0] for x in lone])[pick].view(np.uint64)) |
+                             np.any(m.view(np.uint64) != np.concatenate([x[1] for x in lone])[pick].view(np.uint64), axis=(1, 2)))
+        assert len(bad) == 0, "%d of %d volumes differ from their pair launched alone; the first: volume %d" % (len(bad), n, bad[0])
     finally:
         ins.results()
         ins.free()

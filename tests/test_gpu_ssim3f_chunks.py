@@ -1,4 +1,4 @@
-"""GPU: the scheduling of the volume family (ssim3f: walk, reduction and adjoint kernels, the host flow of ssim3f_abi.cpp) -- every chunk
+"""GPU: the scheduling of the volume family (ssim3f: walk, reduction and adjoint kernels, the host flow of ssim_volumes_abi.cpp) -- every chunk
 depth plan3f can choose, the sub-batches of a call beyond the launch limit and the descriptor ring beyond its slots: every volume must
 have, bit for bit, the sum, the map and the gradients it has when it is launched alone.  Sizes are W x H x D; arrays are (D, H, W).
 

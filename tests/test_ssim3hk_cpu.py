@@ -295,7 +295,8 @@ def test_the_planner_of_the_16_bit_entries_is_plan3k_and_knows_no_sample_size(tm
     """tests/src/plan3k_probe.cpp built with ssim3hk_kernels.h in front of it: the plan3k the 16-bit windowed entries see through that
     header is the one tests/ssim3k_plan.py restates (tests/test_ssim3k_cpu.py holds it to the float32 entries' header), for every
     radius, 17 x 17 x 131 at the counts the GPU module launches included.  Its arguments are radius, W, H, D, count and CUs -- no sample
-    size --, and ssim3h_abi.cpp plans every launch with exactly those."""
+    size --, and the volume host flow (ssim_volumes_abi.cpp: one forward and one gradient, serving both sample types) plans every launch
+    with exactly those."""
     obj3f = "build/obj/ssim3f_kernels.o"
     r = subprocess.run(["make", "-C", ROOT, obj3f], capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -325,7 +326,7 @@ def test_the_planner_of_the_16_bit_entries_is_plan3k_and_knows_no_sample_size(tm
     assert list(inspect.signature(PK.plan3k).parameters) == ["radius", "width", "height", "depth", "count", "cus"]
     with open(os.path.join(CSRC, "ssim3k_kernels.h")) as f:
         assert re.search(r"plan3k\(uint32_t radius, uint32_t width, uint32_t height, uint32_t depth, uint32_t count, int cu_count\)", f.read())
-    with open(os.path.join(CSRC, "ssim3h_abi.cpp")) as f:
+    with open(os.path.join(CSRC, "ssim_volumes_abi.cpp")) as f:
         abi = f.read()
     calls = re.findall(r"plan3k\(([^)]*)\)", abi)
     assert len(calls) == 2 and all(c == "win.radius, W, H, D, n, c->cu_count" for c in calls), calls
