@@ -25,6 +25,13 @@ boundary.  `narrow high` is 0.85 + 0.15 base: means near the range, but its vari
 narrower band (0.98 + 0.02 base) leaves up to 3 times the gradient figure of seven (family, window) pairs in the emulation, more than
 the two an exclusion may cover.  sigma near 0 is driven by the constants, the flat classes and the steps' flat sides at low means only;
 means near the range WITH tiny variance are not covered by this catalogue.
+
+The 2-D multi-scale family (tests/test_gpu_msssimf_content.py, planes of 300 x 40 at 4 scales) is the one place where the condition does
+not hold for every class, and there the amplitudes stay as they are: msssimf_model.CLASS_EMU holds the three classes' own emulated (value,
+mean, gradient) figures and the GPU bound is derived from those.  They are measured limits of centring: the step on a strip column's edge
+(x = 256) is a step ON the centre sample two scales down, where the flat side is blurred at a' = -0.25 and E[a'^2] - mu'^2 cancels against
+C2 (5.0e-6, 2.0e-5, 4.3e-6); with every sample above the range every centre is 0 and nothing is centred (`offset above the range`: 2.5e-6,
+1.2e-5, 2.1e-4; `unit data at range 1e-6`: 8.4e-7, 3.2e-6, 7.6e-5).
 """
 import numpy as np
 

@@ -1,7 +1,7 @@
 """float64 model of the library's multi-scale SSIM of float32 samples and of its gradient (the definition in include/rmgr/ssim-hip.h,
 rmgr_ssim_hip_*_msssimf*), and an fp32 emulation of the kernels that compute it.
 
-The yardstick of tests/test_msssimf_cpu.py and tests/test_gpu_msssimf.py.  Built on tests/ssimf_model.py's blur / blur_t / constants:
+The yardstick of tests/test_msssimf_cpu.py, tests/test_gpu_msssimf.py and tests/test_gpu_msssimf_content.py.  Built on tests/ssimf_model.py's blur / blur_t / constants:
 the clamped 2 x 2 pyramid, cs = A2 / B2 and ssim = A1 A2 / (B1 B2) per pixel and scale, fp64 means over double(W_s) * double(H_s), the
 ReLU'd weighted product with x^0 = 1, and the exact derivative: the ssimf formula per scale (its cs form on every scale but the
 last) with k_s = gOut w_s MS / m_s / (W_s H_s), accumulated from the coarsest scale down through downsample_t, the ADJOINT of the
@@ -17,6 +17,7 @@ the order of the fp64 sums, the 1-ulp reciprocal, fma contraction and the device
 """
 import numpy as np
 
+import content_classes as C
 import ssimf_model as SF
 from ssimf_model import F, STRIP_W, constants, forms, gaussian_taps  # noqa: F401  (re-exported for the tests)
 
@@ -32,6 +33,57 @@ MAX_SCALES = 8
 EMU_VALUE, EMU_MEAN, EMU_GRAD, EMU_IDENT = 1.2e-6, 1.65e-6, 2.7e-4, 3.7e-4
 VALUE_TOL, MEAN_TOL, GRAD_TOL, IDENT_TOL = 2.5e-6, 3.4e-6, 5.5e-4, 7.5e-4
 
+# Sample content (tests/content_classes.py as planes; tests/test_gpu_msssimf_content.py): a plane of 300 x 40 (W x H), 4 scales with
+# uniform weights, gOut = -0.75, and one scale-0 position per scale that is the centre of a strip column of that scale and of no other
+# (centre_scales; tests/test_msssimf_cpu.py asserts it).
+CONTENT_SHAPE, CONTENT_SCALES, CONTENT_G_OUT = (40, 300), 4, -0.75
+CONTENT_WEIGHTS = (0.25,) * 4
+CONTENT_POSITIONS = ((19, 192), (18, 128), (16, 256), (20, 296))          # (y, x) for scale 0, 1, 2, 3
+
+# The classes whose emulation leaves more than 85 % of an EMU figure there, each with its OWN (value, mean, gradient) figures: measured on
+# the CPU, rounded up, pinned from both sides by tests/test_msssimf_cpu.py.  These are measured limits of centring, not of the kernels'
+# other arithmetic: with every sample above the range the centre is 0 and nothing is centred; a step on a strip column's edge (x = 128 k) is
+# a step ON the centre sample two scales down, where the flat side is blurred at a' = -cA and E[a'^2] - mu'^2 cancels against C2; at range
+# 1e-6, C1 and C2 are of order 1e-16 under samples of order 1.  The GPU bound of such a class is its figure times the family's own ratio
+# TOL / EMU (class_bounds); every other class is held to VALUE_TOL, MEAN_TOL, GRAD_TOL and IDENT_TOL.
+# Measured: 2.452e-6, 1.151e-5, 2.086e-4; 4.960e-6, 1.993e-5, 4.280e-6; 8.378e-7, 3.123e-6, 7.537e-5.
+CLASS_EMU = {
+    "offset above the range": (2.5e-6, 1.2e-5, 2.1e-4),
+    "step on x = 256": (5.0e-6, 2.0e-5, 4.3e-6),
+    "unit data at range 1e-6": (8.4e-7, 3.2e-6, 7.6e-5),
+}
+
+
+def class_bounds(name):
+    """(value, per-scale mean, gradient, exact-gradient-0) bounds of a class of the catalogue on the GPU."""
+    if name not in CLASS_EMU:
+        return VALUE_TOL, MEAN_TOL, GRAD_TOL, IDENT_TOL
+    v, m, g = CLASS_EMU[name]
+    return v * (VALUE_TOL / EMU_VALUE), m * (MEAN_TOL / EMU_MEAN), g * (GRAD_TOL / EMU_GRAD), IDENT_TOL
+
+
+def base_pair():
+    """The catalogue's base pair on CONTENT_SHAPE: content_classes.random_pair under the seed of plane_classes."""
+    return C.random_pair(CONTENT_SHAPE, 4200)
+
+
+def planted_pair(pos, side, value):
+    """base_pair() with `value` at `pos` of A or of B."""
+    a, b = (x.copy() for x in base_pair())
+    (a if side == "A" else b)[pos] = value
+    return a, b
+
+
+def content_figures(name, got_value, got_means, got_grads, mod, r, g_out, scales, weights):
+    """What a value, (scales, 2) means and a pair of gradients leave against the float64 Model `mod`: (value error, largest per-scale mean
+    error, largest gradient error over the plane's largest float64 gradient magnitude, largest max|grad| * W * H * R / |gOut| of a gradient
+    whose exact value is 0 -- content_classes.grad_figures decides which)."""
+    mv, mm = mod.msssim(scales, weights)
+    want = mod.grad(g_out, scales, weights)
+    h, w = want[0].shape
+    figs = C.grad_figures(name, got_grads, want, None, abs(g_out) / (float(w) * float(h)), r)
+    return abs(float(got_value) - mv), float(np.abs(np.asarray(got_means, np.float64) - mm).max()), C.worst(figs, False), C.worst(figs, True)
+
 
 def scale_dims(width, height, scales):
     dims = [(width, height)]
@@ -39,6 +91,28 @@ def scale_dims(width, height, scales):
         w, h = dims[-1]
         dims.append(((w + 1) // 2, (h + 1) // 2))
     return dims
+
+
+def scale_centres(shape, s):
+    """[(y, x)] of the centre sample of every strip column of scale s of a plane of `shape` = (H, W), in that scale's coordinates:
+    content_classes.plane_centres on that scale's dimensions."""
+    w, h = scale_dims(shape[1], shape[0], s + 1)[s]
+    return C.plane_centres((h, w))
+
+
+def centre_position(shape, s, column=-1, dy=0, dx=0):
+    """The scale-0 position (y, x) of a plane of `shape` = (H, W) whose 2^s block -- the scale-0 samples that pyramid pixel (y >> s,
+    x >> s) of scale s averages -- lands on the centre of strip column `column` of scale s: the block's first sample moved on by
+    (dy, dx) inside the block and the plane."""
+    cy, cx = scale_centres(shape, s)[column]
+    y, x = (cy << s) + dy, (cx << s) + dx
+    assert 0 <= dy < (1 << s) and 0 <= dx < (1 << s) and y < shape[0] and x < shape[1], (shape, s, column, dy, dx)
+    return y, x
+
+
+def centre_scales(shape, pos, scales):
+    """The scales s < `scales` at which the pyramid pixel over scale-0 position `pos` is the centre of a strip column of scale s."""
+    return [s for s in range(scales) if (pos[0] >> s, pos[1] >> s) in scale_centres(shape, s)]
 
 
 def _taps(h, w):
@@ -170,10 +244,11 @@ class Model(object):
             self._local[key] = (SF.blur_t(d_mu_a, self.g) + 2.0 * a * t_aa + b * t_ab, SF.blur_t(d_mu_b, self.g) + 2.0 * b * t_aa + a * t_ab)
         return self._local[key]
 
-    def grad(self, g_out, scales=5, weights=None):
-        """(dLoss/da, dLoss/db) in float64 for dLoss/dMS = g_out."""
+    def grad(self, g_out, scales=5, weights=None, means=None):
+        """(dLoss/da, dLoss/db) in float64 for dLoss/dMS = g_out.  means: a (scales, 2) array that forms k_s in place of the model's
+        own (what rmgr_ssim_hip_enqueue_msssimf_grad is handed: the means of another pair, when this one's are NaN)."""
         w = check_weights(scales, weights)
-        m = self.means(scales)
+        m = self.means(scales) if means is None else np.asarray(means, np.float64).reshape(scales, 2)
         dims = [(self.planes(s)[0].shape[1], self.planes(s)[0].shape[0]) for s in range(scales)]
         k = coefficients(m, w, g_out, dims)
         ga = gb = None
@@ -309,11 +384,11 @@ class Emulation(object):
         m = self.means(scales)
         return combine(m, w), m
 
-    def grad(self, g_out, scales=5, weights=None):
-        """(float32 dLoss/da, float32 dLoss/db): k_s from the emulation's own means, rounded to float once; scale by scale
-        fp32(local + fp32(0.25 c g_{s+1}(x >> 1, y >> 1)))."""
+    def grad(self, g_out, scales=5, weights=None, means=None):
+        """(float32 dLoss/da, float32 dLoss/db): k_s from the emulation's own means (or from `means`, a (scales, 2) array), rounded to
+        float once; scale by scale fp32(local + fp32(0.25 c g_{s+1}(x >> 1, y >> 1)))."""
         w = check_weights(scales, weights)
-        m = self.means(scales)
+        m = self.means(scales) if means is None else np.asarray(means, np.float64).reshape(scales, 2)
         dims = [(self.scale(s).a.shape[1], self.scale(s).a.shape[0]) for s in range(scales)]
         with np.errstate(all="ignore"):
             k = [F(x) for x in coefficients(m, w, float(F(g_out)), dims)]

@@ -70,11 +70,16 @@ class DevicePairs(object):
         means.free()
         return v, m
 
-    def grads(self, r, g_out, scales=5, weights=None, want_a=True, want_b=True, gstep=1):
+    def grads(self, r, g_out, scales=5, weights=None, want_a=True, want_b=True, gstep=1, means=None):
         """[(dLoss/dA or None, dLoss/dB or None)] per pair, forward then backward; gradient planes with samples gstep apart, the gaps
-        checked untouched."""
+        checked untouched.  means: a float64 (n, scales, 2) array handed to the backward in place of this forward's."""
         ctx, n, h, w = self.ctx, self.n, self.h, self.w
-        _, _, means = self.forward(r, scales, weights, keep=True)
+        if means is None:
+            _, _, means = self.forward(r, scales, weights, keep=True)
+        else:
+            means = np.ascontiguousarray(means, np.float64)
+            assert means.shape == (n, scales, 2)
+            means = ctx.upload(means)
         go = ctx.upload(np.asarray(g_out, np.float32))
         fill = np.full((h, w, gstep), -777.0, np.float32)
         arrs, bufs = [None, None], [[], []]

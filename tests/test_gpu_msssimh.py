@@ -16,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+import content_classes as C
 import halfmodel as HM
 import msssimf_model as M
 import ssim_amd
@@ -101,11 +102,17 @@ class DevicePairs(object):
             return self.ctx.msssimf_device(self.params, self.n, r, scales, weights, per_scale=True)
         return self.ctx.msssimh_device(self.params, self.n, r, self.kind, scales, weights, per_scale=True)
 
-    def grads(self, r, g_out, scales=5, weights=None, want_a=True, want_b=True, gstep=1, lead=0):
+    def grads(self, r, g_out, scales=5, weights=None, want_a=True, want_b=True, gstep=1, lead=0, means=None):
         """[(dLoss/dA or None, dLoss/dB or None)] per pair, forward then backward, in the pairs' sample type; gradient planes with samples
-        gstep apart and `lead` elements into their buffer, everything but the gradient samples checked untouched."""
+        gstep apart and `lead` elements into their buffer, everything but the gradient samples checked untouched.  means: a float64
+        (n, scales, 2) array handed to the backward in place of this forward's."""
         ctx, n, h, w = self.ctx, self.n, self.h, self.w
-        _, _, means = self.forward(r, scales, weights, keep=True)
+        if means is None:
+            _, _, means = self.forward(r, scales, weights, keep=True)
+        else:
+            means = np.ascontiguousarray(means, np.float64)
+            assert means.shape == (n, scales, 2)
+            means = ctx.upload(means)
         go = ctx.upload(np.asarray(g_out, np.float32))
         mark = self.dt(-777.0) if self.kind == "f" else np.uint16(0xABCD)
         fill = np.full(lead + h * w * gstep, mark, self.dt)
@@ -145,23 +152,37 @@ class DevicePairs(object):
             b.free()
 
 
-def reference(ctx, f_pairs, enc, r, g_out, scales=5, weights=None):
+def handed_means(means, clean):
+    """What the backward is handed: None -- the forward's own means --, or, `clean` given, the forward's means with those of every pair
+    that has a NaN among them replaced by `clean`, a finite (scales, 2) array (NaN means make every k_s NaN)."""
+    if clean is None:
+        return None
+    out = np.array(means, np.float64)
+    for i in range(len(out)):
+        if np.isnan(out[i]).any():
+            out[i] = clean
+    return out
+
+
+def reference(ctx, f_pairs, enc, r, g_out, scales=5, weights=None, clean=None):
     """msssimf on the widened planes: (values, means, [(round(dA), round(dB))], the float32 gradients themselves)."""
     ref = DevicePairs(ctx, f_pairs, "f")
     v, m = ref.forward(r, scales, weights)
-    g32 = ref.grads(r, g_out, scales, weights)
+    g32 = ref.grads(r, g_out, scales, weights, means=handed_means(m, clean))
     ref.free()
     return v, m, [(HM.round_to(ga, enc), HM.round_to(gb, enc)) for ga, gb in g32], g32
 
 
-def check_pairs(ctx, u_pairs, f_pairs, enc, r, g_out, scales, weights, what):
-    """Value, means, dA alone, dB alone and both of the bit patterns against the reference.  Returns (both, float32 reference gradients)."""
-    wv, wm, want, g32 = reference(ctx, f_pairs, enc, r, g_out, scales, weights)
+def check_pairs(ctx, u_pairs, f_pairs, enc, r, g_out, scales, weights, what, clean=None):
+    """Value, means, dA alone, dB alone and both of the bit patterns against the reference.  Returns (both, float32 reference gradients).
+    clean: see handed_means; both paths are handed the same means."""
+    wv, wm, want, g32 = reference(ctx, f_pairs, enc, r, g_out, scales, weights, clean)
     dp = DevicePairs(ctx, u_pairs, enc)
     v, m = dp.forward(r, scales, weights)
-    both = dp.grads(r, g_out, scales, weights)
-    only_a = dp.grads(r, g_out, scales, weights, want_b=False)
-    only_b = dp.grads(r, g_out, scales, weights, want_a=False)
+    handed = handed_means(wm, clean)
+    both = dp.grads(r, g_out, scales, weights, means=handed)
+    only_a = dp.grads(r, g_out, scales, weights, want_b=False, means=handed)
+    only_b = dp.grads(r, g_out, scales, weights, want_a=False, means=handed)
     dp.free()
     assert same_f64(v, wv) and same_f64(m, wm), (what, enc, scales, v, wv)
     for i in range(len(u_pairs)):
@@ -409,6 +430,56 @@ def test_one_nan_sample(enc, gpu_ctx):
     assert np.array_equal(nan, np.isnan(planes["f"]))
     # and with the forward's own means: NaN coefficients, NaN everywhere, as msssimf
     check_pairs(gpu_ctx, [u], [f], enc, 1.0, [float(w * h)], 5, None, "nan")
+
+
+@ENC
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")
+def test_sample_content_and_a_bad_sample_at_the_centre_of_every_scale(enc, gpu_ctx):
+    """The catalogue of tests/content_classes.py on the grid the 16-bit encodings hold (exact=True) as planes of 300 x 40, and the eight
+    planes of tests/test_gpu_msssimf_content.py with a 1e15 (Inf in float16), a NaN or an Inf at the centre of a strip column of one
+    scale, on A or on B; 4 uniform scales.  Forward and gradients have the bits of msssimf on the widened planes.  Where the forward's
+    means are NaN the backward of both paths is handed the clean base pair's means, as in test_one_nan_sample: the gradient is then NaN
+    in part of the plane, not all of it.  The 18 classes of range 1 and the eight planes go in one launch, neighbours differing in
+    content; the other ranges one by one."""
+    shape, scales, wts = M.CONTENT_SHAPE, M.CONTENT_SCALES, M.CONTENT_WEIGHTS
+    h, w = shape
+    classes = C.plane_classes(shape, exact=True)
+    base = tuple((np.round(x * np.float32(128)) / np.float32(128)).astype(np.float32) for x in M.base_pair())
+    assert np.array_equal(C.named(classes, "negative")[1], -base[0]) and np.array_equal(C.named(classes, "negative")[2], -base[1])
+    planted = []
+    for s, pos in enumerate(M.CONTENT_POSITIONS):
+        assert M.centre_scales(shape, pos, scales) == [s]
+        for k, side in enumerate("AB"):
+            a, b = base[0].copy(), base[1].copy()
+            (a if side == "A" else b)[pos] = (C.HUGE, np.nan, np.inf)[(2 * s + k) % 3]
+            planted.append(("centre of scale %d (%s)" % (s, side), a, b))
+    unit = [(c[0], c[1], c[2]) for c in classes if c[3] == 1.0]
+    entries = [e for pair in zip(unit, planted) for e in pair] + unit[len(planted):]
+    assert len(entries) == 26
+    (cu, cf) = encoded_pair(base[0], base[1], enc)
+    assert np.array_equal(cf[0], base[0]) and np.array_equal(cf[1], base[1])                     # the grid is exact in both encodings
+    dp = DevicePairs(gpu_ctx, [cf], "f")
+    _, clean = dp.forward(1.0, scales, wts)
+    dp.free()
+    clean = clean[0]
+    assert np.all(np.isfinite(clean))
+    enc_pairs = [encoded_pair(a, b, enc) for _, a, b in entries]
+    us, fs = [u for u, _ in enc_pairs], [f for _, f in enc_pairs]
+    huge = HM.widen(HM.round_to(np.full(1, C.HUGE, np.float32), enc), enc)[0]
+    assert np.isinf(huge) if enc == HM.F16 else (np.isfinite(huge) and huge > 9e14)
+    g_out = [(-0.75 + 0.25 * i) * w * h for i in range(len(entries))]                            # differs per pair; one is 0
+    both, g32 = check_pairs(gpu_ctx, us, fs, enc, 1.0, g_out, scales, wts, "content", clean=clean)
+    partly = 0
+    for i, (name, _, _) in enumerate(entries):
+        if g_out[i] != 0 and not np.all(np.isfinite(fs[i][0]) & np.isfinite(fs[i][1])):
+            nan = HM.is_nan(both[i][0], enc)
+            assert nan.any() and not nan.all() and np.array_equal(nan, np.isnan(g32[i][0])), (name, enc)
+            partly += 1
+    assert partly >= 7, partly
+    for name, a, b, r, _ in classes:
+        if r != 1.0:
+            u, f = encoded_pair(a, b, enc)
+            check_pairs(gpu_ctx, [u], [f], enc, r, [-0.75 * w * h * r], scales, wts, name, clean=clean)
 
 
 def test_float16_overflows_to_inf_exactly_where_the_rounded_float32_gradient_does(gpu_ctx, manifest):
