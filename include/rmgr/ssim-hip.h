@@ -32,6 +32,9 @@
  *       of float16 / bfloat16 images and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssimf_map_grad, rmgr_ssim_hip_enqueue_ssimh_map_grad   gradient of the SSIM MAP for a per-pixel upstream
  *                                      gradient: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_ssimh_win, rmgr_ssim_hip_compute_ssimh_win_device / _host, rmgr_ssim_hip_enqueue_ssimh_win_grad,
+ *   rmgr_ssim_hip_enqueue_ssimh_win_map_grad   the float16 / bfloat16 entries under a caller-chosen window (size, sigma, box): no
+ *                                      reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim3f, rmgr_ssim_hip_compute_ssim3f_device / _host, rmgr_ssim_hip_enqueue_ssim3f_grad   SSIM of float32
  *                                      VOLUMES (three-dimensional window) and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim3f_map_grad      gradient of the 3-D SSIM MAP for a per-voxel upstream gradient: no reference
@@ -759,8 +762,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* ctx, rm
  * Arguments, EINVAL / ENODEV rules, sub-batches, scratch and stream behaviour are those of the entry without _win.  Additional EINVAL,
  * checked before any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
  *
- * Follow-up, not in this interface: float16 / bfloat16 samples (the ssimh entries) and multi-scale SSIM (the msssim, msssimf and msssimh
- * entries) keep the fixed window {11, GAUSSIAN, 1.5f}.
+ * float16 / bfloat16 samples under a caller-chosen window: the ssimh_win entries, below.  Follow-up, not in this interface: multi-scale
+ * SSIM (the msssim, msssimf and msssimh entries) keeps the fixed window {11, GAUSSIAN, 1.5f}.
  */
 enum { RMGR_SSIM_HIP_WINDOW_GAUSSIAN = 0, RMGR_SSIM_HIP_WINDOW_UNIFORM = 1 };
 typedef struct rmgr_ssim_hip_Window {
@@ -779,6 +782,55 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_grad(rmgr_ssim_hip_Context* ctx, rm
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                                       float dataRange, const rmgr_ssim_hip_Window* window, const rmgr_ssim_hip_GradOutF* gradOutMaps,
                                                       const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
+
+/*
+ * SSIM of float16 / bfloat16 samples under a caller-chosen WINDOW: the five entries of the 16-bit family -- _enqueue_ssimh,
+ * _compute_ssimh_device, _compute_ssimh_host, _enqueue_ssimh_grad, _enqueue_ssimh_map_grad -- with one more argument, `window`, after
+ * dataRange: the rmgr_ssim_hip_Window of the float32 _win entries, unchanged.  What a 2-D model trained under mixed precision needs when
+ * its loss is the 3 x 3 box of monodepth-style photometric losses, skimage's 7 x 7 box or another size or sigma: the 16-bit tensors are
+ * read as they are stored, without float32 copies and without a float32 gradient.  No reference counterpart.  Additions only:
+ * RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ * It is the definition of rmgr_ssim_hip_enqueue_ssimf_win -- and of _enqueue_ssimf_win_grad and _enqueue_ssimf_win_map_grad --, word for
+ * word, on samples widened to float32 exactly as the ssimh entries define widening:
+ *   Window   size 3, 5, 7, 9 or 11 taps on both axes, GAUSSIAN of any finite sigma > 0 or UNIFORM; the taps of the float32 _win entries,
+ *            bit for bit.  A NULL window means {11, GAUSSIAN, 1.5f}.
+ *   Value    the value, the float32 map and every per-image fp64 sum have the BITS rmgr_ssim_hip_enqueue_ssimf_win gives on the widened
+ *            planes under the same window.
+ *   Gradient  each gradient pixel is the float32 value _enqueue_ssimf_win_grad / _enqueue_ssimf_win_map_grad would store for the widened
+ *            planes under the same window, rounded ONCE, to nearest-even, into the inputs' encoding (float16: subnormals are kept,
+ *            overflow gives Inf; NaN stays NaN in both encodings).  gradOutDevice and rmgr_ssim_hip_GradOutF stay float32: a loss scale
+ *            arrives before the single rounding.
+ *   Identity with the fixed-window entries  a NULL window and {11, GAUSSIAN, 1.5f} give the BITS of the ssimh entries without _win:
+ *            value, map, sums and both gradient forms.
+ *   Identity of the two gradient forms  a gMap whose every element is float(double(gOut[i]) / (double(W) * double(H))) gives the BITS of
+ *            _enqueue_ssimh_win_grad for gOut[i] under the same window.
+ *   Everything else is ssimf_win's: determinism (alone or anywhere in a batch, at any strip height, after any sub-batch split, as any
+ *            view), the clamped borders, the centre of every 128-column strip column, and the reach of a NaN sample ((2R + 1)^2 map
+ *            pixels, (4R + 1)^2 gradient pixels, clipped) and of a NaN in gMap ((2R + 1)^2).
+ *
+ * Arguments, strides (in 16-bit samples; the map and gMap in floats), EINVAL / ENODEV rules, sub-batches, scratch and stream behaviour are
+ * those of the ssimh entry without _win.  Additional EINVAL, checked after that entry's sample type, data range and pairs, before its
+ * upstream and gradient planes and before any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not
+ * finite or not > 0.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                             rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                             double* sumsDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_win_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                    rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                    float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_win_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                  float* ssim) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                  const float* gradOutDevice, const rmgr_ssim_hip_GradH* gradA,
+                                                  const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win_map_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                      rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                      const rmgr_ssim_hip_GradOutF* gradOutMaps, const rmgr_ssim_hip_GradH* gradA,
+                                                      const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
 
 /*
  * SSIM of `count` pairs of float32 VOLUMES of one size under a THREE-DIMENSIONAL window, and its gradient (MRI / CT reconstruction,

@@ -223,6 +223,8 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssimf_map_grad", "rmgr_ssim_hip_enqueue_ssimh_map_grad",
     "rmgr_ssim_hip_enqueue_ssimf_win", "rmgr_ssim_hip_compute_ssimf_win_device", "rmgr_ssim_hip_compute_ssimf_win_host",
     "rmgr_ssim_hip_enqueue_ssimf_win_grad", "rmgr_ssim_hip_enqueue_ssimf_win_map_grad",
+    "rmgr_ssim_hip_enqueue_ssimh_win", "rmgr_ssim_hip_compute_ssimh_win_device", "rmgr_ssim_hip_compute_ssimh_win_host",
+    "rmgr_ssim_hip_enqueue_ssimh_win_grad", "rmgr_ssim_hip_enqueue_ssimh_win_map_grad",
     "rmgr_ssim_hip_enqueue_msssimh", "rmgr_ssim_hip_compute_msssimh_device", "rmgr_ssim_hip_compute_msssimh_host", "rmgr_ssim_hip_enqueue_msssimh_grad",
     "rmgr_ssim_hip_enqueue_ssim3f", "rmgr_ssim_hip_compute_ssim3f_device", "rmgr_ssim_hip_compute_ssim3f_host", "rmgr_ssim_hip_enqueue_ssim3f_grad",
     "rmgr_ssim_hip_enqueue_ssim3f_map_grad",
@@ -334,6 +336,11 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_ssim3h_host": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_enqueue_ssim3h_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, vp, ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
         "rmgr_ssim_hip_enqueue_ssim3h_map_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, ctypes.POINTER(GradOut3F), ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
+        "rmgr_ssim_hip_enqueue_ssimh_win": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, vp],
+        "rmgr_ssim_hip_compute_ssimh_win_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_compute_ssimh_win_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
+        "rmgr_ssim_hip_enqueue_ssimh_win_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
+        "rmgr_ssim_hip_enqueue_ssimh_win_map_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, ctypes.POINTER(GradOutF), ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
         "rmgr_ssim_hip_enqueue_ssim3h_win": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, vp],
         "rmgr_ssim_hip_compute_ssim3h_win_device": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
         "rmgr_ssim_hip_compute_ssim3h_win_host": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, ctypes.POINTER(ctypes.c_float)],
@@ -808,23 +815,37 @@ def _h_pair(a, b, sample_type):
     return a, b, ta
 
 
-def compute_ssimh(a, b, data_range, sample_type=None, want_map=False, ctx=None):
+def _ssimh_host(handle, count, params, code, data_range, window, out):
+    """rmgr_ssim_hip_compute_ssimh_host, or -- a window given -- rmgr_ssim_hip_compute_ssimh_win_host."""
+    lib = load_library()
+    if window is None:
+        _check("rmgr_ssim_hip_compute_ssimh_host", lib.rmgr_ssim_hip_compute_ssimh_host(handle, count, params, code, data_range, out))
+    else:
+        _check("rmgr_ssim_hip_compute_ssimh_win_host", lib.rmgr_ssim_hip_compute_ssimh_win_host(
+            handle, count, params, code, data_range, _window_ref(window), out))
+
+
+def compute_ssimh(a, b, data_range, sample_type=None, want_map=False, ctx=None, window=None):
     """SSIM of two H x W host arrays of float16 or bfloat16 samples at `data_range` (any strides numpy can express, negative ones
-    included) through rmgr_ssim_hip_compute_ssimh_host.  np.float16 arrays select float16; np.uint16 arrays carry bit patterns and
-    need sample_type="bfloat16" or "float16".  Returns (float32 value, H x W float32 map or None)."""
+    included) through rmgr_ssim_hip_compute_ssimh_host; window (a Window, make_window): through rmgr_ssim_hip_compute_ssimh_win_host
+    under that window.  np.float16 arrays select float16; np.uint16 arrays carry bit patterns and need sample_type="bfloat16" or
+    "float16".  Returns (float32 value, H x W float32 map or None)."""
+    if window is not None:
+        _window_ref(window)
     a, b, code = _h_pair(a, b, sample_type)
     h, w = a.shape
     m = np.empty((h, w), np.float32) if want_map else None
     params = (Params16 * 1)()
     params[0] = _params16_of(a, b, m.ctypes.data if want_map else None)
     out = (ctypes.c_float * 1)()
-    _check("rmgr_ssim_hip_compute_ssimh_host", load_library().rmgr_ssim_hip_compute_ssimh_host(
-        ctx.handle if ctx is not None else None, 1, params, code, data_range, out))
+    _ssimh_host(ctx.handle if ctx is not None else None, 1, params, code, data_range, window, out)
     return np.float32(out[0]), m
 
 
-def compute_ssimh_batch(pairs, data_range, sample_type=None, ctx=None):
+def compute_ssimh_batch(pairs, data_range, sample_type=None, ctx=None, window=None):
     """compute_ssimh() of many host pairs of one size and one sample type in one call (no maps): a float32 array."""
+    if window is not None:
+        _window_ref(window)
     pairs = [_h_pair(a, b, sample_type) for a, b in pairs]
     n = len(pairs)
     codes = set(t for _, _, t in pairs)
@@ -835,8 +856,7 @@ def compute_ssimh_batch(pairs, data_range, sample_type=None, ctx=None):
     for i, (a, b, _) in enumerate(pairs):
         params[i] = _params16_of(a, b)
     out = (ctypes.c_float * max(n, 1))()
-    _check("rmgr_ssim_hip_compute_ssimh_host", load_library().rmgr_ssim_hip_compute_ssimh_host(
-        ctx.handle if ctx is not None else None, n, params, code, data_range, out))
+    _ssimh_host(ctx.handle if ctx is not None else None, n, params, code, data_range, window, out)
     return np.array(out[:n], np.float32)
 
 
@@ -1249,12 +1269,19 @@ class Context(object):
             _check("rmgr_ssim_hip_enqueue_ssim3f_win_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3f_win_grad(
                 self.handle, count, params_array, data_range, _window_ref(window), grad_out_dev_ptr, grad_a, grad_b))
 
-    def ssimh_device(self, params_array, count, data_range, sample_type):
-        """SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_ssimh_device: a
-        float32 array."""
+    # The 16-bit family takes window=None (the engine's 11-tap Gaussian of sigma 1.5: the entry without _win) or a Window (make_window):
+    # the _win entry under that window.
+
+    def ssimh_device(self, params_array, count, data_range, sample_type, window=None):
+        """SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_ssimh_device
+        (window: _ssimh_win_device): a float32 array."""
         out = (ctypes.c_float * max(count, 1))()
-        _check("rmgr_ssim_hip_compute_ssimh_device", self.lib.rmgr_ssim_hip_compute_ssimh_device(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, out))
+        if window is None:
+            _check("rmgr_ssim_hip_compute_ssimh_device", self.lib.rmgr_ssim_hip_compute_ssimh_device(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, out))
+        else:
+            _check("rmgr_ssim_hip_compute_ssimh_win_device", self.lib.rmgr_ssim_hip_compute_ssimh_win_device(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), out))
         return np.array(out[:count], np.float32)
 
     def enqueue_ssim3f_map_grad(self, params_array, count, data_range, grad_out_maps, grad_a=None, grad_b=None, window=None):
@@ -1314,16 +1341,25 @@ class Context(object):
             _check("rmgr_ssim_hip_enqueue_ssim3h_win_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssim3h_win_map_grad(
                 self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), grad_out_maps, grad_a, grad_b))
 
-    def enqueue_ssimh(self, params_array, count, data_range, sample_type, sums_dev_ptr):
-        """rmgr_ssim_hip_enqueue_ssimh: per-pair fp64 sums into device memory, asynchronously on the context's stream."""
-        _check("rmgr_ssim_hip_enqueue_ssimh", self.lib.rmgr_ssim_hip_enqueue_ssimh(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, sums_dev_ptr))
+    def enqueue_ssimh(self, params_array, count, data_range, sample_type, sums_dev_ptr, window=None):
+        """rmgr_ssim_hip_enqueue_ssimh (window: _ssimh_win): per-pair fp64 sums into device memory, asynchronously on the context's stream."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssimh", self.lib.rmgr_ssim_hip_enqueue_ssimh(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, sums_dev_ptr))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssimh_win", self.lib.rmgr_ssim_hip_enqueue_ssimh_win(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), sums_dev_ptr))
 
-    def enqueue_ssimh_grad(self, params_array, count, data_range, sample_type, grad_out_dev_ptr, grad_a=None, grad_b=None):
-        """rmgr_ssim_hip_enqueue_ssimh_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs into the 16-bit planes the GradH
-        arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values; asynchronous, no host synchronisation."""
-        _check("rmgr_ssim_hip_enqueue_ssimh_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_grad(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_dev_ptr, grad_a, grad_b))
+    def enqueue_ssimh_grad(self, params_array, count, data_range, sample_type, grad_out_dev_ptr, grad_a=None, grad_b=None, window=None):
+        """rmgr_ssim_hip_enqueue_ssimh_grad (window: _ssimh_win_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs into the
+        16-bit planes the GradH arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values; asynchronous, no host
+        synchronisation."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssimh_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_dev_ptr, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssimh_win_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_win_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), grad_out_dev_ptr, grad_a, grad_b))
 
     def enqueue_ssimf_map_grad(self, params_array, count, data_range, grad_out_maps, grad_a=None, grad_b=None, window=None):
         """rmgr_ssim_hip_enqueue_ssimf_map_grad (window: _ssimf_win_map_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs for a per-pixel upstream
@@ -1336,11 +1372,15 @@ class Context(object):
             _check("rmgr_ssim_hip_enqueue_ssimf_win_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimf_win_map_grad(
                 self.handle, count, params_array, data_range, _window_ref(window), grad_out_maps, grad_a, grad_b))
 
-    def enqueue_ssimh_map_grad(self, params_array, count, data_range, sample_type, grad_out_maps, grad_a=None, grad_b=None):
-        """rmgr_ssim_hip_enqueue_ssimh_map_grad: the same for float16 / bfloat16 pairs (a Params16 array); the GradH planes receive the
-        float32 value rounded once into the inputs' encoding; the GradOutF planes stay float32."""
-        _check("rmgr_ssim_hip_enqueue_ssimh_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_map_grad(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_maps, grad_a, grad_b))
+    def enqueue_ssimh_map_grad(self, params_array, count, data_range, sample_type, grad_out_maps, grad_a=None, grad_b=None, window=None):
+        """rmgr_ssim_hip_enqueue_ssimh_map_grad (window: _ssimh_win_map_grad): the same for float16 / bfloat16 pairs (a Params16 array); the
+        GradH planes receive the float32 value rounded once into the inputs' encoding; the GradOutF planes stay float32."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_ssimh_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_map_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, grad_out_maps, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_ssimh_win_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_win_map_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), grad_out_maps, grad_a, grad_b))
 
     def msssimf_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False):
         """MS-SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_msssimf_device: a float32

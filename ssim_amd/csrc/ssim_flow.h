@@ -22,7 +22,7 @@ inline bool valid_range(float r) { return r > 0.0f && std::isfinite(r); }
 inline int sample_type(uint32_t sampleType) { return sampleType == RMGR_SSIM_HIP_SAMPLE_BF16 ? ssim_hip::kSHTypeBF16 : ssim_hip::kSHTypeF16; }
 
 // The window of a launch: its radius and taps, centre first (ssimk_kernels.h: window_taps).  Radius 5 runs on the 11-tap kernels of a
-// family, the smaller ones on its ssimk / ssim3k / ssim3hk kernels.
+// family, the smaller ones on its ssimk / ssimhk / ssim3k / ssim3hk kernels.
 struct Window {
     uint32_t radius;
     float    gf[ssim_hip::kSKMaxRadius + 1];

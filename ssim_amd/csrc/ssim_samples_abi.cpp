@@ -2,7 +2,7 @@
 // 9- to 16-bit integers (ssim16), of float32 (ssimf) and of float16 / bfloat16 samples (ssimh), the gradients of the latter two for a
 // scalar and for a per-pixel upstream gradient (ssimw), and multi-scale SSIM of float32 (msssimf) and of float16 / bfloat16 samples
 // (msssimh) with its gradient.  The definitions are in include/rmgr/ssim-hip.h, the kernels in ssim16_ / ssimf_ / ssimh_ / ssimw_ /
-// ssimk_ / msssimf_ / msssimh_kernels.hip.
+// ssimk_ / ssimhk_ / msssimf_ / msssimh_kernels.hip.
 //
 // The three single-scale families differ in their sample type and in what a launch is told (bit depth; data range; encoding and data
 // range); each is described once by a small struct (Family16 / FamilyF / FamilyH) and the host flow -- validation, sub-batches, staging
@@ -17,6 +17,7 @@
 // the launch that read its ring slot kSfSlots enqueues ago.
 #include "ssim_flow.h"
 #include "msssimh_kernels.h"
+#include "ssimhk_kernels.h"
 #include "ssimw_kernels.h"
 
 using namespace ssim_host;
@@ -85,8 +86,15 @@ struct FamilyH {
     static bool fits_narrow(const Desc& d) { return ssim_hip::fitsh_narrow(d); }
     int type;           // kSHTypeF16 / kSHTypeBF16
     float range;
+    Window win;
+    // as FamilyF::launch: geo is planh()'s, a smaller window re-plans its strips
     hipError_t launch(rmgr_ssim_hip_Context* c, const Geometry& geo, const Desc* dev, bool map, bool unit, bool wide, double* sums) const
-    { return ssim_hip::launch_ssimh(geo, dev, type, map, unit, wide, range, c->xcd_count, c->sf_partials, sums, c->stream); }
+    {
+        if (win.radius == 5)
+            return ssim_hip::launch_ssimh(geo, dev, type, map, unit, wide, range, win.gf, c->xcd_count, c->sf_partials, sums, c->stream);
+        return ssim_hip::launch_ssimhk(win.radius, win.gf, ssim_hip::plank(win.radius, geo.width, geo.height, geo.count, c->cu_count), dev, type, map,
+                                       wide, range, c->xcd_count, c->sf_partials, sums, c->stream);
+    }
 };
 
 // ---- validation, before any device is touched -----------------------------------------------------------------------------------------------
@@ -701,6 +709,41 @@ int ssimf_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_h
         });
 }
 
+// ---- SSIM of float16 / bfloat16 samples: the same, with the encoding as one more input ---------------------------------------------------------
+
+int ssimh_enqueue_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t sampleType, float dataRange,
+                        const Window& win, double* sumsDevice)
+{
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return enqueue_all(c, FamilyH{sample_type(sampleType), dataRange, win}, count, params, sumsDevice);
+}
+
+int ssimh_device_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t sampleType, float dataRange,
+                       const Window& win, float* ssim)
+{
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    return blocking(c, FamilyH{sample_type(sampleType), dataRange, win}, count, params, ssim, false);
+}
+
+int ssimh_grad_entry(rmgr_ssim_hip_Context* c, uint32_t count, const rmgr_ssim_hip_Params16* params, uint32_t sampleType, float dataRange,
+                     const Window& win, const float* gradOutDevice, const rmgr_ssim_hip_GradOutF* gradOutMaps, const rmgr_ssim_hip_GradH* gradA,
+                     const rmgr_ssim_hip_GradH* gradB)
+{
+    if (!c) return EINVAL;
+    USE_DEVICE(c);
+    const uint32_t W = params[0].width, H = params[0].height;
+    const int which = grad_which(gradA, gradB), type = sample_type(sampleType);
+    return enqueue_grads<FamilyH>(c, count, params, gradA, gradB, gradOutMaps,
+        [&](uint32_t n, uint32_t i0, const PairHDesc* pd, const GradHDesc* gd, const GradOutFDesc* od) {
+            const float* g_out = gradOutMaps ? NULL : gradOutDevice + i0;
+            if (win.radius != 5) return ssim_hip::launch_ssimhk_grad(win.radius, win.gf, W, H, n, pd, gd, type, g_out, gradOutMaps ? od : NULL, dataRange, which, c->stream);
+            if (gradOutMaps)     return ssim_hip::launch_ssimw_grad_h(W, H, n, pd, gd, type, od, dataRange, win.gf, which, c->stream);
+            return ssim_hip::launch_ssimh_grad(W, H, n, pd, gd, type, g_out, dataRange, win.gf, which, c->stream);
+        });
+}
+
 } // namespace
 
 extern "C" {
@@ -808,32 +851,57 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimf_win_grad(rmgr_ssim_hip_Context* c, rmgr
 }
 
 // ---- SSIM of float16 / bfloat16 samples and its gradient: the ssimf flow with 2-byte samples ---------------------------------------------------
+// As for float32 samples, every entry exists under the engine's window and, _win, under the caller's.
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
                                          rmgr_uint32_t sampleType, float dataRange, double* sumsDevice) RMGR_NOEXCEPT
 {
     const int rc = ssimh_validate(count, params, sampleType, dataRange, sumsDevice);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return enqueue_all(c, FamilyH{sample_type(sampleType), dataRange}, count, params, sumsDevice);
+    return rc ? rc : ssimh_enqueue_entry(c, count, params, sampleType, dataRange, default_window(), sumsDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                             rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                             double* sumsDevice) RMGR_NOEXCEPT
+{
+    Window win;
+    int rc = ssimh_validate(count, params, sampleType, dataRange, sumsDevice);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    return ssimh_enqueue_entry(c, count, params, sampleType, dataRange, win, sumsDevice);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssimh_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
                                                 rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
 {
     const int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
-    if (rc) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    return blocking(c, FamilyH{sample_type(sampleType), dataRange}, count, params, ssim, false);
+    return rc ? rc : ssimh_device_entry(c, count, params, sampleType, dataRange, default_window(), ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                    rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                    float* ssim) RMGR_NOEXCEPT
+{
+    Window win;
+    int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    return ssimh_device_entry(c, count, params, sampleType, dataRange, win, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_compute_ssimh_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
                                               rmgr_uint32_t sampleType, float dataRange, float* ssim) RMGR_NOEXCEPT
 {
     const int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
-    return rc ? rc : blocking_host(c, FamilyH{sample_type(sampleType), dataRange}, count, params, ssim);
+    return rc ? rc : blocking_host(c, FamilyH{sample_type(sampleType), dataRange, default_window()}, count, params, ssim);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_ssimh_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                  float* ssim) RMGR_NOEXCEPT
+{
+    Window win;
+    int rc = ssimh_validate(count, params, sampleType, dataRange, ssim);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    return blocking_host(c, FamilyH{sample_type(sampleType), dataRange, win}, count, params, ssim);
 }
 
 rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
@@ -843,14 +911,19 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_grad(rmgr_ssim_hip_Context* c, rmgr_uin
     int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutDevice);
     if (rc) return rc;
     if ((rc = validate_grads(count, gradA, gradB))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = grad_which(gradA, gradB), type = sample_type(sampleType);
-    return enqueue_grads<FamilyH>(c, count, params, gradA, gradB, NULL,
-        [&](uint32_t n, uint32_t i0, const PairHDesc* pd, const GradHDesc* gd, const GradOutFDesc*) {
-            return ssim_hip::launch_ssimh_grad(W, H, n, pd, gd, type, gradOutDevice + i0, dataRange, which, c->stream);
-        });
+    return ssimh_grad_entry(c, count, params, sampleType, dataRange, default_window(), gradOutDevice, NULL, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                  const float* gradOutDevice, const rmgr_ssim_hip_GradH* gradA,
+                                                  const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
+{
+    Window win;
+    int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutDevice);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    return ssimh_grad_entry(c, count, params, sampleType, dataRange, win, gradOutDevice, NULL, gradA, gradB);
 }
 
 // ---- gradient of the SSIM map for a per-pixel upstream gradient: the _grad flow with one more descriptor per pair, the gMap plane ----------------
@@ -886,14 +959,20 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* c, rmgr
     if (rc) return rc;
     if ((rc = validate_grad_maps(count, gradOutMaps))) return rc;
     if ((rc = validate_grads(count, gradA, gradB))) return rc;
-    if (!c) return EINVAL;
-    USE_DEVICE(c);
-    const uint32_t W = params[0].width, H = params[0].height;
-    const int which = grad_which(gradA, gradB), type = sample_type(sampleType);
-    return enqueue_grads<FamilyH>(c, count, params, gradA, gradB, gradOutMaps,
-        [&](uint32_t n, uint32_t, const PairHDesc* pd, const GradHDesc* gd, const GradOutFDesc* od) {
-            return ssim_hip::launch_ssimw_grad_h(W, H, n, pd, gd, type, od, dataRange, which, c->stream);
-        });
+    return ssimh_grad_entry(c, count, params, sampleType, dataRange, default_window(), NULL, gradOutMaps, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win_map_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                      rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                      const rmgr_ssim_hip_GradOutF* gradOutMaps, const rmgr_ssim_hip_GradH* gradA,
+                                                      const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
+{
+    Window win;
+    int rc = ssimh_validate(count, params, sampleType, dataRange, gradOutMaps);
+    if (rc || (rc = window_validate(window, win))) return rc;
+    if ((rc = validate_grad_maps(count, gradOutMaps))) return rc;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    return ssimh_grad_entry(c, count, params, sampleType, dataRange, win, NULL, gradOutMaps, gradA, gradB);
 }
 
 // ---- multi-scale SSIM of float32 samples and its gradient -------------------------------------------------------------------------------------

@@ -57,10 +57,11 @@ GeometryH planh(uint32_t width, uint32_t height, uint32_t count, int cu_count);
 //   map_unit    every map has ssimStep == 1 and the width is even (8-byte map stores)
 //   wide        some pair fails fitsh_narrow()
 //   data_range  R > 0, finite: sets C1 and C2, and bounds the centre
+//   taps        the window's six taps, centre first, as launch_ssimf (ssimk_kernels.h: window_taps at radius 5)
 //   partials    geo.count * geo.cells_per_image() doubles of device scratch
 //   sums        geo.count doubles (device): each image's fp64 sum of its per-pixel values, in a fixed order
 hipError_t launch_ssimh(const GeometryH& geo, const PairHDesc* descs_dev, int type, bool map, bool map_unit, bool wide, float data_range,
-                        int xcd_count, double* partials, double* sums, hipStream_t stream);
+                        const float (&taps)[6], int xcd_count, double* partials, double* sums, hipStream_t stream);
 
 // Enqueues the gradient kernel of `count` pairs of width x height on `stream`: one fused launch that recomputes the statistics and
 // rounds each gradient pixel once, to nearest-even, into the samples' encoding.
@@ -70,7 +71,7 @@ hipError_t launch_ssimh(const GeometryH& geo, const PairHDesc* descs_dev, int ty
 //   which       1: dLoss/dA into ga; 2: dLoss/dB into gb; 3: both, in one pass, each with the bits it has alone
 // Gradient planes are written, not accumulated; every pixel by exactly one work-item.
 hipError_t launch_ssimh_grad(uint32_t width, uint32_t height, uint32_t count, const PairHDesc* descs_dev, const GradHDesc* grads_dev,
-                             int type, const float* g_out, float data_range, int which, hipStream_t stream);
+                             int type, const float* g_out, float data_range, const float (&taps)[6], int which, hipStream_t stream);
 
 } // namespace ssim_hip
 

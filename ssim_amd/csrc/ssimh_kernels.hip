@@ -33,12 +33,10 @@ uint32_t ssimh_max_count(uint32_t width, uint32_t height) { return ssimf_max_cou
 GeometryH planh(uint32_t width, uint32_t height, uint32_t count, int cu_count) { return plan_strips(width, height, count, cu_count, 10); }
 
 hipError_t launch_ssimh(const GeometryH& geo, const PairHDesc* descs_dev, int type, bool map, bool map_unit, bool wide, float data_range,
-                        int xcd_count, double* partials, double* sums, hipStream_t stream)
+                        const float (&taps)[6], int xcd_count, double* partials, double* sums, hipStream_t stream)
 {
     if (geo.count == 0) return hipSuccess;
     if (!valid_range(data_range) || geo.count > ssimh_max_count(geo.width, geo.height) || !valid_type(type)) return hipErrorInvalidValue;
-    float taps[MAXR + 1];
-    default_taps(taps);
     const Strip2Args<PairHDesc> ka = fill_strip(geo, descs_dev, data_range, taps, xcd_count, partials);
     pick_type(type, [&](auto t) {
         pick_map(map, map_unit, wide, [&](auto m, auto w) {
@@ -52,12 +50,10 @@ hipError_t launch_ssimh(const GeometryH& geo, const PairHDesc* descs_dev, int ty
 }
 
 hipError_t launch_ssimh_grad(uint32_t width, uint32_t height, uint32_t count, const PairHDesc* descs_dev, const GradHDesc* grads_dev,
-                             int type, const float* g_out, float data_range, int which, hipStream_t stream)
+                             int type, const float* g_out, float data_range, const float (&taps)[6], int which, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
     if (!valid_range(data_range) || which < 1 || which > 3 || count > ssimh_max_count(width, height) || !valid_type(type)) return hipErrorInvalidValue;
-    float taps[MAXR + 1];
-    default_taps(taps);
     Grad2Args<PairHDesc, GradHDesc> ka = fill_grad(width, height, descs_dev, grads_dev, data_range, 5, taps);
     ka.g_out = g_out;
     pick_type(type, [&](auto t) {

@@ -22,13 +22,13 @@ struct GradOutFDesc {
 //   grads_dev   count GradFDesc / GradHDesc in device memory
 //   gouts_dev   count GradOutFDesc in device memory
 //   type        (16-bit samples) kSHTypeF16 or kSHTypeBF16
-//   taps        (float32 samples) the window's six taps, centre first, as launch_ssimf; 16-bit samples keep the Gaussian of sigma 1.5
+//   taps        the window's six taps, centre first, as launch_ssimf
 //   which       1: dLoss/dA into ga; 2: dLoss/dB into gb; 3: both, in one pass, each with the bits it has alone
 // count <= ssimf_max_count(width, height).  Gradient planes are written, not accumulated; every pixel by exactly one work-item.
 hipError_t launch_ssimw_grad_f(uint32_t width, uint32_t height, uint32_t count, const PairFDesc* descs_dev, const GradFDesc* grads_dev,
                                const GradOutFDesc* gouts_dev, float data_range, const float (&taps)[6], int which, hipStream_t stream);
 hipError_t launch_ssimw_grad_h(uint32_t width, uint32_t height, uint32_t count, const PairHDesc* descs_dev, const GradHDesc* grads_dev,
-                               int type, const GradOutFDesc* gouts_dev, float data_range, int which, hipStream_t stream);
+                               int type, const GradOutFDesc* gouts_dev, float data_range, const float (&taps)[6], int which, hipStream_t stream);
 
 } // namespace ssim_hip
 

@@ -48,10 +48,8 @@ hipError_t launch_ssimw_grad_f(uint32_t width, uint32_t height, uint32_t count, 
 }
 
 hipError_t launch_ssimw_grad_h(uint32_t width, uint32_t height, uint32_t count, const PairHDesc* descs_dev, const GradHDesc* grads_dev,
-                               int type, const GradOutFDesc* gouts_dev, float data_range, int which, hipStream_t stream)
+                               int type, const GradOutFDesc* gouts_dev, float data_range, const float (&taps)[6], int which, hipStream_t stream)
 {
-    float taps[MAXR + 1];
-    default_taps(taps);           // 16-bit samples: the fixed window
     if (type == kSHTypeBF16) return launch<kSWTypeBF16>(width, height, count, descs_dev, grads_dev, gouts_dev, data_range, taps, which, stream);
     if (type == kSHTypeF16)  return launch<kSWTypeF16>(width, height, count, descs_dev, grads_dev, gouts_dev, data_range, taps, which, stream);
     return hipErrorInvalidValue;

@@ -1,7 +1,7 @@
 """SSIM and multi-scale SSIM of float32, float16 and bfloat16 tensors as differentiable PyTorch operations, on the library's fused gfx950
 kernels.
 
-    from ssim_amd.torch_ops import ssim, ssim_map, SSIMLoss, ms_ssim, ms_ssim_amp, MSSSIMLoss
+    from ssim_amd.torch_ops import ssim, ssim_map, ssim_amp, ssim_map_amp, SSIMLoss, ms_ssim, ms_ssim_amp, MSSSIMLoss
     loss = 0.8 * (x - y).abs().mean() + 0.2 * SSIMLoss()(x, y)      # x, y: (N, C, H, W) float32 on the GPU
     loss = 0.16 * (x - y).abs().mean() + 0.84 * MSSSIMLoss()(x, y)
     loss.backward()
@@ -44,11 +44,23 @@ ignores win_sigma): pytorch-msssim's win_size / win_sigma, torchmetrics' and piq
 filter_sigma, kornia's window_size, skimage's 7 x 7 box, the 3 x 3 box of monodepth-style losses.  The defaults (11, 1.5, "gaussian") take
 exactly the path above; anything else runs the _win entries of the float32 family (rmgr_ssim_hip_enqueue_ssimf_win, _ssimf_win_grad,
 _ssimf_win_map_grad), the small windows on kernels of their own radius.  Edges are clamped for every window: where monodepth-style code
-reflects, the interior is identical and the outermost (win_size - 1) / 2 pixels differ.  The 2-D functions with float16 / bfloat16
-tensors, and ms_ssim, keep the fixed window for now: a non-default window with 16-bit tensors is a TypeError there (volumes take one:
-ssim3d_amp, ssim3d_map_amp and SSIM3DLoss, below).
+reflects, the interior is identical and the outermost (win_size - 1) / 2 pixels differ.  ms_ssim keeps the fixed window for now.
 
     photo = 0.85 * (1 - ssim_map(warped, target, win_size=3, window="uniform")) / 2 + 0.15 * (warped - target).abs()
+
+The window with float16 / bfloat16 tensors.  ssim_amp(x, y, data_range, win_size, win_sigma, window), ssim_map_amp(...) and SSIMLoss on
+GPU tensors take the window keywords with 16-bit tensors as well (rmgr_ssim_hip_enqueue_ssimh_win, _ssimh_win_grad, _ssimh_win_map_grad):
+the value and the map have the bits of ssim(x.float(), y.float(), win_size=...) / ssim_map(...), and the gradient is that call's float32
+gradient rounded once by the kernel into the inputs' dtype -- 2 B/px of torch memory for it instead of the 4 + 4 + 4 of x.float(),
+y.float() and a float32 gradient.  float32 pairs and the default keywords take exactly the path of ssim / ssim_map.  The wart of
+ms_ssim / ms_ssim_amp again: ssim and ssim_map themselves refuse a non-default window with 16-bit tensors (a TypeError, "fixed window",
+pinned by tests from the time there was no such path; the _amp functions are the same functions without that refusal), and SSIMLoss is
+pinned the same way on CPU tensors: it is 1 - ssim_amp(x, y) when both tensors are on a GPU and raises what ssim raises otherwise, so
+two 16-bit CPU tensors under a window still say "fixed window" where every other CPU pair is the "GPU" ValueError.
+
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        loss = SSIMLoss(win_size=7)(net(x), y.bfloat16())              # read as bfloat16; the gradient is bfloat16
+        photo = 0.85 * (1 - ssim_map_amp(warped, target, win_size=3, window="uniform")) / 2 + 0.15 * (warped - target).abs()
 
 Volumes.  ssim3d(x, y, data_range) and SSIM3DLoss take (..., D, H, W) float32 tensors and apply the window over x, y and z
 (rmgr_ssim_hip_enqueue_ssim3f, _ssim3f_grad): the 3-D SSIM of pytorch-msssim (spatial_dims=3), torchmetrics, MONAI and skimage.  ssim() on
@@ -132,36 +144,37 @@ def _sample_type(torch, dtype):
     return {torch.float16: api.SAMPLE_F16, torch.bfloat16: api.SAMPLE_BF16}.get(dtype)
 
 
-def _check(x, y, data_range, half=False):
-    """The documented errors, before any GPU call.  Returns data_range as a float.  half: float16 and bfloat16 pairs are taken too."""
+def _check(x, y, data_range, half=False, name="ssim"):
+    """The documented errors (`name`: the function the message names), before any GPU call.  Returns data_range as a float.  half: float16
+    and bfloat16 pairs are taken too."""
     import torch
     if not isinstance(x, torch.Tensor) or not isinstance(y, torch.Tensor):
-        raise TypeError("ssim: x and y must be torch tensors")
+        raise TypeError("%s: x and y must be torch tensors" % name)
     if half:
         if x.dtype != y.dtype or x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError("ssim: two float32, two float16 or two bfloat16 tensors expected, got %s and %s" % (x.dtype, y.dtype))
+            raise TypeError("%s: two float32, two float16 or two bfloat16 tensors expected, got %s and %s" % (name, x.dtype, y.dtype))
     elif x.dtype != torch.float32 or y.dtype != torch.float32:
-        raise TypeError("ssim: float32 tensors expected, got %s and %s" % (x.dtype, y.dtype))
+        raise TypeError("%s: float32 tensors expected, got %s and %s" % (name, x.dtype, y.dtype))
     if x.dim() < 2:
-        raise ValueError("ssim: tensors of shape (..., H, W) expected, got %d dimension(s)" % x.dim())
+        raise ValueError("%s: tensors of shape (..., H, W) expected, got %d dimension(s)" % (name, x.dim()))
     if x.shape != y.shape:
-        raise ValueError("ssim: shapes differ: %s and %s" % (tuple(x.shape), tuple(y.shape)))
+        raise ValueError("%s: shapes differ: %s and %s" % (name, tuple(x.shape), tuple(y.shape)))
     if not x.is_cuda or not y.is_cuda:
-        raise ValueError("ssim: the tensors must be on a GPU (there is no CPU path)")
+        raise ValueError("%s: the tensors must be on a GPU (there is no CPU path)" % name)
     if x.device != y.device:
-        raise ValueError("ssim: the tensors are on different devices: %s and %s" % (x.device, y.device))
+        raise ValueError("%s: the tensors are on different devices: %s and %s" % (name, x.device, y.device))
     if x.shape[-1] == 0 or x.shape[-2] == 0:
-        raise ValueError("ssim: empty planes: %s" % (tuple(x.shape),))
+        raise ValueError("%s: empty planes: %s" % (name, tuple(x.shape)))
     r = float(data_range)
     if not (r > 0.0) or math.isinf(r):
-        raise ValueError("ssim: data_range must be finite and > 0, got %r" % (data_range,))
+        raise ValueError("%s: data_range must be finite and > 0, got %r" % (name, data_range))
     return r
 
 
 def _window(x, y, win_size, win_sigma, window, name="ssim", fixed16=True):
     """The documented errors of the window arguments (`name`: the function the message names), before any GPU call.  Returns None for
     the defaults (today's path) or an api.Window.  fixed16 (the 2-D names): float16 / bfloat16 tensors keep the fixed window; the 3-D
-    names pass False, their 16-bit path takes a window (ssim3d and ssim3d_map go on to refuse the tensors themselves)."""
+    names and the 2-D _amp names pass False, their 16-bit path takes a window (ssim3d and ssim3d_map go on to refuse the tensors themselves)."""
     if not isinstance(window, str):
         raise TypeError("%s: window must be 'gaussian' or 'uniform', got %s" % (name, type(window).__name__))
     win = api.make_window(win_size, 1.5 if window == "uniform" else win_sigma, window)      # TypeError / ValueError
@@ -228,7 +241,7 @@ def _make_function():
                 if st is None:
                     _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr(), **_win_kw(win))
                 else:
-                    _context(x.device, work).enqueue_ssimh(params, n, data_range, st, sums.data_ptr())
+                    _context(x.device, work).enqueue_ssimh(params, n, data_range, st, sums.data_ptr(), **_win_kw(win))
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
@@ -257,7 +270,7 @@ def _make_function():
                 if st is None:
                     _context(x.device, work).enqueue_ssimf_grad(params, n, ctx.data_range, g.data_ptr(), ga, gb, **_win_kw(ctx.win))
                 else:
-                    _context(x.device, work).enqueue_ssimh_grad(params, n, ctx.data_range, st, g.data_ptr(), ga, gb)
+                    _context(x.device, work).enqueue_ssimh_grad(params, n, ctx.data_range, st, g.data_ptr(), ga, gb, **_win_kw(ctx.win))
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None, None
@@ -321,7 +334,7 @@ def _make_map_function():
                 if st is None:
                     _context(x.device, work).enqueue_ssimf(params, n, data_range, sums.data_ptr(), **_win_kw(win))
                 else:
-                    _context(x.device, work).enqueue_ssimh(params, n, data_range, st, sums.data_ptr())
+                    _context(x.device, work).enqueue_ssimh(params, n, data_range, st, sums.data_ptr(), **_win_kw(win))
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y)
@@ -351,7 +364,7 @@ def _make_map_function():
                 if st is None:
                     _context(x.device, work).enqueue_ssimf_map_grad(params, n, ctx.data_range, maps, ga, gb, **_win_kw(ctx.win))
                 else:
-                    _context(x.device, work).enqueue_ssimh_map_grad(params, n, ctx.data_range, st, maps, ga, gb)
+                    _context(x.device, work).enqueue_ssimh_map_grad(params, n, ctx.data_range, st, maps, ga, gb, **_win_kw(ctx.win))
                 if work is not cur:
                     cur.wait_stream(work)
             return gx, gy, None, None
@@ -374,10 +387,42 @@ def ssim_map(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"
     return _map_function.apply(x, y, r, win)
 
 
+def ssim_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
+    """ssim() for tensors as they come under mixed precision, with the window: ssim() without its refusal of a non-default window for
+    float16 / bfloat16 tensors.  float32 pairs, and every pair under the default keywords, take exactly ssim()'s path.  Two float16 or two
+    bfloat16 GPU tensors under another window run rmgr_ssim_hip_enqueue_ssimh_win, and the backward rmgr_ssim_hip_enqueue_ssimh_win_grad
+    under the window kept on the autograd context: the value has the bits of ssim(x.float(), y.float(), ...) under that window, the
+    gradient has the inputs' dtype and is that call's float32 gradient rounded once by the kernel (grad_out stays float32: a GradScaler's
+    scale arrives before the rounding).  Every other error is ssim()'s, under this function's name."""
+    global _function
+    win = _window(x, y, win_size, win_sigma, window, "ssim_amp", fixed16=False)
+    r = _check(x, y, data_range, half=True, name="ssim_amp")
+    if _function is None:
+        _function = _make_function()
+    return _function.apply(x, y, r, win)
+
+
+def ssim_map_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gaussian"):
+    """ssim_map() without its refusal of a non-default window for float16 / bfloat16 tensors, as ssim_amp() is to ssim(): the map is
+    float32 with the bits of ssim_map(x.float(), y.float(), ...) under that window (rmgr_ssim_hip_enqueue_ssimh_win), and the backward
+    (rmgr_ssim_hip_enqueue_ssimh_win_map_grad) reads grad_out per pixel, in place, and writes the gradient in the inputs' dtype with one
+    rounding.  float32 pairs and the default keywords take exactly ssim_map()'s path.  Every other error is ssim_map()'s, under this
+    function's name."""
+    global _map_function
+    win = _window(x, y, win_size, win_sigma, window, "ssim_map_amp", fixed16=False)
+    r = _check(x, y, data_range, half=True, name="ssim_map_amp")
+    if _map_function is None:
+        _map_function = _make_map_function()
+    return _map_function.apply(x, y, r, win)
+
+
 class SSIMLoss(object):
-    """1 - ssim(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per plane), float32 whatever the inputs' dtype (float32,
-    float16 or bfloat16, as ssim()).  win_size, win_sigma, window: the window, as ssim(), checked here.  A plain callable: it has no
-    parameters."""
+    """1 - ssim_amp(x, y, data_range): reduction "mean" (a scalar) or "none" (one value per plane), float32 whatever the inputs' dtype
+    (float32, float16 or bfloat16).  win_size, win_sigma, window: the window, as ssim(), checked here; GPU tensors take it at every dtype,
+    16-bit ones through the rmgr_ssim_hip_*_ssimh_win* entries.  A wart, pinned by tests from the time 16-bit tensors kept the fixed
+    window: unless both tensors are on a GPU this raises exactly what ssim() raises, so two float16 / bfloat16 CPU tensors under a
+    non-default window are a TypeError that says "fixed window", not the "GPU" ValueError of every other CPU pair.  A plain callable: it
+    has no parameters."""
 
     def __init__(self, data_range=1.0, reduction="mean", win_size=11, win_sigma=1.5, window="gaussian"):
         if reduction not in ("mean", "none"):
@@ -387,7 +432,8 @@ class SSIMLoss(object):
         self.win_size, self.win_sigma, self.window = win_size, win_sigma, window
 
     def __call__(self, x, y):
-        loss = 1.0 - ssim(x, y, self.data_range, self.win_size, self.win_sigma, self.window)
+        on_gpu = bool(getattr(x, "is_cuda", False)) and bool(getattr(y, "is_cuda", False))
+        loss = 1.0 - (ssim_amp if on_gpu else ssim)(x, y, self.data_range, self.win_size, self.win_sigma, self.window)
         return loss.mean() if self.reduction == "mean" else loss
 
 
