@@ -21,8 +21,8 @@ lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr
 
 # The objects both flavours share: kernels, the C ABI's host layer apart from ssim_context (the only one that reads
 # RMGR_SSIM_USE_DOUBLE: $(OBJ)/ssim_context.o / ssim_context_double.o), the drop-in layer.
-ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/msssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssimhk_kernels.o $(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o $(OBJ)/msssim3f_kernels.o $(OBJ)/msssim3h_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_volumes_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
-HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_flow.h $(SRC)/ssim3_flow.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/msssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimhk_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/msssim3f_kernels.h $(SRC)/msssim3h_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/msssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssimhk_kernels.o $(OBJ)/msssimk_kernels.o $(OBJ)/msssimhk_kernels.o $(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o $(OBJ)/msssim3f_kernels.o $(OBJ)/msssim3h_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_volumes_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
+HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_flow.h $(SRC)/ssim3_flow.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/msssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimhk_kernels.h $(SRC)/msssimk_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/msssim3f_kernels.h $(SRC)/msssim3h_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
 
 # Static flavour under the reference's archive name (CMakeLists.txt:205): the same objects, linked into ONE relocatable
 # object whose only global symbols are the API (the shared libraries' export list has no counterpart for archives: the
@@ -72,8 +72,8 @@ $(OBJ)/ssim16_kernels.o: $(SRC)/ssim16_kernels.hip $(SRC)/ssim16_kernels.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# The 2-D float-sample family: seven kernel files, one per group of entry points, whose tests count and budget their kernels.  The strip
-# walk, the reduction and the gradient tile are written once, in ssim2_walk.h, which every one of the seven includes; each is its own
+# The 2-D float-sample family: nine kernel files, one per group of entry points, whose tests count and budget their kernels.  The strip
+# walk, the reduction and the gradient tile are written once, in ssim2_walk.h, which every one of the nine includes; each is its own
 # object for the reason above, and all are built with the same flags -- the 16-bit, windowed and multi-scale results are held to
 # ssimf_kernels.o's, bit for bit (-ffp-contract=off: tests/ssimf_model.py and tests/ssimk_model.py restate the arithmetic operation by
 # operation).
@@ -84,8 +84,10 @@ $(OBJ)/ssim16_kernels.o: $(SRC)/ssim16_kernels.hip $(SRC)/ssim16_kernels.h
 #   ssimhk   float16 / bfloat16 samples under a window of 3, 5, 7 or 9 taps, both upstream forms (rmgr_ssim_hip_*_ssimh_win*)
 #   msssimf  multi-scale SSIM of float32 samples and its gradient (rmgr_ssim_hip_*_msssimf*); the pyramid, the product, k_s
 #   msssimh  multi-scale SSIM of float16 / bfloat16 samples (rmgr_ssim_hip_*_msssimh*): scale 0's kernels
-SSIM2_HDRS := $(SRC)/ssim2_walk.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimhk_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/msssimh_kernels.h
-$(OBJ)/ssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssimhk_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/msssimh_kernels.o: $(OBJ)/%.o: $(SRC)/%.hip $(SSIM2_HDRS)
+#   msssimk  a scale of multi-scale SSIM of float32 samples under a window of 3, 5, 7 or 9 taps (rmgr_ssim_hip_*_msssimf_win*)
+#   msssimhk scale 0 of multi-scale SSIM of float16 / bfloat16 samples under such a window (rmgr_ssim_hip_*_msssimh_win*)
+SSIM2_HDRS := $(SRC)/ssim2_walk.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimhk_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/msssimh_kernels.h $(SRC)/msssimk_kernels.h
+$(OBJ)/ssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssimhk_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/msssimh_kernels.o $(OBJ)/msssimk_kernels.o $(OBJ)/msssimhk_kernels.o: $(OBJ)/%.o: $(SRC)/%.hip $(SSIM2_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

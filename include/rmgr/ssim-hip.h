@@ -35,6 +35,9 @@
  *   rmgr_ssim_hip_enqueue_ssimh_win, rmgr_ssim_hip_compute_ssimh_win_device / _host, rmgr_ssim_hip_enqueue_ssimh_win_grad,
  *   rmgr_ssim_hip_enqueue_ssimh_win_map_grad   the float16 / bfloat16 entries under a caller-chosen window (size, sigma, box): no
  *                                      reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_msssimf_win, rmgr_ssim_hip_compute_msssimf_win_device / _host, rmgr_ssim_hip_enqueue_msssimf_win_grad and
+ *   the four msssimh_win counterparts          the multi-scale float32 and float16 / bfloat16 entries under a caller-chosen window:
+ *                                      no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim3f, rmgr_ssim_hip_compute_ssim3f_device / _host, rmgr_ssim_hip_enqueue_ssim3f_grad   SSIM of float32
  *                                      VOLUMES (three-dimensional window) and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_ssim3f_map_grad      gradient of the 3-D SSIM MAP for a per-voxel upstream gradient: no reference
@@ -762,8 +765,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_map_grad(rmgr_ssim_hip_Context* ctx, rm
  * Arguments, EINVAL / ENODEV rules, sub-batches, scratch and stream behaviour are those of the entry without _win.  Additional EINVAL,
  * checked before any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
  *
- * float16 / bfloat16 samples under a caller-chosen window: the ssimh_win entries, below.  Follow-up, not in this interface: multi-scale
- * SSIM (the msssim, msssimf and msssimh entries) keeps the fixed window {11, GAUSSIAN, 1.5f}.
+ * float16 / bfloat16 samples under a caller-chosen window: the ssimh_win entries, below.  Multi-scale SSIM of float32 and 16-bit
+ * samples under a caller-chosen window: the msssimf_win and msssimh_win entries, further below.
  */
 enum { RMGR_SSIM_HIP_WINDOW_GAUSSIAN = 0, RMGR_SSIM_HIP_WINDOW_UNIFORM = 1 };
 typedef struct rmgr_ssim_hip_Window {
@@ -831,6 +834,75 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win_map_grad(rmgr_ssim_hip_Context* ctx
                                                       rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
                                                       const rmgr_ssim_hip_GradOutF* gradOutMaps, const rmgr_ssim_hip_GradH* gradA,
                                                       const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
+
+/*
+ * MULTI-SCALE SSIM of float32 and of float16 / bfloat16 samples under a caller-chosen WINDOW: the four entries of each multi-scale
+ * family -- _enqueue_msssimf, _compute_msssimf_device, _compute_msssimf_host, _enqueue_msssimf_grad and their msssimh counterparts --
+ * with one more argument, `window`, after dataRange: the rmgr_ssim_hip_Window of the single-scale _win entries, unchanged.  What
+ * pytorch-msssim calls ms_ssim(win_size, win_sigma), torchmetrics kernel_size / sigma, TensorFlow filter_size / filter_sigma.  No
+ * reference counterpart: tests/msssimk_model.py restates it in float64, the gradient included.  Additions only:
+ * RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ * It is the definition of rmgr_ssim_hip_enqueue_msssimf / _enqueue_msssimf_grad (of _enqueue_msssimh / _enqueue_msssimh_grad) with 5
+ * replaced by R = (size - 1) / 2 AT EVERY SCALE:
+ *   Window   size 3, 5, 7, 9 or 11 taps on both axes, GAUSSIAN of any finite sigma > 0 or UNIFORM; the taps of the single-scale _win
+ *            entries, bit for bit.  The SAME window -- size and taps -- applies to every scale of the pyramid, as in pytorch-msssim; it
+ *            is not rescaled with the planes.  A NULL window means {11, GAUSSIAN, 1.5f}.
+ *   Per scale  mu, s_aa, s_bb, s_ab of a scale's planes are those of rmgr_ssim_hip_enqueue_ssimf_win under the window: separable, edges
+ *            clamped.  A coarse plane smaller than the window clamps like any other, down to 1 x 1: every tap then reads the same few
+ *            samples and the adjoint's tails (tail[d] = g_d + ... + g_R, summed in double and rounded once) fold onto them.
+ *   Unchanged, word for word  the pyramid and its rounding order; C1 and C2; cs = A2 / B2 and ssim = A1 A2 / (B1 B2); the fp64 means over
+ *            double(W_s) * double(H_s); the ReLU'd weighted product in double; k_s; the local gradient Gt(k d_mu) + 2 a Gt(k d_aa) +
+ *            b Gt(k d_ab) with Gt the adjoint of the clamped window; the adjoint of the clamped box filter, 0.25 c g_{s+1}(x >> 1, y >> 1),
+ *            one more rounding per scale; the centre of every 128-column strip column of each scale with its |c| <= dataRange test;
+ *            +0 from a scale whose k_s is 0.  None of them depends on the radius.
+ *   16-bit samples  as the msssimh entries define them: the value and every per-scale mean have the BITS of the msssimf_win entry on the
+ *            widened planes under the same window; each gradient pixel is the float32 value _enqueue_msssimf_win_grad would store for
+ *            the widened planes, rounded ONCE, to nearest-even, into the inputs' encoding.  gradOutDevice stays float32.
+ *   Identity with the fixed-window entries  a NULL window and {11, GAUSSIAN, 1.5f} give the BITS of the entries without _win: values,
+ *            per-scale means and gradients.
+ *   Determinism  every promise of msssimf / msssimh: the same bits alone or anywhere in a batch, after any sub-batch split, through every
+ *            entry point, on every call, with one gradient or both, and for any view of the same pixels.  No floating-point atomics.
+ *   Reach    a window reads nothing beyond its radius at any scale; it is not a zero-padded 11-tap window.
+ *   Accuracy measured per window against the float64 model: tests/msssimk_model.py (EMU) and DESIGN.md section 26.
+ *
+ * Arguments, EINVAL / ENODEV rules, sub-batches, scratch (it does not depend on the window) and stream behaviour are those of the entry
+ * without _win.  Additional EINVAL, checked after that entry's data range, pairs, scales and weights, before its other pointers and before
+ * the context or any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
+ *
+ * Not in this interface: the uint8 multi-scale entries (rmgr_ssim_hip_compute_msssim_*) keep the reference's window.  Follow-up:
+ * multi-scale SSIM of volumes (the msssim3f and msssim3h entries) keeps the fixed window {11, GAUSSIAN, 1.5f}.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                               float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                               const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_win_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                      float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                      const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_win_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                    float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                    const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_win_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
+                                                    float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                    const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
+                                                    const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                               rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                               rmgr_uint32_t scales, const double* weights, double* valuesDevice,
+                                               double* scaleMeansDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssimh_win_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                      rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                      rmgr_uint32_t scales, const double* weights, float* msssim,
+                                                      double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssimh_win_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                    rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                    rmgr_uint32_t scales, const double* weights, float* msssim,
+                                                    double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh_win_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                    rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                    rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice,
+                                                    const float* gradOutDevice, const rmgr_ssim_hip_GradH* gradA,
+                                                    const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT;
 
 /*
  * SSIM of `count` pairs of float32 VOLUMES of one size under a THREE-DIMENSIONAL window, and its gradient (MRI / CT reconstruction,

@@ -226,6 +226,10 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssimh_win", "rmgr_ssim_hip_compute_ssimh_win_device", "rmgr_ssim_hip_compute_ssimh_win_host",
     "rmgr_ssim_hip_enqueue_ssimh_win_grad", "rmgr_ssim_hip_enqueue_ssimh_win_map_grad",
     "rmgr_ssim_hip_enqueue_msssimh", "rmgr_ssim_hip_compute_msssimh_device", "rmgr_ssim_hip_compute_msssimh_host", "rmgr_ssim_hip_enqueue_msssimh_grad",
+    "rmgr_ssim_hip_enqueue_msssimf_win", "rmgr_ssim_hip_compute_msssimf_win_device", "rmgr_ssim_hip_compute_msssimf_win_host",
+    "rmgr_ssim_hip_enqueue_msssimf_win_grad",
+    "rmgr_ssim_hip_enqueue_msssimh_win", "rmgr_ssim_hip_compute_msssimh_win_device", "rmgr_ssim_hip_compute_msssimh_win_host",
+    "rmgr_ssim_hip_enqueue_msssimh_win_grad",
     "rmgr_ssim_hip_enqueue_ssim3f", "rmgr_ssim_hip_compute_ssim3f_device", "rmgr_ssim_hip_compute_ssim3f_host", "rmgr_ssim_hip_enqueue_ssim3f_grad",
     "rmgr_ssim_hip_enqueue_ssim3f_map_grad",
     "rmgr_ssim_hip_enqueue_ssim3h", "rmgr_ssim_hip_compute_ssim3h_device", "rmgr_ssim_hip_compute_ssim3h_host", "rmgr_ssim_hip_enqueue_ssim3h_grad",
@@ -369,6 +373,14 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_msssimh_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimh_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_enqueue_msssimh_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
+        "rmgr_ssim_hip_enqueue_msssimf_win": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
+        "rmgr_ssim_hip_compute_msssimf_win_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssimf_win_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_msssimf_win_grad": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(GradF), ctypes.POINTER(GradF)],
+        "rmgr_ssim_hip_enqueue_msssimh_win": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
+        "rmgr_ssim_hip_compute_msssimh_win_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssimh_win_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_msssimh_win_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
     }
     for name, args in sig.items():
         if path is None and os.environ.get("RMGR_SSIM_LIB") and not hasattr(lib, name):
@@ -957,36 +969,53 @@ def _weights_array(weights):
     return (ctypes.c_double * max(len(weights), 1))(*[float(x) for x in weights])
 
 
-def _msssimf_call(fn_name, handle, params, count, data_range, scales, weights, per_scale):
+def _win_name(fn_name):
+    """The name of the _win sibling of a multi-scale entry: rmgr_ssim_hip_compute_msssimf_host -> rmgr_ssim_hip_compute_msssimf_win_host."""
+    for tail in ("_device", "_host", "_grad"):
+        if fn_name.endswith(tail):
+            return fn_name[:-len(tail)] + "_win" + tail
+    return fn_name + "_win"
+
+
+def _msssimf_call(fn_name, handle, params, count, data_range, scales, weights, per_scale, window=None):
+    """window None: the entry fn_name; a Window: its _win sibling."""
+    ref = _window_ref(window)
     out = (ctypes.c_float * max(count, 1))()
     means = (ctypes.c_double * max(count * scales * 2, 1))() if per_scale else None
-    _check(fn_name, getattr(load_library(), fn_name)(handle, count, params, data_range, scales, _weights_array(weights), out, means))
+    if ref is None:
+        _check(fn_name, getattr(load_library(), fn_name)(handle, count, params, data_range, scales, _weights_array(weights), out, means))
+    else:
+        fn_name = _win_name(fn_name)
+        _check(fn_name, getattr(load_library(), fn_name)(handle, count, params, data_range, ref, scales, _weights_array(weights), out, means))
     vals = np.array(out[:count], np.float32)
     if not per_scale:
         return vals
     return vals, np.array(means[:count * scales * 2], np.float64).reshape(count, scales, 2)
 
 
-def compute_msssimf(a, b, data_range, scales=5, weights=None, per_scale=False, ctx=None):
+def compute_msssimf(a, b, data_range, scales=5, weights=None, per_scale=False, ctx=None, window=None):
     """Multi-scale SSIM of two H x W float32 host arrays at `data_range` (any strides numpy can express, negative ones included)
-    through rmgr_ssim_hip_compute_msssimf_host.  weights None: Wang's five (scales must be 5).  Returns a float32, and with
-    per_scale=True also a (scales, 2) float64 array of [scale]{mcs, mssim}."""
+    through rmgr_ssim_hip_compute_msssimf_host; window (a Window, make_window): through rmgr_ssim_hip_compute_msssimf_win_host under that
+    window at every scale.  weights None: Wang's five (scales must be 5).  Returns a float32, and with per_scale=True also a (scales, 2)
+    float64 array of [scale]{mcs, mssim}.  TypeError: a window that is neither None nor a Window."""
     a, b = _f32_view(a), _f32_view(b)
     assert a.shape == b.shape
     params = (ParamsF * 1)()
     params[0] = _params_f_of(a, b)
-    r = _msssimf_call("rmgr_ssim_hip_compute_msssimf_host", ctx.handle if ctx is not None else None, params, 1, data_range, scales, weights, per_scale)
+    r = _msssimf_call("rmgr_ssim_hip_compute_msssimf_host", ctx.handle if ctx is not None else None, params, 1, data_range, scales, weights, per_scale,
+                      window)
     return (r[0][0], r[1][0]) if per_scale else r[0]
 
 
-def compute_msssimf_batch(pairs, data_range, scales=5, weights=None, per_scale=False, ctx=None):
+def compute_msssimf_batch(pairs, data_range, scales=5, weights=None, per_scale=False, ctx=None, window=None):
     """compute_msssimf() of many host pairs of one size in one call: a float32 array (and a (count, scales, 2) array with per_scale)."""
     pairs = [(_f32_view(a), _f32_view(b)) for a, b in pairs]
     n = len(pairs)
     params = (ParamsF * max(n, 1))()
     for i, (a, b) in enumerate(pairs):
         params[i] = _params_f_of(a, b)
-    return _msssimf_call("rmgr_ssim_hip_compute_msssimf_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale)
+    return _msssimf_call("rmgr_ssim_hip_compute_msssimf_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale,
+                         window)
 
 
 def compute_msssim3f(a, b, data_range, scales=5, weights=None, per_scale=False, ctx=None):
@@ -1012,29 +1041,37 @@ def compute_msssim3f_batch(pairs, data_range, scales=5, weights=None, per_scale=
     return _msssimf_call("rmgr_ssim_hip_compute_msssim3f_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale)
 
 
-def _msssimh_call(fn_name, handle, params, count, code, data_range, scales, weights, per_scale):
+def _msssimh_call(fn_name, handle, params, count, code, data_range, scales, weights, per_scale, window=None):
+    """window None: the entry fn_name; a Window: its _win sibling."""
+    ref = _window_ref(window)
     out = (ctypes.c_float * max(count, 1))()
     means = (ctypes.c_double * max(count * scales * 2, 1))() if per_scale else None
-    _check(fn_name, getattr(load_library(), fn_name)(handle, count, params, code, data_range, scales, _weights_array(weights), out, means))
+    if ref is None:
+        _check(fn_name, getattr(load_library(), fn_name)(handle, count, params, code, data_range, scales, _weights_array(weights), out, means))
+    else:
+        fn_name = _win_name(fn_name)
+        _check(fn_name, getattr(load_library(), fn_name)(handle, count, params, code, data_range, ref, scales, _weights_array(weights), out, means))
     vals = np.array(out[:count], np.float32)
     if not per_scale:
         return vals
     return vals, np.array(means[:count * scales * 2], np.float64).reshape(count, scales, 2)
 
 
-def compute_msssimh(a, b, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
+def compute_msssimh(a, b, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None, window=None):
     """Multi-scale SSIM of two H x W host arrays of float16 or bfloat16 samples at `data_range` (any strides numpy can express, negative
-    ones included) through rmgr_ssim_hip_compute_msssimh_host.  Arrays and sample_type: as compute_ssimh (np.float16 arrays select
+    ones included) through rmgr_ssim_hip_compute_msssimh_host; window (a Window, make_window): through
+    rmgr_ssim_hip_compute_msssimh_win_host under that window at every scale.  Arrays and sample_type: as compute_ssimh (np.float16 arrays select
     float16; np.uint16 arrays carry bit patterns and need sample_type), with its errors.  weights None: Wang's five (scales must be 5).
     Returns a float32, and with per_scale=True also a (scales, 2) float64 array of [scale]{mcs, mssim}."""
     a, b, code = _h_pair(a, b, sample_type)
     params = (Params16 * 1)()
     params[0] = _params16_of(a, b)
-    r = _msssimh_call("rmgr_ssim_hip_compute_msssimh_host", ctx.handle if ctx is not None else None, params, 1, code, data_range, scales, weights, per_scale)
+    r = _msssimh_call("rmgr_ssim_hip_compute_msssimh_host", ctx.handle if ctx is not None else None, params, 1, code, data_range, scales, weights, per_scale,
+                      window)
     return (r[0][0], r[1][0]) if per_scale else r[0]
 
 
-def compute_msssimh_batch(pairs, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
+def compute_msssimh_batch(pairs, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None, window=None):
     """compute_msssimh() of many host pairs of one size and one sample type in one call: a float32 array (and a (count, scales, 2) array
     with per_scale)."""
     pairs = [_h_pair(a, b, sample_type) for a, b in pairs]
@@ -1046,7 +1083,8 @@ def compute_msssimh_batch(pairs, data_range, sample_type=None, scales=5, weights
     params = (Params16 * max(n, 1))()
     for i, (a, b, _) in enumerate(pairs):
         params[i] = _params16_of(a, b)
-    return _msssimh_call("rmgr_ssim_hip_compute_msssimh_host", ctx.handle if ctx is not None else None, params, n, code, data_range, scales, weights, per_scale)
+    return _msssimh_call("rmgr_ssim_hip_compute_msssimh_host", ctx.handle if ctx is not None else None, params, n, code, data_range, scales, weights, per_scale,
+                         window)
 
 
 def compute_msssim3h(a, b, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
@@ -1382,22 +1420,33 @@ class Context(object):
             _check("rmgr_ssim_hip_enqueue_ssimh_win_map_grad", self.lib.rmgr_ssim_hip_enqueue_ssimh_win_map_grad(
                 self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), grad_out_maps, grad_a, grad_b))
 
-    def msssimf_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False):
-        """MS-SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_msssimf_device: a float32
-        array, and with per_scale=True also a (count, scales, 2) float64 array of [pair][scale]{mcs, mssim}."""
-        return _msssimf_call("rmgr_ssim_hip_compute_msssimf_device", self.handle, params_array, count, data_range, scales, weights, per_scale)
+    def msssimf_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False, window=None):
+        """MS-SSIM of `count` device-resident float32 pairs (a ParamsF array) through rmgr_ssim_hip_compute_msssimf_device (window:
+        _msssimf_win_device): a float32 array, and with per_scale=True also a (count, scales, 2) float64 array of
+        [pair][scale]{mcs, mssim}."""
+        return _msssimf_call("rmgr_ssim_hip_compute_msssimf_device", self.handle, params_array, count, data_range, scales, weights, per_scale, window)
 
-    def enqueue_msssimf(self, params_array, count, data_range, values_dev_ptr, means_dev_ptr, scales=5, weights=None):
-        """rmgr_ssim_hip_enqueue_msssimf: per-pair fp64 values and count x scales x 2 fp64 means into device memory, asynchronously on the
-        context's stream."""
-        _check("rmgr_ssim_hip_enqueue_msssimf", self.lib.rmgr_ssim_hip_enqueue_msssimf(
-            self.handle, count, params_array, data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+    def enqueue_msssimf(self, params_array, count, data_range, values_dev_ptr, means_dev_ptr, scales=5, weights=None, window=None):
+        """rmgr_ssim_hip_enqueue_msssimf (window: _msssimf_win): per-pair fp64 values and count x scales x 2 fp64 means into device memory,
+        asynchronously on the context's stream."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_msssimf", self.lib.rmgr_ssim_hip_enqueue_msssimf(
+                self.handle, count, params_array, data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+        else:
+            _check("rmgr_ssim_hip_enqueue_msssimf_win", self.lib.rmgr_ssim_hip_enqueue_msssimf_win(
+                self.handle, count, params_array, data_range, _window_ref(window), scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
 
-    def enqueue_msssimf_grad(self, params_array, count, data_range, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5, weights=None):
-        """rmgr_ssim_hip_enqueue_msssimf_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs, from the forward's means
+    def enqueue_msssimf_grad(self, params_array, count, data_range, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5, weights=None,
+                             window=None):
+        """rmgr_ssim_hip_enqueue_msssimf_grad (window: _msssimf_win_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs, from the forward's means
         (device memory), into the planes the GradF arrays describe; asynchronous on the context's stream, no host synchronisation."""
-        _check("rmgr_ssim_hip_enqueue_msssimf_grad", self.lib.rmgr_ssim_hip_enqueue_msssimf_grad(
-            self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_msssimf_grad", self.lib.rmgr_ssim_hip_enqueue_msssimf_grad(
+                self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_msssimf_win_grad", self.lib.rmgr_ssim_hip_enqueue_msssimf_win_grad(
+                self.handle, count, params_array, data_range, _window_ref(window), scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr,
+                grad_a, grad_b))
 
     def msssim3f_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False):
         """MS-SSIM of `count` device-resident pairs of float32 volumes (a Params3F array) through rmgr_ssim_hip_compute_msssim3f_device: a
@@ -1416,26 +1465,37 @@ class Context(object):
         _check("rmgr_ssim_hip_enqueue_msssim3f_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3f_grad(
             self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
 
-    def msssimh_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False):
-        """MS-SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_msssimh_device: a
-        float32 array, and with per_scale=True also a (count, scales, 2) float64 array of [pair][scale]{mcs, mssim}."""
+    def msssimh_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False, window=None):
+        """MS-SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_msssimh_device
+        (window: _msssimh_win_device): a float32 array, and with per_scale=True also a (count, scales, 2) float64 array of
+        [pair][scale]{mcs, mssim}."""
         return _msssimh_call("rmgr_ssim_hip_compute_msssimh_device", self.handle, params_array, count, sample_type_code(sample_type), data_range,
-                             scales, weights, per_scale)
+                             scales, weights, per_scale, window)
 
-    def enqueue_msssimh(self, params_array, count, data_range, sample_type, values_dev_ptr, means_dev_ptr, scales=5, weights=None):
-        """rmgr_ssim_hip_enqueue_msssimh: per-pair fp64 values and count x scales x 2 fp64 means into device memory, asynchronously on the
-        context's stream."""
-        _check("rmgr_ssim_hip_enqueue_msssimh", self.lib.rmgr_ssim_hip_enqueue_msssimh(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+    def enqueue_msssimh(self, params_array, count, data_range, sample_type, values_dev_ptr, means_dev_ptr, scales=5, weights=None, window=None):
+        """rmgr_ssim_hip_enqueue_msssimh (window: _msssimh_win): per-pair fp64 values and count x scales x 2 fp64 means into device memory,
+        asynchronously on the context's stream."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_msssimh", self.lib.rmgr_ssim_hip_enqueue_msssimh(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+        else:
+            _check("rmgr_ssim_hip_enqueue_msssimh_win", self.lib.rmgr_ssim_hip_enqueue_msssimh_win(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), scales, _weights_array(weights),
+                values_dev_ptr, means_dev_ptr))
 
     def enqueue_msssimh_grad(self, params_array, count, data_range, sample_type, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5,
-                             weights=None):
-        """rmgr_ssim_hip_enqueue_msssimh_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs, from the forward's means (device
+                             weights=None, window=None):
+        """rmgr_ssim_hip_enqueue_msssimh_grad (window: _msssimh_win_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs, from the forward's means (device
         memory), into the 16-bit planes the GradH arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32 values;
         asynchronous on the context's stream, no host synchronisation."""
-        _check("rmgr_ssim_hip_enqueue_msssimh_grad", self.lib.rmgr_ssim_hip_enqueue_msssimh_grad(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), means_dev_ptr,
-            grad_out_dev_ptr, grad_a, grad_b))
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_msssimh_grad", self.lib.rmgr_ssim_hip_enqueue_msssimh_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), means_dev_ptr,
+                grad_out_dev_ptr, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_msssimh_win_grad", self.lib.rmgr_ssim_hip_enqueue_msssimh_win_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), scales, _weights_array(weights),
+                means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
 
     def msssim3h_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False):
         """MS-SSIM of `count` device-resident pairs of float16 / bfloat16 volumes (a Params3H array) through

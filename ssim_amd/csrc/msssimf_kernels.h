@@ -5,6 +5,7 @@
 #define SSIM_AMD_MSSSIMF_KERNELS_H
 
 #include "ssimf_kernels.h"      // PairFDesc, GradFDesc, kSFStripW, kSFTile, kSFMaxDim
+#include "ssimk_kernels.h"      // kSKMaxRadius
 
 namespace ssim_hip {
 
@@ -73,12 +74,29 @@ hipError_t launch_msssimf_grad(const PairFDesc* descs_dev, const GradFDesc* grad
 // scale 0's share of `partials`, which comes first and has msf_cells(width, height, 0) x 2 x count doubles.  first == 0 is the launcher
 // above.  first == 1 skips the pyramid step, the strip kernel and the gradient kernel of scale 0 and reads nothing of row 0 of descs_dev
 // and grads_dev; the reduction, the product and the coefficients cover every scale.  `wide` is scale 0's and ignored when first == 1.
-hipError_t launch_msssimf_from(uint32_t first, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales,
-                               bool wide, float data_range, const double* weights, int cu_count, int xcd_count, double* partials,
-                               double* means, double* values, hipStream_t stream);
-hipError_t launch_msssimf_grad_from(uint32_t first, const PairFDesc* descs_dev, const GradFDesc* grads_dev, uint32_t count, uint32_t width,
-                                    uint32_t height, uint32_t scales, float data_range, const double* weights, const double* means,
-                                    const float* g_out, float* coef, int which, hipStream_t stream);
+//
+// They also take the window, the same at every scale: its taps, centre first (ssimk_kernels.h: window_taps), and its radius, which must
+// be 5 here: windows of 11 taps run on the kernels of this file with the window's taps -- the engine's taps: the two launchers above, bit
+// for bit.  Radius 1 .. 4: launch_msssimk_from / launch_msssimk_grad_from of msssimk_kernels.h, on kernels of that radius.
+hipError_t launch_msssimf_from(uint32_t first, uint32_t radius, const float (&taps)[kSKMaxRadius + 1], const PairFDesc* descs_dev, uint32_t count,
+                               uint32_t width, uint32_t height, uint32_t scales, bool wide, float data_range, const double* weights, int cu_count,
+                               int xcd_count, double* partials, double* means, double* values, hipStream_t stream);
+hipError_t launch_msssimf_grad_from(uint32_t first, uint32_t radius, const float (&taps)[kSKMaxRadius + 1], const PairFDesc* descs_dev,
+                                    const GradFDesc* grads_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales, float data_range,
+                                    const double* weights, const double* means, const float* g_out, float* coef, int which, hipStream_t stream);
+
+// What does not depend on the window, as the launchers above enqueue it -- for them and for msssimk_kernels.hip, whose launchers differ in
+// the strip and gradient kernels alone:
+//   _pyramid  the pyramid of `count` pairs from scale `first` (0 or 1) on, one launch per step, finest first: row s + 1 of descs_dev from row s
+//   _means    the reduction of every (pair, scale, kind) over `partials` as laid out above ([scale][pair][cell]{cs, ssim}, the cells of a
+//             scale msf_cells()) into `means`, then the ReLU'd weighted product into `values`
+//   _coef     k_s of every pair and scale into `coef` (count x scales floats), from the forward's means and g_out
+hipError_t launch_msssimf_pyramid(uint32_t first, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales,
+                                  hipStream_t stream);
+hipError_t launch_msssimf_means(uint32_t count, uint32_t width, uint32_t height, uint32_t scales, const double* weights, const double* partials,
+                                double* means, double* values, hipStream_t stream);
+hipError_t launch_msssimf_coef(uint32_t count, uint32_t width, uint32_t height, uint32_t scales, const double* weights, const double* means,
+                               const float* g_out, float* coef, hipStream_t stream);
 
 } // namespace ssim_hip
 

@@ -199,63 +199,98 @@ hipError_t launch_msssimf(const PairFDesc* descs_dev, uint32_t count, uint32_t w
                           float data_range, const double* weights, int cu_count, int xcd_count, double* partials, double* means,
                           double* values, hipStream_t stream)
 {
-    return launch_msssimf_from(0, descs_dev, count, width, height, scales, wide, data_range, weights, cu_count, xcd_count, partials, means, values, stream);
+    float taps[MAXR + 1];
+    default_taps(taps);
+    return launch_msssimf_from(0, MAXR, taps, descs_dev, count, width, height, scales, wide, data_range, weights, cu_count, xcd_count, partials, means,
+                               values, stream);
 }
 
-hipError_t launch_msssimf_from(uint32_t first, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales,
-                               bool wide, float data_range, const double* weights, int cu_count, int xcd_count, double* partials,
-                               double* means, double* values, hipStream_t stream)
+// ---- the steps that do not depend on the window, for this file's launchers and for msssimk_kernels.hip's --------------------------
+
+hipError_t launch_msssimf_pyramid(uint32_t first, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales,
+                                  hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_call(count, width, height, scales, data_range, weights) || first > 1) return hipErrorInvalidValue;
-    hipError_t e = launch_pyramid(first, descs_dev, count, width, height, scales, stream);
-    if (e != hipSuccess) return e;
+    if (first > 1 || scales < 1 || scales > kMSFMaxScales || count > msssimf_max_count(width, height)) return hipErrorInvalidValue;
+    return launch_pyramid(first, descs_dev, count, width, height, scales, stream);
+}
+
+hipError_t launch_msssimf_means(uint32_t count, uint32_t width, uint32_t height, uint32_t scales, const double* weights, const double* partials,
+                                double* means, double* values, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (!valid_call(count, width, height, scales, 1.0f, weights)) return hipErrorInvalidValue;
     KRArgs kr;
     kr.partials = partials; kr.means = means; kr.count = count; kr.scales = scales;
     uint64_t offset = 0;
     for (uint32_t s = 0; s < kMSFMaxScales; ++s) { kr.offset[s] = 0; kr.cells[s] = 0; kr.pixels[s] = 1.0; }
-    float taps[MAXR + 1];
-    default_taps(taps);
+    for (uint32_t s = 0; s < scales; ++s) {
+        kr.offset[s] = offset; kr.cells[s] = msf_cells(width, height, s); kr.pixels[s] = (double)msf_dim(width, s) * (double)msf_dim(height, s);
+        offset += kr.cells[s] * 2 * count;
+    }
+    hipLaunchKernelGGL(msssimf_reduce_kernel, dim3(count * scales * 2), dim3(kReduceThreads), 0, stream, kr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(msssimf_finalise_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, scales, weights), means, values);
+    return hipGetLastError();
+}
+
+hipError_t launch_msssimf_coef(uint32_t count, uint32_t width, uint32_t height, uint32_t scales, const double* weights, const double* means,
+                               const float* g_out, float* coef, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (!valid_call(count, width, height, scales, 1.0f, weights)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(msssimf_coef_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, scales, weights), means, g_out, coef);
+    return hipGetLastError();
+}
+
+// ---- the launchers of the 11-tap window ---------------------------------------------------------------------------------------------
+
+hipError_t launch_msssimf_from(uint32_t first, uint32_t radius, const float (&taps)[kSKMaxRadius + 1], const PairFDesc* descs_dev, uint32_t count,
+                               uint32_t width, uint32_t height, uint32_t scales, bool wide, float data_range, const double* weights, int cu_count,
+                               int xcd_count, double* partials, double* means, double* values, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (!valid_call(count, width, height, scales, data_range, weights) || first > 1 || radius != MAXR) return hipErrorInvalidValue;
+    hipError_t e = launch_pyramid(first, descs_dev, count, width, height, scales, stream);
+    if (e != hipSuccess) return e;
+    uint64_t offset = 0;
     for (uint32_t s = 0; s < scales; ++s) {
         const GeometryF geo = planf(msf_dim(width, s), msf_dim(height, s), count, cu_count);
         const Strip2Args<PairFDesc> ka = fill_strip(geo, descs_dev + (size_t)s * count, data_range, taps, xcd_count, partials + offset);
-        kr.offset[s] = offset; kr.cells[s] = geo.cells_per_image(); kr.pixels[s] = (double)geo.width * (double)geo.height;
-        offset += kr.cells[s] * 2 * count;
+        offset += geo.cells_per_image() * 2 * count;
         if (s < first) continue;                  // the caller's own strip kernel fills this scale's partials
         pick_bool(wide && s == 0, [&](auto w) { hipLaunchKernelGGL((msssimf_strip_kernel<decltype(w)::value>), strip_grid(geo), dim3(64), 0, stream, ka); });
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(msssimf_reduce_kernel, dim3(count * scales * 2), dim3(kReduceThreads), 0, stream, kr);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(msssimf_finalise_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, scales, weights), means, values);
-    return hipGetLastError();
+    return launch_msssimf_means(count, width, height, scales, weights, partials, means, values, stream);
 }
 
 hipError_t launch_msssimf_grad(const PairFDesc* descs_dev, const GradFDesc* grads_dev, uint32_t count, uint32_t width, uint32_t height,
                                uint32_t scales, float data_range, const double* weights, const double* means, const float* g_out,
                                float* coef, int which, hipStream_t stream)
 {
-    return launch_msssimf_grad_from(0, descs_dev, grads_dev, count, width, height, scales, data_range, weights, means, g_out, coef, which, stream);
-}
-
-hipError_t launch_msssimf_grad_from(uint32_t first, const PairFDesc* descs_dev, const GradFDesc* grads_dev, uint32_t count, uint32_t width,
-                                    uint32_t height, uint32_t scales, float data_range, const double* weights, const double* means,
-                                    const float* g_out, float* coef, int which, hipStream_t stream)
-{
-    if (count == 0) return hipSuccess;
-    if (!valid_call(count, width, height, scales, data_range, weights) || which < 1 || which > 3 || first > 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(msssimf_coef_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, scales, weights), means, g_out, coef);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = launch_pyramid(first, descs_dev, count, width, height, scales, stream)) != hipSuccess) return e;
     float taps[MAXR + 1];
     default_taps(taps);
+    return launch_msssimf_grad_from(0, MAXR, taps, descs_dev, grads_dev, count, width, height, scales, data_range, weights, means, g_out, coef, which,
+                                    stream);
+}
+
+hipError_t launch_msssimf_grad_from(uint32_t first, uint32_t radius, const float (&taps)[kSKMaxRadius + 1], const PairFDesc* descs_dev,
+                                    const GradFDesc* grads_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t scales, float data_range,
+                                    const double* weights, const double* means, const float* g_out, float* coef, int which, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (!valid_call(count, width, height, scales, data_range, weights) || which < 1 || which > 3 || first > 1 || radius != MAXR)
+        return hipErrorInvalidValue;
+    hipError_t e = launch_msssimf_coef(count, width, height, scales, weights, means, g_out, coef, stream);
+    if (e != hipSuccess) return e;
+    if ((e = launch_pyramid(first, descs_dev, count, width, height, scales, stream)) != hipSuccess) return e;
     for (uint32_t s = scales; s-- > first;) {
         const bool last = s + 1 == scales;
         Grad2Args<PairFDesc, GradFDesc> ka = fill_grad(msf_dim(width, s), msf_dim(height, s), descs_dev + (size_t)s * count, grads_dev + (size_t)s * count,
-                                                       data_range, 5, taps);
+                                                       data_range, MAXR, taps);
         ka.up = last ? nullptr : grads_dev + (size_t)(s + 1) * count;
         ka.g_out = coef + s; ka.g_out_stride = scales;      // k_s of pair i at coef[i * scales + s]
         pick_bool(last, [&](auto l) {

@@ -70,12 +70,21 @@ void launch_down(const PairHDesc* descs0_dev, const PairFDesc* descs_dev, uint32
 
 } // namespace
 
-hipError_t launch_msssimh(const PairHDesc* descs0_dev, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height,
-                          uint32_t scales, int type, bool wide, float data_range, const double* weights, int cu_count, int xcd_count,
-                          double* partials, double* means, double* values, hipStream_t stream)
+hipError_t launch_msssimh_down(const PairHDesc* descs0_dev, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, int type,
+                               hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_type(type) || !valid_range(data_range) || scales < 1 || scales > kMSFMaxScales || count > msssimf_max_count(width, height))
+    if (!valid_type(type) || count > msssimf_max_count(width, height)) return hipErrorInvalidValue;
+    pick_type(type, [&](auto t) { launch_down<decltype(t)::value>(descs0_dev, descs_dev, count, width, height, stream); });
+    return hipGetLastError();
+}
+
+hipError_t launch_msssimh(const PairHDesc* descs0_dev, const PairFDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height,
+                          uint32_t scales, int type, bool wide, float data_range, uint32_t radius, const float (&taps)[kSKMaxRadius + 1],
+                          const double* weights, int cu_count, int xcd_count, double* partials, double* means, double* values, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (!valid_type(type) || !valid_range(data_range) || radius != MAXR || scales < 1 || scales > kMSFMaxScales || count > msssimf_max_count(width, height))
         return hipErrorInvalidValue;
     hipError_t e;
     if (scales > 1) {
@@ -84,8 +93,6 @@ hipError_t launch_msssimh(const PairHDesc* descs0_dev, const PairFDesc* descs_de
     }
     // scale 0's strips and cells, as launch_msssimf_from lays them out: its partials come first
     const GeometryF geo = planf(width, height, count, cu_count);
-    float taps[MAXR + 1];
-    default_taps(taps);
     const Strip2Args<PairHDesc> ka = fill_strip(geo, descs0_dev, data_range, taps, xcd_count, partials);
     pick_type(type, [&](auto t) {
         pick_bool(wide, [&](auto w) {
@@ -93,16 +100,17 @@ hipError_t launch_msssimh(const PairHDesc* descs0_dev, const PairFDesc* descs_de
         });
     });
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    return launch_msssimf_from(1, descs_dev, count, width, height, scales, false, data_range, weights, cu_count, xcd_count, partials, means,
+    return launch_msssimf_from(1, radius, taps, descs_dev, count, width, height, scales, false, data_range, weights, cu_count, xcd_count, partials, means,
                                values, stream);
 }
 
 hipError_t launch_msssimh_grad(const PairHDesc* descs0_dev, const PairFDesc* descs_dev, const GradHDesc* grads0_dev, const GradFDesc* grads_dev,
-                               uint32_t count, uint32_t width, uint32_t height, uint32_t scales, int type, float data_range,
-                               const double* weights, const double* means, const float* g_out, float* coef, int which, hipStream_t stream)
+                               uint32_t count, uint32_t width, uint32_t height, uint32_t scales, int type, float data_range, uint32_t radius,
+                               const float (&taps)[kSKMaxRadius + 1], const double* weights, const double* means, const float* g_out, float* coef,
+                               int which, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_type(type) || !valid_range(data_range) || scales < 1 || scales > kMSFMaxScales || which < 1 || which > 3 ||
+    if (!valid_type(type) || !valid_range(data_range) || radius != MAXR || scales < 1 || scales > kMSFMaxScales || which < 1 || which > 3 ||
         count > msssimf_max_count(width, height))
         return hipErrorInvalidValue;
     hipError_t e;
@@ -111,13 +119,11 @@ hipError_t launch_msssimh_grad(const PairHDesc* descs0_dev, const PairFDesc* des
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     // the coefficients of every scale, the rest of the pyramid, the float32 gradients from the coarsest scale down to scale 1
-    if ((e = launch_msssimf_grad_from(1, descs_dev, grads_dev, count, width, height, scales, data_range, weights, means, g_out, coef, which,
+    if ((e = launch_msssimf_grad_from(1, radius, taps, descs_dev, grads_dev, count, width, height, scales, data_range, weights, means, g_out, coef, which,
                                       stream)) != hipSuccess)
         return e;
     const bool last = scales == 1;
-    float taps[MAXR + 1];
-    default_taps(taps);
-    Grad2Args<PairHDesc, GradHDesc> ka = fill_grad(width, height, descs0_dev, grads0_dev, data_range, 5, taps);
+    Grad2Args<PairHDesc, GradHDesc> ka = fill_grad(width, height, descs0_dev, grads0_dev, data_range, MAXR, taps);
     ka.up = last ? nullptr : grads_dev + (size_t)count;
     ka.g_out = coef; ka.g_out_stride = scales;              // k_0 of pair i at coef[i * scales]
     pick_type(type, [&](auto t) {

@@ -1,10 +1,10 @@
 // ssim2_walk.h -- the strip walk of SSIM on 2-D float-family samples and the gradient tile, written once for the kernel files of the
-// family (ssimf / ssimh / ssimk / ssimhk / ssimw / msssimf / msssimh _kernels.hip).  Not installed, and included by those seven files only: each of
+// family (ssimf / ssimh / ssimk / ssimhk / ssimw / msssimf / msssimh / msssimk / msssimhk _kernels.hip).  Not installed, and included by those nine files only: each of
 // them keeps its __global__ kernels -- their names, template parameters and launch bounds, which its tests count and budget -- as
 // one-line calls of strip_body, grad_body and reduce_body, and its launch_* functions.  Everything here has internal linkage, so an
 // instantiation and its LDS belong to the one kernel of the including file that calls it.  The definition the kernels implement is in
 // include/rmgr/ssim-hip.h; tests/ssimf_model.py and tests/ssimk_model.py restate it in float64 and restate the arithmetic below in fp32.
-// The seven files are built with the same flags (-ffp-contract=off).
+// The nine files are built with the same flags (-ffp-contract=off).
 //
 // The bodies are templates on these things, and on nothing else:
 //  * Sample: how a sample gets into a register and how a gradient pixel leaves one.  SampleF32 is a float load / store.  SampleH<TYPE>

@@ -2,7 +2,7 @@
 // 9- to 16-bit integers (ssim16), of float32 (ssimf) and of float16 / bfloat16 samples (ssimh), the gradients of the latter two for a
 // scalar and for a per-pixel upstream gradient (ssimw), and multi-scale SSIM of float32 (msssimf) and of float16 / bfloat16 samples
 // (msssimh) with its gradient.  The definitions are in include/rmgr/ssim-hip.h, the kernels in ssim16_ / ssimf_ / ssimh_ / ssimw_ /
-// ssimk_ / ssimhk_ / msssimf_ / msssimh_kernels.hip.
+// ssimk_ / ssimhk_ / msssimf_ / msssimh_ / msssimk_ / msssimhk_kernels.hip.
 //
 // The three single-scale families differ in their sample type and in what a launch is told (bit depth; data range; encoding and data
 // range); each is described once by a small struct (Family16 / FamilyF / FamilyH) and the host flow -- validation, sub-batches, staging
@@ -17,6 +17,7 @@
 // the launch that read its ring slot kSfSlots enqueues ago.
 #include "ssim_flow.h"
 #include "msssimh_kernels.h"
+#include "msssimk_kernels.h"
 #include "ssimhk_kernels.h"
 #include "ssimw_kernels.h"
 
@@ -407,7 +408,8 @@ int enqueue_grads(rmgr_ssim_hip_Context* c, uint32_t count, const typename F::Pa
 // Scale 0 is read where the caller has it; the planes of scales >= 1 (and, in the backward, their gradient planes) are dense float32
 // planes of the context's scratch, one set per pair, rewritten by every sub-batch in stream order.  The two families differ in scale 0
 // alone -- its samples, its descriptors and the kernels that read and write them -- and each is described by a small struct (MultiF /
-// MultiH) over which the flow is written once.
+// MultiH) over which the flow is written once.  The window, the engine's or the caller's (_win), is one more member of it: the same at
+// every scale, and nothing of the flow -- pyramid, scratch, sub-batches, tables -- depends on it.
 //
 // A launch reads one table of pair descriptors, scales x n PairFDesc as [scale][pair] (rows >= 1: the pyramid), and -- backward -- one of
 // gradient descriptors, scales x n GradFDesc.  MultiF: row 0 holds the caller's planes.  MultiH: row 0 is not read (zeroed), and the
@@ -416,6 +418,7 @@ int enqueue_grads(rmgr_ssim_hip_Context* c, uint32_t count, const typename F::Pa
 struct MultiF {
     typedef FamilyF Single;
     float range;
+    Window win;
     int validate(uint32_t count, const rmgr_ssim_hip_ParamsF* params, const void* out) const { return ssimf_validate(count, params, range, out); }
     static size_t pair_bytes(uint32_t scales, uint32_t n) { return (size_t)scales * n * sizeof(PairFDesc); }
     static size_t grad_bytes(uint32_t scales, uint32_t n) { return (size_t)scales * n * sizeof(GradFDesc); }
@@ -425,14 +428,17 @@ struct MultiF {
     hipError_t forward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, uint32_t n, uint32_t W, uint32_t H, uint32_t scales, bool wide, const double* w,
                        double* means, double* values) const
     {
-        return ssim_hip::launch_msssimf(reinterpret_cast<const PairFDesc*>(pairs), n, W, H, scales, wide, range, w, c->cu_count, c->xcd_count,
-                                        c->msf_partials, means, values, c->stream);
+        // as FamilyF::launch: windows of 11 taps on the kernels of msssimf_kernels.hip, smaller ones on kernels of their radius
+        return (win.radius == 5 ? ssim_hip::launch_msssimf_from : ssim_hip::launch_msssimk_from)(
+            0, win.radius, win.gf, reinterpret_cast<const PairFDesc*>(pairs), n, W, H, scales, wide, range, w, c->cu_count, c->xcd_count, c->msf_partials,
+            means, values, c->stream);
     }
     hipError_t backward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, const uint8_t* grads, uint32_t n, uint32_t W, uint32_t H, uint32_t scales,
                         const double* w, const double* means, const float* g_out, int which) const
     {
-        return ssim_hip::launch_msssimf_grad(reinterpret_cast<const PairFDesc*>(pairs), reinterpret_cast<const GradFDesc*>(grads), n, W, H, scales,
-                                             range, w, means, g_out, c->msf_coef, which, c->stream);
+        return (win.radius == 5 ? ssim_hip::launch_msssimf_grad_from : ssim_hip::launch_msssimk_grad_from)(
+            0, win.radius, win.gf, reinterpret_cast<const PairFDesc*>(pairs), reinterpret_cast<const GradFDesc*>(grads), n, W, H, scales, range, w, means,
+            g_out, c->msf_coef, which, c->stream);
     }
 };
 
@@ -440,6 +446,7 @@ struct MultiH {
     typedef FamilyH Single;
     uint32_t sampleType;
     float range;
+    Window win;
     int validate(uint32_t count, const rmgr_ssim_hip_Params16* params, const void* out) const { return ssimh_validate(count, params, sampleType, range, out); }
     static size_t pair_bytes(uint32_t scales, uint32_t n) { return (size_t)scales * n * sizeof(PairFDesc) + n * sizeof(PairHDesc); }
     static size_t grad_bytes(uint32_t scales, uint32_t n) { return (size_t)scales * n * sizeof(GradFDesc) + n * sizeof(GradHDesc); }
@@ -456,18 +463,18 @@ struct MultiH {
     hipError_t forward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, uint32_t n, uint32_t W, uint32_t H, uint32_t scales, bool wide, const double* w,
                        double* means, double* values) const
     {
-        return ssim_hip::launch_msssimh(reinterpret_cast<const PairHDesc*>(pairs + (size_t)scales * n * sizeof(PairFDesc)),
-                                        reinterpret_cast<const PairFDesc*>(pairs), n, W, H, scales, sample_type(sampleType), wide, range, w, c->cu_count,
-                                        c->xcd_count, c->msf_partials, means, values, c->stream);
+        return (win.radius == 5 ? ssim_hip::launch_msssimh : ssim_hip::launch_msssimhk)(reinterpret_cast<const PairHDesc*>(pairs + (size_t)scales * n * sizeof(PairFDesc)),
+                                        reinterpret_cast<const PairFDesc*>(pairs), n, W, H, scales, sample_type(sampleType), wide, range, win.radius,
+                                        win.gf, w, c->cu_count, c->xcd_count, c->msf_partials, means, values, c->stream);
     }
     hipError_t backward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, const uint8_t* grads, uint32_t n, uint32_t W, uint32_t H, uint32_t scales,
                         const double* w, const double* means, const float* g_out, int which) const
     {
-        return ssim_hip::launch_msssimh_grad(reinterpret_cast<const PairHDesc*>(pairs + (size_t)scales * n * sizeof(PairFDesc)),
+        return (win.radius == 5 ? ssim_hip::launch_msssimh_grad : ssim_hip::launch_msssimhk_grad)(reinterpret_cast<const PairHDesc*>(pairs + (size_t)scales * n * sizeof(PairFDesc)),
                                              reinterpret_cast<const PairFDesc*>(pairs),
                                              reinterpret_cast<const GradHDesc*>(grads + (size_t)scales * n * sizeof(GradFDesc)),
-                                             reinterpret_cast<const GradFDesc*>(grads), n, W, H, scales, sample_type(sampleType), range, w, means, g_out,
-                                             c->msf_coef, which, c->stream);
+                                             reinterpret_cast<const GradFDesc*>(grads), n, W, H, scales, sample_type(sampleType), range, win.radius, win.gf,
+                                             w, means, g_out, c->msf_coef, which, c->stream);
     }
 };
 
@@ -980,7 +987,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win_map_grad(rmgr_ssim_hip_Context* c, 
 rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
                                            rmgr_uint32_t scales, const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
 {
-    const MultiF fam = {dataRange};
+    const MultiF fam = {dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
     return rc ? rc : ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
 }
@@ -988,7 +995,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf(rmgr_ssim_hip_Context* c, rmgr_uint32
 rmgr_int32_t rmgr_ssim_hip_compute_msssimf_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
                                                   rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const MultiF fam = {dataRange};
+    const MultiF fam = {dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, msssim);
     return rc ? rc : ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
@@ -996,7 +1003,7 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssimf_device(rmgr_ssim_hip_Context* c, rmgr
 rmgr_int32_t rmgr_ssim_hip_compute_msssimf_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange,
                                                 rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const MultiF fam = {dataRange};
+    const MultiF fam = {dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, msssim);
     return rc ? rc : ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
@@ -1005,7 +1012,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_grad(rmgr_ssim_hip_Context* c, rmgr_u
                                                 rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
                                                 const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
 {
-    const MultiF fam = {dataRange};
+    const MultiF fam = {dataRange, default_window()};
     int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
     if (rc) return rc;
     if (scaleMeansDevice == NULL) return EINVAL;
@@ -1019,7 +1026,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh(rmgr_ssim_hip_Context* c, rmgr_uint32
                                            rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
                                            double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
 {
-    const MultiH fam = {sampleType, dataRange};
+    const MultiH fam = {sampleType, dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
     return rc ? rc : ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
 }
@@ -1028,7 +1035,7 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssimh_device(rmgr_ssim_hip_Context* c, rmgr
                                                   rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
                                                   float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const MultiH fam = {sampleType, dataRange};
+    const MultiH fam = {sampleType, dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, msssim);
     return rc ? rc : ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
@@ -1037,7 +1044,7 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssimh_host(rmgr_ssim_hip_Context* c, rmgr_u
                                                 rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
                                                 float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const MultiH fam = {sampleType, dataRange};
+    const MultiH fam = {sampleType, dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, msssim);
     return rc ? rc : ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
@@ -1047,9 +1054,93 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh_grad(rmgr_ssim_hip_Context* c, rmgr_u
                                                 const double* scaleMeansDevice, const float* gradOutDevice, const rmgr_ssim_hip_GradH* gradA,
                                                 const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
 {
-    const MultiH fam = {sampleType, dataRange};
+    const MultiH fam = {sampleType, dataRange, default_window()};
     int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
     if (rc) return rc;
+    if (scaleMeansDevice == NULL) return EINVAL;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    return ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);
+}
+
+// ---- the same under the caller's window: both run the same flow; the window is one more input of the family -----------------------------------
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const rmgr_ssim_hip_Window* window,
+                                           rmgr_uint32_t scales, const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
+{
+    MultiF fam = {dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                  rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    MultiF fam = {dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimf_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    MultiF fam = {dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_win_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
+                                                const rmgr_ssim_hip_GradF* gradA, const rmgr_ssim_hip_GradF* gradB) RMGR_NOEXCEPT
+{
+    MultiF fam = {dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    if (scaleMeansDevice == NULL) return EINVAL;
+    if ((rc = validate_grads(count, gradA, gradB))) return rc;
+    return ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                           rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales, const double* weights,
+                                           double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
+{
+    MultiH fam = {sampleType, dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimh_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                  rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales, const double* weights,
+                                                  float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    MultiH fam = {sampleType, dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssimh_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales, const double* weights,
+                                                float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    MultiH fam = {sampleType, dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssimh_win_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params16* params,
+                                                rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales, const double* weights,
+                                                const double* scaleMeansDevice, const float* gradOutDevice, const rmgr_ssim_hip_GradH* gradA,
+                                                const rmgr_ssim_hip_GradH* gradB) RMGR_NOEXCEPT
+{
+    MultiH fam = {sampleType, dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
     if (scaleMeansDevice == NULL) return EINVAL;
     if ((rc = validate_grads(count, gradA, gradB))) return rc;
     return ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);

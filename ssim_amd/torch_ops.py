@@ -44,7 +44,8 @@ ignores win_sigma): pytorch-msssim's win_size / win_sigma, torchmetrics' and piq
 filter_sigma, kornia's window_size, skimage's 7 x 7 box, the 3 x 3 box of monodepth-style losses.  The defaults (11, 1.5, "gaussian") take
 exactly the path above; anything else runs the _win entries of the float32 family (rmgr_ssim_hip_enqueue_ssimf_win, _ssimf_win_grad,
 _ssimf_win_map_grad), the small windows on kernels of their own radius.  Edges are clamped for every window: where monodepth-style code
-reflects, the interior is identical and the outermost (win_size - 1) / 2 pixels differ.  ms_ssim keeps the fixed window for now.
+reflects, the interior is identical and the outermost (win_size - 1) / 2 pixels differ.  ms_ssim, ms_ssim_amp and MSSSIMLoss take the same three keywords, at every dtype their
+tensors may have: one window for every scale (the msssimf_win and msssimh_win entries).
 
     photo = 0.85 * (1 - ssim_map(warped, target, win_size=3, window="uniform")) / 2 + 0.15 * (warped - target).abs()
 
@@ -462,7 +463,7 @@ def _make_ms_function():
 
     class _MSSSIM(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, y, data_range, scales, weights):
+        def forward(ctx, x, y, data_range, scales, weights, win):
             lead = x.shape[:-2]
             params, n = _params(x, y)
             values = torch.empty(n, dtype=torch.float64, device=x.device)
@@ -473,13 +474,15 @@ def _make_ms_function():
                     work.wait_stream(cur)
                 st = _sample_type(torch, x.dtype)
                 if st is None:
-                    _context(x.device, work).enqueue_msssimf(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights)
+                    _context(x.device, work).enqueue_msssimf(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights,
+                                                             **_win_kw(win))
                 else:
-                    _context(x.device, work).enqueue_msssimh(params, n, data_range, st, values.data_ptr(), means.data_ptr(), scales, weights)
+                    _context(x.device, work).enqueue_msssimh(params, n, data_range, st, values.data_ptr(), means.data_ptr(), scales, weights,
+                                                             **_win_kw(win))
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y, means)
-            ctx.data_range, ctx.scales, ctx.weights = data_range, scales, weights
+            ctx.data_range, ctx.scales, ctx.weights, ctx.win = data_range, scales, weights, win
             return values.to(torch.float32).reshape(lead)
 
         @staticmethod
@@ -489,7 +492,7 @@ def _make_ms_function():
             h, w = x.shape[-2], x.shape[-1]
             want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             if not (want_x or want_y):
-                return None, None, None, None, None
+                return None, None, None, None, None, None
             params, n = _params(x, y)
             g = grad_out.to(torch.float32).reshape(-1).contiguous()
             gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
@@ -502,13 +505,14 @@ def _make_ms_function():
                 ga = _grad_planes(gx, n, h, w) if want_x else None
                 gb = _grad_planes(gy, n, h, w) if want_y else None
                 if st is None:
-                    _context(x.device, work).enqueue_msssimf_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales, ctx.weights)
+                    _context(x.device, work).enqueue_msssimf_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales, ctx.weights,
+                                                                  **_win_kw(ctx.win))
                 else:
                     _context(x.device, work).enqueue_msssimh_grad(params, n, ctx.data_range, st, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales,
-                                                                  ctx.weights)
+                                                                  ctx.weights, **_win_kw(ctx.win))
                 if work is not cur:
                     cur.wait_stream(work)
-            return gx, gy, None, None, None
+            return gx, gy, None, None, None, None
 
     return _MSSSIM
 
@@ -519,52 +523,62 @@ def _is_half_pair(x, y):
     return isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.dtype == y.dtype and x.dtype in (torch.float16, torch.bfloat16)
 
 
-def _ms_ssim(x, y, r, scales, weights):
+def _ms_ssim(x, y, r, scales, weights, win):
     global _ms_function
     scales, w = _check_scales(scales, weights)
     if _ms_function is None:
         _ms_function = _make_ms_function()
-    return _ms_function.apply(x, y, r, scales, w)
+    return _ms_function.apply(x, y, r, scales, w, win)
 
 
-def ms_ssim(x, y, data_range=1.0, scales=5, weights=None):
+def ms_ssim(x, y, data_range=1.0, scales=5, weights=None, win_size=11, win_sigma=1.5, window="gaussian"):
     """Per-plane multi-scale SSIM of two float32 GPU tensors of identical shape (..., H, W), any strides (each plane is addressed in
     place, no copy): a float32 tensor of shape x.shape[:-2].  weights None: Wang's five (scales must be 5); else `scales` finite weights
     >= 0.  Differentiable with respect to x, y or both; the gradient is computed only for the inputs that need it, from x, y and the
     (planes, scales, 2) float64 per-scale means the forward keeps.  TypeError / ValueError as ssim(), plus ValueError for scales outside
     1 .. 8, a wrong number of weights, a negative or non-finite weight (TypeError: scales is not an int).  float16 and bfloat16 tensors
     are a TypeError here, on any device: tests/tools/ssimh_torch_checks.py and tests/test_ssimh_cpu.py pin that refusal from the time
-    there was no 16-bit path.  ms_ssim_amp() and MSSSIMLoss take them."""
+    there was no 16-bit path.  ms_ssim_amp() and MSSSIMLoss take them.
+    The window: win_size, win_sigma and window are ssim()'s keywords with ssim()'s errors, and mean the same window at EVERY scale
+    (rmgr_ssim_hip_enqueue_msssimf_win, _msssimf_win_grad; pytorch-msssim's ms_ssim(win_size, win_sigma)); the defaults are the engine's
+    window and take exactly the path without these arguments.  Planes smaller than the window at coarse scales clamp."""
     if _is_half_pair(x, y):
         raise TypeError("ms_ssim: float32 tensors expected, got %s; ms_ssim_amp() and MSSSIMLoss take float16 / bfloat16 tensors" % (x.dtype,))
-    return _ms_ssim(x, y, _check(x, y, data_range), scales, weights)
+    win = _window(x, y, win_size, win_sigma, window, "ms_ssim", fixed16=False)
+    return _ms_ssim(x, y, _check(x, y, data_range), scales, weights, win)
 
 
-def ms_ssim_amp(x, y, data_range=1.0, scales=5, weights=None):
+def ms_ssim_amp(x, y, data_range=1.0, scales=5, weights=None, win_size=11, win_sigma=1.5, window="gaussian"):
     """ms_ssim() for tensors as they come under mixed precision: two GPU tensors of identical shape (..., H, W), both float32, both float16
     or both bfloat16, any strides (each plane is addressed in place, no copy or widening): a float32 tensor of shape x.shape[:-2] at every
     input dtype.  float32 tensors: exactly ms_ssim().  float16 and bfloat16: the value has the bits of ms_ssim(x.float(), y.float()),
     the gradient has the inputs' dtype and is that call's float32 gradient rounded once (see the top of this file for autocast and loss
     scaling); saved for the backward are x, y and the float64 means.  Errors: as ms_ssim(), and -- unlike ssim(), where every CPU tensor
     is a ValueError -- two float16 or two bfloat16 CPU tensors are a TypeError: 16-bit tensors are taken on a GPU only (one of the two
-    on a GPU: the ValueError)."""
+    on a GPU: the ValueError).  win_size, win_sigma, window: as ms_ssim(), at every input dtype: with float16 and bfloat16 tensors
+    (rmgr_ssim_hip_enqueue_msssimh_win, _msssimh_win_grad) the value has the bits of ms_ssim(x.float(), y.float(), win_size=...) under the
+    same window and the gradient is that call's, rounded once."""
+    win = _window(x, y, win_size, win_sigma, window, "ms_ssim_amp", fixed16=False)
     if _is_half_pair(x, y) and not x.is_cuda and not y.is_cuda:
         raise TypeError("ms_ssim_amp: float16 / bfloat16 tensors are taken on a GPU only, got %s on %s and %s" % (x.dtype, x.device, y.device))
-    return _ms_ssim(x, y, _check(x, y, data_range, half=True), scales, weights)
+    return _ms_ssim(x, y, _check(x, y, data_range, half=True), scales, weights, win)
 
 
 class MSSSIMLoss(object):
     """1 - ms_ssim_amp(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per plane).  A plain callable:
-    it has no parameters.  float32, float16 or bfloat16 tensors, as ms_ssim_amp(); the loss is float32 at every input dtype."""
+    it has no parameters.  float32, float16 or bfloat16 tensors, as ms_ssim_amp(); the loss is float32 at every input dtype.  win_size,
+    win_sigma, window: the window of every scale, as ms_ssim(), checked here; GPU tensors take it at every dtype."""
 
-    def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean"):
+    def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean", win_size=11, win_sigma=1.5, window="gaussian"):
         if reduction not in ("mean", "none"):
             raise ValueError("MSSSIMLoss: reduction must be 'mean' or 'none', got %r" % (reduction,))
         _check_scales(scales, weights)
+        _window(None, None, win_size, win_sigma, window, "MSSSIMLoss", fixed16=False)
         self.data_range, self.scales, self.weights, self.reduction = data_range, scales, weights, reduction
+        self.win_size, self.win_sigma, self.window = win_size, win_sigma, window
 
     def __call__(self, x, y):
-        loss = 1.0 - ms_ssim_amp(x, y, self.data_range, self.scales, self.weights)
+        loss = 1.0 - ms_ssim_amp(x, y, self.data_range, self.scales, self.weights, self.win_size, self.win_sigma, self.window)
         return loss.mean() if self.reduction == "mean" else loss
 
 
