@@ -21,8 +21,8 @@ lib: $(OUT)/librmgr-ssim-hip.so $(OUT)/librmgr-ssim-hip-double.so $(OUT)/librmgr
 
 # The objects both flavours share: kernels, the C ABI's host layer apart from ssim_context (the only one that reads
 # RMGR_SSIM_USE_DOUBLE: $(OBJ)/ssim_context.o / ssim_context_double.o), the drop-in layer.
-ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/msssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssimhk_kernels.o $(OBJ)/msssimk_kernels.o $(OBJ)/msssimhk_kernels.o $(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o $(OBJ)/msssim3f_kernels.o $(OBJ)/msssim3h_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_volumes_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
-HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_flow.h $(SRC)/ssim3_flow.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/msssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimhk_kernels.h $(SRC)/msssimk_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/msssim3f_kernels.h $(SRC)/msssim3h_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
+ABI_OBJS := $(OBJ)/ssim_kernels.o $(OBJ)/ssim_probe.o $(OBJ)/msssim_kernels.o $(OBJ)/ssim16_kernels.o $(OBJ)/ssimf_kernels.o $(OBJ)/msssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/msssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssimk_kernels.o $(OBJ)/ssimhk_kernels.o $(OBJ)/msssimk_kernels.o $(OBJ)/msssimhk_kernels.o $(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o $(OBJ)/msssim3f_kernels.o $(OBJ)/msssim3h_kernels.o $(OBJ)/msssim3k_kernels.o $(OBJ)/msssim3hk_kernels.o $(OBJ)/ssim_hip_abi.o $(OBJ)/ssim_samples_abi.o $(OBJ)/ssim_volumes_abi.o $(OBJ)/ssim_comm.o $(OBJ)/ssim_tune.o $(OBJ)/ssim_dropin.o
+HOST_HDRS := $(SRC)/ssim_context.h $(SRC)/ssim_flow.h $(SRC)/ssim3_flow.h $(SRC)/ssim_kernels.h $(SRC)/msssim_kernels.h $(SRC)/ssim16_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/msssimf_kernels.h $(SRC)/ssimh_kernels.h $(SRC)/msssimh_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimhk_kernels.h $(SRC)/msssimk_kernels.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/msssim3f_kernels.h $(SRC)/msssim3h_kernels.h $(SRC)/msssim3k_kernels.h $(SRC)/msssim3hk_kernels.h include/rmgr/ssim-hip.h include/rmgr/ssim.h
 
 # Static flavour under the reference's archive name (CMakeLists.txt:205): the same objects, linked into ONE relocatable
 # object whose only global symbols are the API (the shared libraries' export list has no counterpart for archives: the
@@ -91,8 +91,8 @@ $(OBJ)/ssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssim
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# The volume (3-D) family: seven kernel files, one per group of entry points, whose tests count and budget their kernels.  The slice
-# walk and its adjoint are written once, in ssim3_walk.h, which every one of the seven includes; the same flags as the 2-D float files
+# The volume (3-D) family: nine kernel files, one per group of entry points, whose tests count and budget their kernels.  The slice
+# walk and its adjoint are written once, in ssim3_walk.h, which every one of the nine includes; the same flags as the 2-D float files
 # (-ffp-contract=off: tests/ssim3f_model.py and tests/ssim3k_model.py restate the arithmetic operation by operation).
 #   ssim3f   float32 volumes under the 11-tap window and its gradient (rmgr_ssim_hip_*_ssim3f*); the reduction and the planner
 #   ssim3w   gradient of the map for a per-voxel upstream gradient (rmgr_ssim_hip_enqueue_ssim3f_map_grad)
@@ -101,8 +101,10 @@ $(OBJ)/ssimf_kernels.o $(OBJ)/ssimh_kernels.o $(OBJ)/ssimw_kernels.o $(OBJ)/ssim
 #   ssim3hk  float16 / bfloat16 volumes under a window of 3, 5, 7 or 9 taps (rmgr_ssim_hip_*_ssim3h_win*)
 #   msssim3f multi-scale SSIM of float32 volumes and its gradient (rmgr_ssim_hip_*_msssim3f*); the pyramid, the product, k_s
 #   msssim3h multi-scale SSIM of float16 / bfloat16 volumes (rmgr_ssim_hip_*_msssim3h*): scale 0's kernels
-SSIM3_HDRS := $(SRC)/ssim3_walk.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/msssim3f_kernels.h $(SRC)/msssim3h_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
-$(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o $(OBJ)/msssim3f_kernels.o $(OBJ)/msssim3h_kernels.o: $(OBJ)/%.o: $(SRC)/%.hip $(SSIM3_HDRS)
+#   msssim3k a scale of multi-scale SSIM of float32 volumes under a window of 3, 5, 7 or 9 taps (rmgr_ssim_hip_*_msssim3f_win*)
+#   msssim3hk scale 0 of multi-scale SSIM of float16 / bfloat16 volumes under such a window (rmgr_ssim_hip_*_msssim3h_win*)
+SSIM3_HDRS := $(SRC)/ssim3_walk.h $(SRC)/ssim3f_kernels.h $(SRC)/ssim3w_kernels.h $(SRC)/ssim3h_kernels.h $(SRC)/ssim3k_kernels.h $(SRC)/ssim3hk_kernels.h $(SRC)/msssim3f_kernels.h $(SRC)/msssim3h_kernels.h $(SRC)/msssim3k_kernels.h $(SRC)/msssim3hk_kernels.h $(SRC)/ssimk_kernels.h $(SRC)/ssimw_kernels.h $(SRC)/ssimf_kernels.h $(SRC)/ssimh_kernels.h
+$(OBJ)/ssim3f_kernels.o $(OBJ)/ssim3w_kernels.o $(OBJ)/ssim3h_kernels.o $(OBJ)/ssim3k_kernels.o $(OBJ)/ssim3hk_kernels.o $(OBJ)/msssim3f_kernels.o $(OBJ)/msssim3h_kernels.o $(OBJ)/msssim3k_kernels.o $(OBJ)/msssim3hk_kernels.o: $(OBJ)/%.o: $(SRC)/%.hip $(SSIM3_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

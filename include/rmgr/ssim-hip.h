@@ -54,6 +54,9 @@
  *                                      SSIM of float32 VOLUMES and its gradient: no reference counterpart (definition below)
  *   rmgr_ssim_hip_enqueue_msssim3h, rmgr_ssim_hip_compute_msssim3h_device / _host, rmgr_ssim_hip_enqueue_msssim3h_grad   multi-scale
  *                                      SSIM of float16 / bfloat16 VOLUMES and its gradient: no reference counterpart (definition below)
+ *   rmgr_ssim_hip_enqueue_msssim3f_win, rmgr_ssim_hip_compute_msssim3f_win_device / _host, rmgr_ssim_hip_enqueue_msssim3f_win_grad and
+ *   the four msssim3h_win counterparts         the multi-scale float32 and float16 / bfloat16 VOLUME entries under a caller-chosen
+ *                                      window: no reference counterpart (definition below)
  *
  * All functions return 0 or an errno value (EINVAL, ENOMEM, ECHILD = a HIP call failed,
  * ENODEV = no gfx950 device / extension not usable), exactly like the reference's API; the multi-GPU
@@ -870,8 +873,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssimh_win_map_grad(rmgr_ssim_hip_Context* ctx
  * without _win.  Additional EINVAL, checked after that entry's data range, pairs, scales and weights, before its other pointers and before
  * the context or any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not finite or not > 0.
  *
- * Not in this interface: the uint8 multi-scale entries (rmgr_ssim_hip_compute_msssim_*) keep the reference's window.  Follow-up:
- * multi-scale SSIM of volumes (the msssim3f and msssim3h entries) keeps the fixed window {11, GAUSSIAN, 1.5f}.
+ * Not in this interface: the uint8 multi-scale entries (rmgr_ssim_hip_compute_msssim_*) keep the reference's window.  Multi-scale SSIM
+ * of volumes under a caller-chosen window: the msssim3f_win and msssim3h_win entries, last of the volume entries.
  */
 rmgr_int32_t rmgr_ssim_hip_enqueue_msssimf_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_ParamsF* params,
                                                float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
@@ -1241,8 +1244,8 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win_map_grad(rmgr_ssim_hip_Context* ct
  * Against pytorch-msssim's MS_SSIM(spatial_dims=3): that one uses a valid window and zero-padded pooling and refuses small sides; this
  * one clamps the window at the borders, pools with clamped coordinates and runs down to 1 x 1 x 1, so values are close, not equal.
  *
- * float16 / bfloat16 volumes: the msssim3h entries below.  Follow-ups, not in this interface: a caller-chosen window for the multi-scale
- * form, and a multi-scale map gradient.
+ * float16 / bfloat16 volumes: the msssim3h entries below.  A caller-chosen window for the multi-scale form: the msssim3f_win and
+ * msssim3h_win entries, further below.  Follow-up, not in this interface: a multi-scale map gradient.
  */
 rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
                                             float dataRange, rmgr_uint32_t scales, const double* weights, double* valuesDevice,
@@ -1308,6 +1311,80 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h_grad(rmgr_ssim_hip_Context* ctx, rmg
                                                  rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
                                                  const double* scaleMeansDevice, const float* gradOutDevice,
                                                  const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
+
+/*
+ * MULTI-SCALE SSIM of float32 and of float16 / bfloat16 VOLUMES under a caller-chosen WINDOW: the four entries of each multi-scale
+ * volume family -- _enqueue_msssim3f, _compute_msssim3f_device, _compute_msssim3f_host, _enqueue_msssim3f_grad and their msssim3h
+ * counterparts -- with one more argument, `window`, after dataRange: the rmgr_ssim_hip_Window of the single-scale _win entries,
+ * unchanged.  What pytorch-msssim calls MS_SSIM(spatial_dims=3, win_size, win_sigma); MONAI and torchmetrics expose the same window.  No
+ * reference counterpart: tests/msssim3k_model.py restates it in float64, the gradient included.  Additions only:
+ * RMGR_SSIM_HIP_ABI_VERSION stays 6.
+ *
+ * It is the definition of rmgr_ssim_hip_enqueue_msssim3f / _enqueue_msssim3f_grad (of _enqueue_msssim3h / _enqueue_msssim3h_grad) with 5
+ * replaced by R = (size - 1) / 2 ON EVERY AXIS AT EVERY SCALE:
+ *   Window   size 3, 5, 7, 9 or 11 taps on all three axes, GAUSSIAN of any finite sigma > 0 or UNIFORM; the taps of
+ *            rmgr_ssim_hip_enqueue_ssim3f_win, bit for bit.  The SAME window -- size and taps -- applies to every scale of the pyramid, as
+ *            in pytorch-msssim; it is not rescaled with the volumes.  A NULL window means {11, GAUSSIAN, 1.5f}.
+ *   Per scale  mu, s_aa, s_bb, s_ab of a scale's volumes are those of rmgr_ssim_hip_enqueue_ssim3f_win under the window: separable, edges
+ *            clamped.  A coarse volume smaller than the window clamps like any other, down to 1 x 1 x 1: every tap then reads the same
+ *            few samples and the adjoint's tails (tail[d] = g_d + ... + g_R, summed in double and rounded once) fold onto them.  The
+ *            pyramid halves all three axes, so a 12-frame clip has depth 12, 6, 3, 2, 1: from scale 2 on an 11-tap window is nothing but
+ *            border along z, which is what a window of 7 or 3 taps is for.
+ *   Unchanged, word for word  the clamped 2 x 2 x 2 pyramid and its fp32 order; C1 and C2; cs = A2 / B2 and ssim = A1 A2 / (B1 B2); the
+ *            fp64 means over double(W_s) * double(H_s) * double(D_s); the ReLU'd weighted product in double; k_s; the local gradient
+ *            Gt(k d_mu) + 2 a Gt(k d_aa) + b Gt(k d_ab) with Gt the adjoint of the clamped window; the adjoint of the clamped box filter,
+ *            0.125 c g_{s+1}(x >> 1, y >> 1, z >> 1), one more rounding per scale; one centre per volume per scale with its |c| <=
+ *            dataRange test; the 16 x 16 x 8 cells at absolute positions; +0 from a scale whose k_s is 0.  None of them depends on the
+ *            radius.
+ *   16-bit samples  as the msssim3h entries define them: the value and both means of every scale have the BITS of the msssim3f_win entry
+ *            on the exactly widened volumes under the same window; each gradient voxel is the float32 value _enqueue_msssim3f_win_grad
+ *            would store for the widened volumes, rounded ONCE, to nearest-even, into the inputs' encoding.  There is no tolerance in
+ *            this contract.  gradOutDevice stays float32, so a loss scale arrives before the single rounding.
+ *   Identity with the fixed-window entries  a NULL window and {11, GAUSSIAN, 1.5f} give the BITS of the entries without _win: values,
+ *            per-scale means and gradients.
+ *   Determinism  every promise of msssim3f / msssim3h: the same bits alone or anywhere in a batch, at any z-chunk depth of any scale,
+ *            after any sub-batch split, through every entry point, on every call, with one gradient or both, and for any view of the
+ *            same voxels.  One writer per gradient voxel, no floating-point atomics.
+ *   Reach    a window reads nothing beyond its radius at any scale; it is not a zero-padded 11-tap window.
+ *   Accuracy measured per window against the float64 model: tests/msssim3k_model.py (EMU, ODD_EMU) and DESIGN.md section 27.
+ *
+ * Arguments, EINVAL / ENODEV rules, sub-batches, scratch (it does not depend on the window) and stream behaviour are those of the entry
+ * without _win.  Additional EINVAL, checked after that entry's sample type, data range, pairs, scales and weights, before its other
+ * pointers and before the context or any device is touched: a size outside the five, an unknown kind, a Gaussian sigma that is not
+ * finite or not > 0.  _host without a device: ENODEV.
+ *
+ * Follow-up, not in this interface: a multi-scale map gradient.
+ */
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_win_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                       float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                       const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_win_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                     float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                     const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f_win_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                     float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                     const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
+                                                     const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h_win(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                rmgr_uint32_t scales, const double* weights, double* valuesDevice,
+                                                double* scaleMeansDevice) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3h_win_device(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                       rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                       rmgr_uint32_t scales, const double* weights, float* msssim,
+                                                       double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3h_win_host(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                     rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                     rmgr_uint32_t scales, const double* weights, float* msssim,
+                                                     double* scaleMeans) RMGR_NOEXCEPT;
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h_win_grad(rmgr_ssim_hip_Context* ctx, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                     rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window,
+                                                     rmgr_uint32_t scales, const double* weights, const double* scaleMeansDevice,
+                                                     const float* gradOutDevice, const rmgr_ssim_hip_Grad3H* gradA,
+                                                     const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT;
 
 /*
  * Multi-GPU exchange without any other runtime: one process per GPU, images sharded by rank (no image

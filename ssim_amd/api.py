@@ -240,6 +240,10 @@ C_SYMBOLS = [
     "rmgr_ssim_hip_enqueue_ssim3h_win_grad", "rmgr_ssim_hip_enqueue_ssim3h_win_map_grad",
     "rmgr_ssim_hip_enqueue_msssim3f", "rmgr_ssim_hip_compute_msssim3f_device", "rmgr_ssim_hip_compute_msssim3f_host", "rmgr_ssim_hip_enqueue_msssim3f_grad",
     "rmgr_ssim_hip_enqueue_msssim3h", "rmgr_ssim_hip_compute_msssim3h_device", "rmgr_ssim_hip_compute_msssim3h_host", "rmgr_ssim_hip_enqueue_msssim3h_grad",
+    "rmgr_ssim_hip_enqueue_msssim3f_win", "rmgr_ssim_hip_compute_msssim3f_win_device", "rmgr_ssim_hip_compute_msssim3f_win_host",
+    "rmgr_ssim_hip_enqueue_msssim3f_win_grad",
+    "rmgr_ssim_hip_enqueue_msssim3h_win", "rmgr_ssim_hip_compute_msssim3h_win_device", "rmgr_ssim_hip_compute_msssim3h_win_host",
+    "rmgr_ssim_hip_enqueue_msssim3h_win_grad",
 ]
 # non-inline C++ entry points of the reference, Itanium-mangled
 CXX_SYMBOLS = [
@@ -373,6 +377,14 @@ def load_library(path=None):
         "rmgr_ssim_hip_compute_msssimh_device": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimh_host": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_enqueue_msssimh_grad": [vp, u32, ctypes.POINTER(Params16), u32, ctypes.c_float, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(GradH), ctypes.POINTER(GradH)],
+        "rmgr_ssim_hip_enqueue_msssim3f_win": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
+        "rmgr_ssim_hip_compute_msssim3f_win_device": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssim3f_win_host": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_msssim3f_win_grad": [vp, u32, ctypes.POINTER(Params3F), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(Grad3F), ctypes.POINTER(Grad3F)],
+        "rmgr_ssim_hip_enqueue_msssim3h_win": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
+        "rmgr_ssim_hip_compute_msssim3h_win_device": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_compute_msssim3h_win_host": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
+        "rmgr_ssim_hip_enqueue_msssim3h_win_grad": [vp, u32, ctypes.POINTER(Params3H), u32, ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp, ctypes.POINTER(Grad3H), ctypes.POINTER(Grad3H)],
         "rmgr_ssim_hip_enqueue_msssimf_win": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), vp, vp],
         "rmgr_ssim_hip_compute_msssimf_win_device": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
         "rmgr_ssim_hip_compute_msssimf_win_host": [vp, u32, ctypes.POINTER(ParamsF), ctypes.c_float, PW, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)],
@@ -1018,27 +1030,30 @@ def compute_msssimf_batch(pairs, data_range, scales=5, weights=None, per_scale=F
                          window)
 
 
-def compute_msssim3f(a, b, data_range, scales=5, weights=None, per_scale=False, ctx=None):
+def compute_msssim3f(a, b, data_range, scales=5, weights=None, per_scale=False, ctx=None, window=None):
     """Multi-scale SSIM of two D x H x W float32 host volumes at `data_range` (any strides numpy can express, negative ones included)
-    through rmgr_ssim_hip_compute_msssim3f_host: the 11-tap window on all three axes, all three axes halved from scale to scale.  weights
+    through rmgr_ssim_hip_compute_msssim3f_host: the 11-tap window on all three axes, all three axes halved from scale to scale; window (a
+    Window, make_window): through rmgr_ssim_hip_compute_msssim3f_win_host under that window on all three axes at every scale.  weights
     None: Wang's five (scales must be 5).  Returns a float32, and with per_scale=True also a (scales, 2) float64 array of
-    [scale]{mcs, mssim}."""
+    [scale]{mcs, mssim}.  TypeError: a window that is neither None nor a Window."""
     a, b = _f32_volume(a), _f32_volume(b)
     assert a.shape == b.shape
     params = (Params3F * 1)()
     params[0] = _params3f_of(a, b)
-    r = _msssimf_call("rmgr_ssim_hip_compute_msssim3f_host", ctx.handle if ctx is not None else None, params, 1, data_range, scales, weights, per_scale)
+    r = _msssimf_call("rmgr_ssim_hip_compute_msssim3f_host", ctx.handle if ctx is not None else None, params, 1, data_range, scales, weights, per_scale,
+                      window)
     return (r[0][0], r[1][0]) if per_scale else r[0]
 
 
-def compute_msssim3f_batch(pairs, data_range, scales=5, weights=None, per_scale=False, ctx=None):
+def compute_msssim3f_batch(pairs, data_range, scales=5, weights=None, per_scale=False, ctx=None, window=None):
     """compute_msssim3f() of many host pairs of one size in one call: a float32 array (and a (count, scales, 2) array with per_scale)."""
     pairs = [(_f32_volume(a), _f32_volume(b)) for a, b in pairs]
     n = len(pairs)
     params = (Params3F * max(n, 1))()
     for i, (a, b) in enumerate(pairs):
         params[i] = _params3f_of(a, b)
-    return _msssimf_call("rmgr_ssim_hip_compute_msssim3f_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale)
+    return _msssimf_call("rmgr_ssim_hip_compute_msssim3f_host", ctx.handle if ctx is not None else None, params, n, data_range, scales, weights, per_scale,
+                         window)
 
 
 def _msssimh_call(fn_name, handle, params, count, code, data_range, scales, weights, per_scale, window=None):
@@ -1087,19 +1102,21 @@ def compute_msssimh_batch(pairs, data_range, sample_type=None, scales=5, weights
                          window)
 
 
-def compute_msssim3h(a, b, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
+def compute_msssim3h(a, b, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None, window=None):
     """Multi-scale SSIM of two D x H x W host volumes of float16 or bfloat16 samples at `data_range` (any strides numpy can express,
-    negative ones included) through rmgr_ssim_hip_compute_msssim3h_host.  Arrays and sample_type: as compute_ssim3h (np.float16 arrays
+    negative ones included) through rmgr_ssim_hip_compute_msssim3h_host; window (a Window, make_window): through
+    rmgr_ssim_hip_compute_msssim3h_win_host under that window at every scale.  Arrays and sample_type: as compute_ssim3h (np.float16 arrays
     select float16; np.uint16 arrays carry bit patterns and need sample_type), with its errors.  weights None: Wang's five (scales must be
     5).  Returns a float32, and with per_scale=True also a (scales, 2) float64 array of [scale]{mcs, mssim}."""
     a, b, code = _h_volume_pair(a, b, sample_type)
     params = (Params3H * 1)()
     params[0] = _params3h_of(a, b)
-    r = _msssimh_call("rmgr_ssim_hip_compute_msssim3h_host", ctx.handle if ctx is not None else None, params, 1, code, data_range, scales, weights, per_scale)
+    r = _msssimh_call("rmgr_ssim_hip_compute_msssim3h_host", ctx.handle if ctx is not None else None, params, 1, code, data_range, scales, weights, per_scale,
+                      window)
     return (r[0][0], r[1][0]) if per_scale else r[0]
 
 
-def compute_msssim3h_batch(pairs, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None):
+def compute_msssim3h_batch(pairs, data_range, sample_type=None, scales=5, weights=None, per_scale=False, ctx=None, window=None):
     """compute_msssim3h() of many host pairs of one size and one sample type in one call: a float32 array (and a (count, scales, 2) array
     with per_scale)."""
     pairs = [_h_volume_pair(a, b, sample_type) for a, b in pairs]
@@ -1111,7 +1128,8 @@ def compute_msssim3h_batch(pairs, data_range, sample_type=None, scales=5, weight
     params = (Params3H * max(n, 1))()
     for i, (a, b, _) in enumerate(pairs):
         params[i] = _params3h_of(a, b)
-    return _msssimh_call("rmgr_ssim_hip_compute_msssim3h_host", ctx.handle if ctx is not None else None, params, n, code, data_range, scales, weights, per_scale)
+    return _msssimh_call("rmgr_ssim_hip_compute_msssim3h_host", ctx.handle if ctx is not None else None, params, n, code, data_range, scales, weights, per_scale,
+                         window)
 
 
 class DeviceBuffer(object):
@@ -1448,22 +1466,34 @@ class Context(object):
                 self.handle, count, params_array, data_range, _window_ref(window), scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr,
                 grad_a, grad_b))
 
-    def msssim3f_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False):
-        """MS-SSIM of `count` device-resident pairs of float32 volumes (a Params3F array) through rmgr_ssim_hip_compute_msssim3f_device: a
-        float32 array, and with per_scale=True also a (count, scales, 2) float64 array of [pair][scale]{mcs, mssim}."""
-        return _msssimf_call("rmgr_ssim_hip_compute_msssim3f_device", self.handle, params_array, count, data_range, scales, weights, per_scale)
+    def msssim3f_device(self, params_array, count, data_range, scales=5, weights=None, per_scale=False, window=None):
+        """MS-SSIM of `count` device-resident pairs of float32 volumes (a Params3F array) through rmgr_ssim_hip_compute_msssim3f_device
+        (window: _msssim3f_win_device): a float32 array, and with per_scale=True also a (count, scales, 2) float64 array of
+        [pair][scale]{mcs, mssim}."""
+        return _msssimf_call("rmgr_ssim_hip_compute_msssim3f_device", self.handle, params_array, count, data_range, scales, weights, per_scale, window)
 
-    def enqueue_msssim3f(self, params_array, count, data_range, values_dev_ptr, means_dev_ptr, scales=5, weights=None):
-        """rmgr_ssim_hip_enqueue_msssim3f: per-pair fp64 values and count x scales x 2 fp64 means into device memory, asynchronously on the
-        context's stream."""
-        _check("rmgr_ssim_hip_enqueue_msssim3f", self.lib.rmgr_ssim_hip_enqueue_msssim3f(
-            self.handle, count, params_array, data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+    def enqueue_msssim3f(self, params_array, count, data_range, values_dev_ptr, means_dev_ptr, scales=5, weights=None, window=None):
+        """rmgr_ssim_hip_enqueue_msssim3f (window: _msssim3f_win): per-pair fp64 values and count x scales x 2 fp64 means into device memory,
+        asynchronously on the context's stream."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_msssim3f", self.lib.rmgr_ssim_hip_enqueue_msssim3f(
+                self.handle, count, params_array, data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+        else:
+            _check("rmgr_ssim_hip_enqueue_msssim3f_win", self.lib.rmgr_ssim_hip_enqueue_msssim3f_win(
+                self.handle, count, params_array, data_range, _window_ref(window), scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
 
-    def enqueue_msssim3f_grad(self, params_array, count, data_range, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5, weights=None):
-        """rmgr_ssim_hip_enqueue_msssim3f_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes, from the forward's
-        means (device memory), into the volumes the Grad3F arrays describe; asynchronous on the context's stream, no host synchronisation."""
-        _check("rmgr_ssim_hip_enqueue_msssim3f_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3f_grad(
-            self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
+    def enqueue_msssim3f_grad(self, params_array, count, data_range, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5, weights=None,
+                              window=None):
+        """rmgr_ssim_hip_enqueue_msssim3f_grad (window: _msssim3f_win_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs of
+        volumes, from the forward's means (device memory), into the volumes the Grad3F arrays describe; asynchronous on the context's
+        stream, no host synchronisation."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_msssim3f_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3f_grad(
+                self.handle, count, params_array, data_range, scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_msssim3f_win_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3f_win_grad(
+                self.handle, count, params_array, data_range, _window_ref(window), scales, _weights_array(weights), means_dev_ptr, grad_out_dev_ptr,
+                grad_a, grad_b))
 
     def msssimh_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False, window=None):
         """MS-SSIM of `count` device-resident float16 / bfloat16 pairs (a Params16 array) through rmgr_ssim_hip_compute_msssimh_device
@@ -1497,26 +1527,37 @@ class Context(object):
                 self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), scales, _weights_array(weights),
                 means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
 
-    def msssim3h_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False):
+    def msssim3h_device(self, params_array, count, data_range, sample_type, scales=5, weights=None, per_scale=False, window=None):
         """MS-SSIM of `count` device-resident pairs of float16 / bfloat16 volumes (a Params3H array) through
-        rmgr_ssim_hip_compute_msssim3h_device: a float32 array, and with per_scale=True also a (count, scales, 2) float64 array."""
+        rmgr_ssim_hip_compute_msssim3h_device (window: _msssim3h_win_device): a float32 array, and with per_scale=True also a
+        (count, scales, 2) float64 array."""
         return _msssimh_call("rmgr_ssim_hip_compute_msssim3h_device", self.handle, params_array, count, sample_type_code(sample_type), data_range,
-                             scales, weights, per_scale)
+                             scales, weights, per_scale, window)
 
-    def enqueue_msssim3h(self, params_array, count, data_range, sample_type, values_dev_ptr, means_dev_ptr, scales=5, weights=None):
-        """rmgr_ssim_hip_enqueue_msssim3h: per-pair fp64 values and count x scales x 2 fp64 means into device memory, asynchronously on the
-        context's stream."""
-        _check("rmgr_ssim_hip_enqueue_msssim3h", self.lib.rmgr_ssim_hip_enqueue_msssim3h(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+    def enqueue_msssim3h(self, params_array, count, data_range, sample_type, values_dev_ptr, means_dev_ptr, scales=5, weights=None, window=None):
+        """rmgr_ssim_hip_enqueue_msssim3h (window: _msssim3h_win): per-pair fp64 values and count x scales x 2 fp64 means into device memory,
+        asynchronously on the context's stream."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_msssim3h", self.lib.rmgr_ssim_hip_enqueue_msssim3h(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), values_dev_ptr, means_dev_ptr))
+        else:
+            _check("rmgr_ssim_hip_enqueue_msssim3h_win", self.lib.rmgr_ssim_hip_enqueue_msssim3h_win(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), scales, _weights_array(weights),
+                values_dev_ptr, means_dev_ptr))
 
     def enqueue_msssim3h_grad(self, params_array, count, data_range, sample_type, means_dev_ptr, grad_out_dev_ptr, grad_a=None, grad_b=None, scales=5,
-                              weights=None):
-        """rmgr_ssim_hip_enqueue_msssim3h_grad: dLoss/dA and / or dLoss/dB of `count` device-resident pairs of volumes, from the forward's
-        means (device memory), into the 16-bit volumes the Grad3H arrays describe, in the inputs' encoding; grad_out_dev_ptr: count float32
-        values; asynchronous on the context's stream, no host synchronisation."""
-        _check("rmgr_ssim_hip_enqueue_msssim3h_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3h_grad(
-            self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), means_dev_ptr,
-            grad_out_dev_ptr, grad_a, grad_b))
+                              weights=None, window=None):
+        """rmgr_ssim_hip_enqueue_msssim3h_grad (window: _msssim3h_win_grad): dLoss/dA and / or dLoss/dB of `count` device-resident pairs of
+        volumes, from the forward's means (device memory), into the 16-bit volumes the Grad3H arrays describe, in the inputs' encoding;
+        grad_out_dev_ptr: count float32 values; asynchronous on the context's stream, no host synchronisation."""
+        if window is None:
+            _check("rmgr_ssim_hip_enqueue_msssim3h_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3h_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, scales, _weights_array(weights), means_dev_ptr,
+                grad_out_dev_ptr, grad_a, grad_b))
+        else:
+            _check("rmgr_ssim_hip_enqueue_msssim3h_win_grad", self.lib.rmgr_ssim_hip_enqueue_msssim3h_win_grad(
+                self.handle, count, params_array, sample_type_code(sample_type), data_range, _window_ref(window), scales, _weights_array(weights),
+                means_dev_ptr, grad_out_dev_ptr, grad_a, grad_b))
 
     def enqueue_batch(self, params_array, count, sums_dev_ptr):
         _check("rmgr_ssim_hip_enqueue_batch", self.lib.rmgr_ssim_hip_enqueue_batch(self.handle, count, params_array, sums_dev_ptr))

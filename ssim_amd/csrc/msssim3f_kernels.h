@@ -78,17 +78,37 @@ hipError_t launch_msssim3f_grad(const Pair3FDesc* descs_dev, const Grad3FDesc* g
                                 uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count, const double* means,
                                 const float* g_out, float* ks, float* coef, int which, hipStream_t stream);
 
-// The two launchers above are the first_scale = 0 form of these.  first_scale = 1 is for a caller that runs scale 0 itself
-// (msssim3h_kernels.hip: only scale 0 holds 16-bit samples): the pyramid steps from scale 1 down, the walks of scales >= 1, the reduction
-// over ALL scales -- scale 0's cell partials first, at offset 0, laid out by plan3f(width, height, depth, count, cu_count) --, the product
-// and k_s; in the backward the coefficient and adjoint walks from the coarsest scale down to scale 1.  Row 0 of descs_dev and of
+// The two launchers above are the first_scale = 0 form of these under the engine's window.  first_scale = 1 is for a caller that runs
+// scale 0 itself (msssim3h_kernels.hip: only scale 0 holds 16-bit samples): the pyramid steps from scale 1 down, the walks of scales >= 1,
+// the reduction over ALL scales -- scale 0's cell partials first, at offset 0, laid out by plan3f(width, height, depth, count, cu_count) --,
+// the product and k_s; in the backward the coefficient and adjoint walks from the coarsest scale down to scale 1.  Row 0 of descs_dev and of
 // grads_dev is not read; the caller has written scale 1's volumes (forward: and scale 0's partials) earlier on `stream`.
-hipError_t launch_msssim3f_from(uint32_t first_scale, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth,
-                                uint32_t scales, float data_range, const double* weights, int cu_count, double* partials, double* means,
-                                double* values, hipStream_t stream);
-hipError_t launch_msssim3f_grad_from(uint32_t first_scale, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, uint32_t count, uint32_t width,
-                                     uint32_t height, uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count,
-                                     const double* means, const float* g_out, float* ks, float* coef, int which, hipStream_t stream);
+//
+// They also take the window, the same at every scale: its radius, which must be 5 here, and its taps, centre first (NULL: the engine's,
+// as launch_ssim3f takes them).  Windows of 11 taps run on the kernels of this file with the window's taps -- the engine's taps: the two
+// launchers above, bit for bit.  Radius 1 .. 4: launch_msssim3k_from / launch_msssim3k_grad_from of msssim3k_kernels.h, on kernels of
+// that radius.
+hipError_t launch_msssim3f_from(uint32_t first_scale, uint32_t radius, const float* taps, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width,
+                                uint32_t height, uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count,
+                                double* partials, double* means, double* values, hipStream_t stream);
+hipError_t launch_msssim3f_grad_from(uint32_t first_scale, uint32_t radius, const float* taps, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev,
+                                     uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, float data_range,
+                                     const double* weights, int cu_count, const double* means, const float* g_out, float* ks, float* coef, int which,
+                                     hipStream_t stream);
+
+// What does not depend on the window, as the launchers above enqueue it -- for them and for msssim3k_kernels.hip, whose launchers differ
+// in the walk and the adjoint walk of each scale alone:
+//   _pyramid  the pyramid of `count` pairs from scale `first_scale` (0 or 1) on, one launch per step, finest first: row s + 1 of descs_dev
+//             from row s
+//   _means    the reduction of every (pair, scale, kind) over `partials` as laid out above ([scale][pair][cell]{cs, ssim}, the cells of a
+//             scale ms3_cells()) into `means`, then the ReLU'd weighted product into `values`
+//   _coef     k_s of every pair and scale into `ks` (scales x count floats, [scale][pair]), from the forward's means and g_out
+hipError_t launch_msssim3f_pyramid(uint32_t first_scale, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth,
+                                   uint32_t scales, hipStream_t stream);
+hipError_t launch_msssim3f_means(uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, const double* weights,
+                                 const double* partials, double* means, double* values, hipStream_t stream);
+hipError_t launch_msssim3f_coef(uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, const double* weights,
+                                const double* means, const float* g_out, float* ks, hipStream_t stream);
 
 } // namespace ssim_hip
 

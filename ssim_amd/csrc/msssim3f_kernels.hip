@@ -226,65 +226,101 @@ uint32_t msssim3f_per_sub_batch(uint32_t width, uint32_t height, uint32_t depth,
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fit, msssim3f_max_count(width, height, depth)));
 }
 
-// first_scale 1 (msssim3h_kernels.hip): scale 0 is the caller's -- its pyramid step and its walk, whose partials lie first -- and row 0
-// of descs_dev is not read.  The layout of the partials, the reduction and the product are the same.
-hipError_t launch_msssim3f_from(uint32_t first_scale, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth,
-                                uint32_t scales, float data_range, const double* weights, int cu_count, double* partials, double* means,
-                                double* values, hipStream_t stream)
+// ---- the steps that do not depend on the window, for this file's launchers and for msssim3k_kernels.hip's ---------------------------------
+
+hipError_t launch_msssim3f_pyramid(uint32_t first_scale, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth,
+                                   uint32_t scales, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (first_scale > 1 || !valid_call(count, width, height, depth, scales, data_range, weights)) return hipErrorInvalidValue;
-    hipError_t e = launch_pyramid(first_scale, descs_dev, count, width, height, depth, scales, stream);
-    if (e != hipSuccess) return e;
+    if (first_scale > 1 || scales < 1 || scales > kMS3MaxScales || count > msssim3f_max_count(width, height, depth)) return hipErrorInvalidValue;
+    return launch_pyramid(first_scale, descs_dev, count, width, height, depth, scales, stream);
+}
+
+hipError_t launch_msssim3f_means(uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, const double* weights,
+                                 const double* partials, double* means, double* values, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (!valid_call(count, width, height, depth, scales, 1.0f, weights)) return hipErrorInvalidValue;
     KR3Args kr;
     kr.partials = partials; kr.means = means; kr.count = count; kr.scales = scales;
     for (uint32_t s = 0; s < kMS3MaxScales; ++s) { kr.offset[s] = 0; kr.cells[s] = 0; kr.voxels[s] = 1.0; }
     uint64_t offset = 0;
     for (uint32_t s = 0; s < scales; ++s) {
+        kr.offset[s] = offset; kr.cells[s] = ms3_cells(width, height, depth, s);
+        kr.voxels[s] = (double)ms3_dim(width, s) * (double)ms3_dim(height, s) * (double)ms3_dim(depth, s);
+        offset += kr.cells[s] * 2 * count;
+    }
+    hipLaunchKernelGGL(msssim3f_reduce_kernel, dim3(count * scales * 2), dim3(kReduceThreads), 0, stream, kr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(msssim3f_finalise_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, depth, scales, weights),
+                       means, values);
+    return hipGetLastError();
+}
+
+hipError_t launch_msssim3f_coef(uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, const double* weights,
+                                const double* means, const float* g_out, float* ks, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (!valid_call(count, width, height, depth, scales, 1.0f, weights)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(msssim3f_coef_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, depth, scales, weights),
+                       means, g_out, ks);
+    return hipGetLastError();
+}
+
+// ---- the launchers of the 11-tap window -----------------------------------------------------------------------------------------------------
+
+// first_scale 1 (msssim3h_kernels.hip): scale 0 is the caller's -- its pyramid step and its walk, whose partials lie first -- and row 0
+// of descs_dev is not read.  The layout of the partials, the reduction and the product are the same.
+hipError_t launch_msssim3f_from(uint32_t first_scale, uint32_t radius, const float* taps, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width,
+                                uint32_t height, uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count,
+                                double* partials, double* means, double* values, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (first_scale > 1 || radius != 5 || !valid_call(count, width, height, depth, scales, data_range, weights)) return hipErrorInvalidValue;
+    hipError_t e = launch_pyramid(first_scale, descs_dev, count, width, height, depth, scales, stream);
+    if (e != hipSuccess) return e;
+    uint64_t offset = 0;
+    for (uint32_t s = 0; s < scales; ++s) {
         const uint32_t w = ms3_dim(width, s), h = ms3_dim(height, s), d = ms3_dim(depth, s);
         const Geometry3F geo = plan3f(w, h, d, count, cu_count);
         K3Args ka;
-        if (!fill_args(ka, geo, data_range, 5, NULL)) return hipErrorInvalidValue;
+        if (!fill_args(ka, geo, data_range, radius, taps)) return hipErrorInvalidValue;
         ka.descs = descs_dev + (size_t)s * count;
         ka.partials = partials + offset;
-        kr.offset[s] = offset; kr.cells[s] = geo.cells_per_volume(); kr.voxels[s] = (double)w * (double)h * (double)d;
-        offset += kr.cells[s] * 2 * count;
+        offset += geo.cells_per_volume() * 2 * count;
         if (s < first_scale) continue;
         hipLaunchKernelGGL((msssim3f_walk_kernel<0, kFormMulti>), grid_of(geo), dim3(256), 0, stream, ka);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(msssim3f_reduce_kernel, dim3(count * scales * 2), dim3(kReduceThreads), 0, stream, kr);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(msssim3f_finalise_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, depth, scales, weights),
-                       means, values);
-    return hipGetLastError();
+    return launch_msssim3f_means(count, width, height, depth, scales, weights, partials, means, values, stream);
 }
 
 hipError_t launch_msssim3f(const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales,
                            float data_range, const double* weights, int cu_count, double* partials, double* means, double* values,
                            hipStream_t stream)
 {
-    return launch_msssim3f_from(0, descs_dev, count, width, height, depth, scales, data_range, weights, cu_count, partials, means, values, stream);
+    return launch_msssim3f_from(0, 5, NULL, descs_dev, count, width, height, depth, scales, data_range, weights, cu_count, partials, means, values, stream);
 }
 
 // first_scale 1: the k_s of every scale, the pyramid from scale 1 down, the walks from the coarsest scale down to scale 1; rows 0 of
 // descs_dev and grads_dev are not read.
-hipError_t launch_msssim3f_grad_from(uint32_t first_scale, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev, uint32_t count, uint32_t width,
-                                     uint32_t height, uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count,
-                                     const double* means, const float* g_out, float* ks, float* coef, int which, hipStream_t stream)
+hipError_t launch_msssim3f_grad_from(uint32_t first_scale, uint32_t radius, const float* taps, const Pair3FDesc* descs_dev, const Grad3FDesc* grads_dev,
+                                     uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, float data_range,
+                                     const double* weights, int cu_count, const double* means, const float* g_out, float* ks, float* coef, int which,
+                                     hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (first_scale > 1 || !valid_call(count, width, height, depth, scales, data_range, weights) || which < 1 || which > 3) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(msssim3f_coef_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, weight_args(count, width, height, depth, scales, weights),
-                       means, g_out, ks);
-    hipError_t e = hipGetLastError();
+    if (first_scale > 1 || radius != 5 || !valid_call(count, width, height, depth, scales, data_range, weights) || which < 1 || which > 3)
+        return hipErrorInvalidValue;
+    hipError_t e = launch_msssim3f_coef(count, width, height, depth, scales, weights, means, g_out, ks, stream);
     if (e != hipSuccess) return e;
     if ((e = launch_pyramid(first_scale, descs_dev, count, width, height, depth, scales, stream)) != hipSuccess) return e;
     for (uint32_t s = scales; s-- > first_scale;) {
         const bool last = s + 1 == scales;
         const Geometry3F geo = plan3f(ms3_dim(width, s), ms3_dim(height, s), ms3_dim(depth, s), count, cu_count);
         KM3Args ka;
-        if (!fill_args(ka, geo, data_range, 5, NULL)) return hipErrorInvalidValue;
+        if (!fill_args(ka, geo, data_range, radius, taps)) return hipErrorInvalidValue;
         ka.descs = descs_dev + (size_t)s * count;
         ka.grads = grads_dev + (size_t)s * count;
         ka.up = last ? nullptr : grads_dev + (size_t)(s + 1) * count;
@@ -309,7 +345,7 @@ hipError_t launch_msssim3f_grad(const Pair3FDesc* descs_dev, const Grad3FDesc* g
                                 uint32_t depth, uint32_t scales, float data_range, const double* weights, int cu_count, const double* means,
                                 const float* g_out, float* ks, float* coef, int which, hipStream_t stream)
 {
-    return launch_msssim3f_grad_from(0, descs_dev, grads_dev, count, width, height, depth, scales, data_range, weights, cu_count, means, g_out, ks,
+    return launch_msssim3f_grad_from(0, 5, NULL, descs_dev, grads_dev, count, width, height, depth, scales, data_range, weights, cu_count, means, g_out, ks,
                                      coef, which, stream);
 }
 

@@ -19,10 +19,13 @@ namespace ssim_hip {
 //   descs_dev    scales x count Pair3FDesc in device memory, [scale][pair]: rows >= 1 dense scratch volumes that this call writes; row 0
 //                is not read
 //   type         kSHTypeF16 or kSHTypeBF16
+//   radius, taps the window, the same at every scale, as launch_msssim3f_from takes it: the radius must be 5 (windows of 11 taps run on these
+//                kernels with the window's taps; NULL: the engine's); radius 1 .. 4: launch_msssim3hk / launch_msssim3hk_grad of
+//                msssim3k_kernels.h
 //   the rest     as launch_msssim3f
 hipError_t launch_msssim3h(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height,
-                           uint32_t depth, uint32_t scales, int type, float data_range, const double* weights, int cu_count, double* partials,
-                           double* means, double* values, hipStream_t stream);
+                           uint32_t depth, uint32_t scales, int type, float data_range, uint32_t radius, const float* taps, const double* weights,
+                           int cu_count, double* partials, double* means, double* values, hipStream_t stream);
 
 // Enqueues the gradient of `count` pairs on `stream`: the pyramid step from scale 0 to scale 1, launch_msssim3f_grad_from(1, ...) -- the
 // coefficients k_s, the rest of the pyramid, the float32 walks from the coarsest scale down to scale 1 --, then the coefficient walk and
@@ -30,11 +33,17 @@ hipError_t launch_msssim3h(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs
 //   descs0_dev, descs_dev   as above
 //   grads0_dev   count Grad3HDesc in device memory: the caller's gradient volumes
 //   grads_dev    scales x count Grad3FDesc in device memory, [scale][pair]: rows >= 1 dense float32 scratch volumes; row 0 is not read
+//   radius, taps as above
 //   the rest     as launch_msssim3f_grad
 hipError_t launch_msssim3h_grad(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs_dev, const Grad3HDesc* grads0_dev, const Grad3FDesc* grads_dev,
                                 uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, int type, float data_range,
-                                const double* weights, int cu_count, const double* means, const float* g_out, float* ks, float* coef, int which,
-                                hipStream_t stream);
+                                uint32_t radius, const float* taps, const double* weights, int cu_count, const double* means, const float* g_out,
+                                float* ks, float* coef, int which, hipStream_t stream);
+
+// The pyramid step from the 16-bit scale 0 into row 1 of descs_dev, as the two launchers above enqueue it -- for them and for
+// msssim3hk_kernels.hip; it does not depend on the window.
+hipError_t launch_msssim3h_down(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height,
+                                uint32_t depth, int type, hipStream_t stream);
 
 } // namespace ssim_hip
 

@@ -107,18 +107,26 @@ hipError_t launch_down(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs_dev
 
 } // namespace
 
-hipError_t launch_msssim3h(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height,
-                           uint32_t depth, uint32_t scales, int type, float data_range, const double* weights, int cu_count, double* partials,
-                           double* means, double* values, hipStream_t stream)
+hipError_t launch_msssim3h_down(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height,
+                                uint32_t depth, int type, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_call(count, width, height, depth, scales, type, data_range, weights)) return hipErrorInvalidValue;
+    if (count > msssim3f_max_count(width, height, depth)) return hipErrorInvalidValue;
+    return launch_down(descs0_dev, descs_dev, count, width, height, depth, type, stream);
+}
+
+hipError_t launch_msssim3h(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs_dev, uint32_t count, uint32_t width, uint32_t height,
+                           uint32_t depth, uint32_t scales, int type, float data_range, uint32_t radius, const float* taps, const double* weights,
+                           int cu_count, double* partials, double* means, double* values, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    if (radius != 5 || !valid_call(count, width, height, depth, scales, type, data_range, weights)) return hipErrorInvalidValue;
     hipError_t e;
     if (scales > 1 && (e = launch_down(descs0_dev, descs_dev, count, width, height, depth, type, stream)) != hipSuccess) return e;
     // scale 0's tiles and cells, as launch_msssim3f_from lays them out: its partials come first
     const Geometry3F geo = plan3f(width, height, depth, count, cu_count);
     K3HArgs ka;
-    if (!fill_args(ka, geo, data_range, 5, NULL)) return hipErrorInvalidValue;
+    if (!fill_args(ka, geo, data_range, radius, taps)) return hipErrorInvalidValue;
     ka.descs = descs0_dev;
     ka.partials = partials;
     if (!with_constant<0, 1>(type, [&](auto TYPE) {
@@ -126,26 +134,28 @@ hipError_t launch_msssim3h(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs
             return true; }))
         return hipErrorInvalidValue;
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    return launch_msssim3f_from(1, descs_dev, count, width, height, depth, scales, data_range, weights, cu_count, partials, means, values, stream);
+    return launch_msssim3f_from(1, radius, taps, descs_dev, count, width, height, depth, scales, data_range, weights, cu_count, partials, means, values,
+                                stream);
 }
 
 hipError_t launch_msssim3h_grad(const Pair3HDesc* descs0_dev, const Pair3FDesc* descs_dev, const Grad3HDesc* grads0_dev, const Grad3FDesc* grads_dev,
                                 uint32_t count, uint32_t width, uint32_t height, uint32_t depth, uint32_t scales, int type, float data_range,
-                                const double* weights, int cu_count, const double* means, const float* g_out, float* ks, float* coef, int which,
-                                hipStream_t stream)
+                                uint32_t radius, const float* taps, const double* weights, int cu_count, const double* means, const float* g_out,
+                                float* ks, float* coef, int which, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    if (!valid_call(count, width, height, depth, scales, type, data_range, weights) || which < 1 || which > 3) return hipErrorInvalidValue;
+    if (radius != 5 || !valid_call(count, width, height, depth, scales, type, data_range, weights) || which < 1 || which > 3)
+        return hipErrorInvalidValue;
     hipError_t e;
     if (scales > 1 && (e = launch_down(descs0_dev, descs_dev, count, width, height, depth, type, stream)) != hipSuccess) return e;
     // the k_s of every scale, the rest of the pyramid, the float32 gradients from the coarsest scale down to scale 1
-    if ((e = launch_msssim3f_grad_from(1, descs_dev, grads_dev, count, width, height, depth, scales, data_range, weights, cu_count, means, g_out, ks,
-                                       coef, which, stream)) != hipSuccess)
+    if ((e = launch_msssim3f_grad_from(1, radius, taps, descs_dev, grads_dev, count, width, height, depth, scales, data_range, weights, cu_count, means,
+                                       g_out, ks, coef, which, stream)) != hipSuccess)
         return e;
     const bool last = scales == 1;
     const Geometry3F geo = plan3f(width, height, depth, count, cu_count);
     KM3HArgs ka;
-    if (!fill_args(ka, geo, data_range, 5, NULL)) return hipErrorInvalidValue;
+    if (!fill_args(ka, geo, data_range, radius, taps)) return hipErrorInvalidValue;
     ka.descs = descs0_dev;
     ka.grads = grads0_dev;
     ka.up = last ? nullptr : grads_dev + (size_t)count;

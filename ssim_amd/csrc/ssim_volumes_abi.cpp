@@ -2,7 +2,7 @@
 // float16 / bfloat16 samples (ssim3h), its gradient for a scalar and for a per-voxel upstream gradient, each under the engine's window
 // and, _win, under the caller's; and multi-scale SSIM of float32 (msssim3f) and of float16 / bfloat16 volumes (msssim3h) with its
 // gradient.  The definitions are in include/rmgr/ssim-hip.h, the kernels in ssim3f_ / ssim3w_ / ssim3k_ / ssim3h_ / ssim3hk_ /
-// msssim3f_ / msssim3h_kernels.hip.
+// msssim3f_ / msssim3h_ / msssim3k_ / msssim3hk_kernels.hip.
 //
 // The flow is the one of ssim_samples_abi.cpp, written for three strides: validation before any device is touched, sub-batches under
 // kScratchCap of device scratch (cell partials, staged volumes and maps; the backward's coefficient volumes; the pyramids) with at least
@@ -22,6 +22,7 @@
 #include "ssim3w_kernels.h"
 #include "ssim3hk_kernels.h"
 #include "msssim3h_kernels.h"
+#include "msssim3hk_kernels.h"
 
 using namespace ssim_host;
 using namespace ssim_host::volumes;      // volume_bytes, take3f, copy_map_back
@@ -391,7 +392,9 @@ int grad_entry_checked(rmgr_ssim_hip_Context* c, F fam, uint32_t count, const ty
 // scales >= 1 (and, in the backward, their gradient volumes) are dense float32 volumes of the context's scratch, one set per pair,
 // rewritten by every sub-batch in stream order; the sub-batches are msssim3f_per_sub_batch's and msssim3f_scratch_bytes', the same for
 // both families since all of the scratch is float32 / float64.  The two families differ in scale 0 alone -- its samples, its descriptors
-// and the kernels that read and write them -- and each is described by a small struct (Multi3F / Multi3H).
+// and the kernels that read and write them -- and each is described by a small struct (Multi3F / Multi3H).  The window, the engine's or
+// the caller's (_win), is one more member of it: the same at every scale, and nothing of the flow -- pyramid, scratch, sub-batches,
+// tables -- depends on it.  Radius 5 runs on the 11-tap kernels with the window's taps, the smaller ones on the k kernels.
 //
 // A launch reads one table of pair descriptors, scales x n Pair3FDesc as [scale][pair] (rows >= 1: the pyramid), and -- backward -- one
 // of gradient descriptors behind it, scales x n Grad3FDesc.  Multi3F: row 0 holds the caller's volumes.  Multi3H: the caller's n
@@ -401,19 +404,27 @@ int grad_entry_checked(rmgr_ssim_hip_Context* c, F fam, uint32_t count, const ty
 struct Multi3F {
     typedef Family3F Single;
     float range;
+    Window win;
     int check() const { return check_call(range); }
     static constexpr size_t kPair0 = 0, kGrad0 = 0;
     hipError_t forward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, uint32_t n, uint32_t W, uint32_t H, uint32_t D, uint32_t scales, const double* w,
                        double* means, double* values) const
     {
-        return ssim_hip::launch_msssim3f(reinterpret_cast<const Pair3FDesc*>(pairs), n, W, H, D, scales, range, w, c->cu_count, c->msf_partials, means,
-                                         values, c->stream);
+        const Pair3FDesc* pd = reinterpret_cast<const Pair3FDesc*>(pairs);
+        if (win.radius == 5)
+            return ssim_hip::launch_msssim3f_from(0, win.radius, win.gf, pd, n, W, H, D, scales, range, w, c->cu_count, c->msf_partials, means, values, c->stream);
+        return ssim_hip::launch_msssim3k_from(0, win.radius, win.gf, pd, n, W, H, D, scales, range, w, c->cu_count, c->msf_partials, means, values, c->stream);
     }
     hipError_t backward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, const uint8_t* grads, uint32_t n, uint32_t W, uint32_t H, uint32_t D,
                         uint32_t scales, const double* w, const double* means, const float* g_out, int which) const
     {
-        return ssim_hip::launch_msssim3f_grad(reinterpret_cast<const Pair3FDesc*>(pairs), reinterpret_cast<const Grad3FDesc*>(grads), n, W, H, D, scales,
-                                              range, w, c->cu_count, means, g_out, c->msf_coef, c->s3_coef, which, c->stream);
+        const Pair3FDesc* pd = reinterpret_cast<const Pair3FDesc*>(pairs);
+        const Grad3FDesc* gd = reinterpret_cast<const Grad3FDesc*>(grads);
+        if (win.radius == 5)
+            return ssim_hip::launch_msssim3f_grad_from(0, win.radius, win.gf, pd, gd, n, W, H, D, scales, range, w, c->cu_count, means, g_out, c->msf_coef,
+                                                       c->s3_coef, which, c->stream);
+        return ssim_hip::launch_msssim3k_grad_from(0, win.radius, win.gf, pd, gd, n, W, H, D, scales, range, w, c->cu_count, means, g_out, c->msf_coef,
+                                                   c->s3_coef, which, c->stream);
     }
 };
 
@@ -421,21 +432,32 @@ struct Multi3H {
     typedef Family3H Single;
     uint32_t sampleType;
     float range;
+    Window win;
     int check() const { return check_call(sampleType, range); }
     static constexpr size_t kPair0 = sizeof(Pair3HDesc), kGrad0 = sizeof(Grad3HDesc);
     hipError_t forward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, uint32_t n, uint32_t W, uint32_t H, uint32_t D, uint32_t scales, const double* w,
                        double* means, double* values) const
     {
-        return ssim_hip::launch_msssim3h(reinterpret_cast<const Pair3HDesc*>(pairs), reinterpret_cast<const Pair3FDesc*>(pairs + n * kPair0), n, W, H, D,
-                                         scales, sample_type(sampleType), range, w, c->cu_count, c->msf_partials, means, values, c->stream);
+        const Pair3HDesc* pd0 = reinterpret_cast<const Pair3HDesc*>(pairs);
+        const Pair3FDesc* pd = reinterpret_cast<const Pair3FDesc*>(pairs + n * kPair0);
+        if (win.radius == 5)
+            return ssim_hip::launch_msssim3h(pd0, pd, n, W, H, D, scales, sample_type(sampleType), range, win.radius, win.gf, w, c->cu_count,
+                                             c->msf_partials, means, values, c->stream);
+        return ssim_hip::launch_msssim3hk(pd0, pd, n, W, H, D, scales, sample_type(sampleType), range, win.radius, win.gf, w, c->cu_count,
+                                          c->msf_partials, means, values, c->stream);
     }
     hipError_t backward(rmgr_ssim_hip_Context* c, const uint8_t* pairs, const uint8_t* grads, uint32_t n, uint32_t W, uint32_t H, uint32_t D,
                         uint32_t scales, const double* w, const double* means, const float* g_out, int which) const
     {
-        return ssim_hip::launch_msssim3h_grad(reinterpret_cast<const Pair3HDesc*>(pairs), reinterpret_cast<const Pair3FDesc*>(pairs + n * kPair0),
-                                              reinterpret_cast<const Grad3HDesc*>(grads), reinterpret_cast<const Grad3FDesc*>(grads + n * kGrad0), n, W, H,
-                                              D, scales, sample_type(sampleType), range, w, c->cu_count, means, g_out, c->msf_coef, c->s3_coef, which,
-                                              c->stream);
+        const Pair3HDesc* pd0 = reinterpret_cast<const Pair3HDesc*>(pairs);
+        const Pair3FDesc* pd = reinterpret_cast<const Pair3FDesc*>(pairs + n * kPair0);
+        const Grad3HDesc* gd0 = reinterpret_cast<const Grad3HDesc*>(grads);
+        const Grad3FDesc* gd = reinterpret_cast<const Grad3FDesc*>(grads + n * kGrad0);
+        if (win.radius == 5)
+            return ssim_hip::launch_msssim3h_grad(pd0, pd, gd0, gd, n, W, H, D, scales, sample_type(sampleType), range, win.radius, win.gf, w, c->cu_count,
+                                                  means, g_out, c->msf_coef, c->s3_coef, which, c->stream);
+        return ssim_hip::launch_msssim3hk_grad(pd0, pd, gd0, gd, n, W, H, D, scales, sample_type(sampleType), range, win.radius, win.gf, w, c->cu_count,
+                                               means, g_out, c->msf_coef, c->s3_coef, which, c->stream);
     }
 };
 
@@ -828,7 +850,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_ssim3h_win_map_grad(rmgr_ssim_hip_Context* c,
 rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataRange,
                                             rmgr_uint32_t scales, const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
 {
-    const Multi3F fam = {dataRange};
+    const Multi3F fam = {dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
     return rc ? rc : ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
 }
@@ -836,7 +858,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f(rmgr_ssim_hip_Context* c, rmgr_uint3
 rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataRange,
                                                    rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const Multi3F fam = {dataRange};
+    const Multi3F fam = {dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, msssim);
     return rc ? rc : ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
@@ -844,7 +866,7 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_device(rmgr_ssim_hip_Context* c, rmg
 rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params, float dataRange,
                                                  rmgr_uint32_t scales, const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const Multi3F fam = {dataRange};
+    const Multi3F fam = {dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, msssim);
     return rc ? rc : ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
@@ -854,7 +876,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f_grad(rmgr_ssim_hip_Context* c, rmgr_
                                                  const float* gradOutDevice, const rmgr_ssim_hip_Grad3F* gradA,
                                                  const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT
 {
-    const Multi3F fam = {dataRange};
+    const Multi3F fam = {dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
     return rc ? rc : ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);
 }
@@ -865,7 +887,7 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h(rmgr_ssim_hip_Context* c, rmgr_uint3
                                             rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
                                             double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
 {
-    const Multi3H fam = {sampleType, dataRange};
+    const Multi3H fam = {sampleType, dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
     return rc ? rc : ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
 }
@@ -874,7 +896,7 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssim3h_device(rmgr_ssim_hip_Context* c, rmg
                                                    rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
                                                    float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const Multi3H fam = {sampleType, dataRange};
+    const Multi3H fam = {sampleType, dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, msssim);
     return rc ? rc : ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
@@ -883,7 +905,7 @@ rmgr_int32_t rmgr_ssim_hip_compute_msssim3h_host(rmgr_ssim_hip_Context* c, rmgr_
                                                  rmgr_uint32_t sampleType, float dataRange, rmgr_uint32_t scales, const double* weights,
                                                  float* msssim, double* scaleMeans) RMGR_NOEXCEPT
 {
-    const Multi3H fam = {sampleType, dataRange};
+    const Multi3H fam = {sampleType, dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, msssim);
     return rc ? rc : ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
 }
@@ -893,9 +915,95 @@ rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h_grad(rmgr_ssim_hip_Context* c, rmgr_
                                                  const double* scaleMeansDevice, const float* gradOutDevice, const rmgr_ssim_hip_Grad3H* gradA,
                                                  const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT
 {
-    const Multi3H fam = {sampleType, dataRange};
+    const Multi3H fam = {sampleType, dataRange, default_window()};
     const int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
     return rc ? rc : ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);
+}
+
+// ---- the same under the caller's window: both run the same flow; the window is one more input of the family -------------------------------
+// The checks of the entry without _win come first (sample type, data range, pairs, scales, weights), then the window, then the remaining
+// pointers; all of them before the context or any device is touched.
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
+{
+    Multi3F fam = {dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                       float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                       const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    Multi3F fam = {dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3f_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                     float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                     const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    Multi3F fam = {dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3f_win_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3F* params,
+                                                     float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                     const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
+                                                     const rmgr_ssim_hip_Grad3F* gradA, const rmgr_ssim_hip_Grad3F* gradB) RMGR_NOEXCEPT
+{
+    Multi3F fam = {dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h_win(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                const double* weights, double* valuesDevice, double* scaleMeansDevice) RMGR_NOEXCEPT
+{
+    Multi3H fam = {sampleType, dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, valuesDevice);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_enqueue_entry(c, fam, count, params, scales, weights, valuesDevice, scaleMeansDevice);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3h_win_device(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                       rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                       const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    Multi3H fam = {sampleType, dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_device_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_compute_msssim3h_win_host(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                     rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                     const double* weights, float* msssim, double* scaleMeans) RMGR_NOEXCEPT
+{
+    Multi3H fam = {sampleType, dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, msssim);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_host_entry(c, fam, count, params, scales, weights, msssim, scaleMeans);
+}
+
+rmgr_int32_t rmgr_ssim_hip_enqueue_msssim3h_win_grad(rmgr_ssim_hip_Context* c, rmgr_uint32_t count, const rmgr_ssim_hip_Params3H* params,
+                                                     rmgr_uint32_t sampleType, float dataRange, const rmgr_ssim_hip_Window* window, rmgr_uint32_t scales,
+                                                     const double* weights, const double* scaleMeansDevice, const float* gradOutDevice,
+                                                     const rmgr_ssim_hip_Grad3H* gradA, const rmgr_ssim_hip_Grad3H* gradB) RMGR_NOEXCEPT
+{
+    Multi3H fam = {sampleType, dataRange, Window()};
+    int rc = ms_validate(fam, count, params, scales, weights, gradOutDevice);
+    if (rc || (rc = window_validate(window, fam.win))) return rc;
+    return ms_grad_entry(c, fam, count, params, scales, weights, scaleMeansDevice, gradOutDevice, gradA, gradB);
 }
 
 } // extern "C"

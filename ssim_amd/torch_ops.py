@@ -888,8 +888,9 @@ def ssim3d_map_amp(x, y, data_range=1.0, win_size=11, win_sigma=1.5, window="gau
 # ms_ssim3d(x, y, data_range, scales, weights) is the definition in include/rmgr/ssim-hip.h (rmgr_ssim_hip_enqueue_msssim3f): ms_ssim's
 # weighted product with ssim3d's per-voxel terms over a pyramid that halves x, y and z.  The backward is
 # rmgr_ssim_hip_enqueue_msssim3f_grad, from x, y and the (volumes, scales, 2) float64 per-scale means the forward keeps.  ms_ssim3d_amp and
-# MSSSIM3DLoss take float16 / bfloat16 volumes as well, on the msssim3h entries, through the same autograd function.  The engine's 11-tap
-# window only; a window and a multi-scale map gradient are follow-ups.
+# MSSSIM3DLoss take float16 / bfloat16 volumes as well, on the msssim3h entries, through the same autograd function.  win_size, win_sigma
+# and window are ssim3d()'s keywords and mean the same window on all three axes at EVERY scale (the msssim3f_win and msssim3h_win
+# entries); the defaults take exactly the path without them.  A multi-scale map gradient is a follow-up.
 
 _ms_function3d = None
 
@@ -899,7 +900,7 @@ def _make_ms_function3d():
 
     class _MSSSIM3D(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, y, data_range, scales, weights):
+        def forward(ctx, x, y, data_range, scales, weights, win):
             lead = x.shape[:-3]
             params, n = _params3d(x, y)
             values = torch.empty(n, dtype=torch.float64, device=x.device)
@@ -910,13 +911,15 @@ def _make_ms_function3d():
                     work.wait_stream(cur)
                 st = _sample_type(torch, x.dtype)
                 if st is None:
-                    _context(x.device, work).enqueue_msssim3f(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights)
+                    _context(x.device, work).enqueue_msssim3f(params, n, data_range, values.data_ptr(), means.data_ptr(), scales, weights,
+                                                              **_win_kw(win))
                 else:
-                    _context(x.device, work).enqueue_msssim3h(params, n, data_range, st, values.data_ptr(), means.data_ptr(), scales, weights)
+                    _context(x.device, work).enqueue_msssim3h(params, n, data_range, st, values.data_ptr(), means.data_ptr(), scales, weights,
+                                                              **_win_kw(win))
                 if work is not cur:
                     cur.wait_stream(work)
             ctx.save_for_backward(x, y, means)
-            ctx.data_range, ctx.scales, ctx.weights = data_range, scales, weights
+            ctx.data_range, ctx.scales, ctx.weights, ctx.win = data_range, scales, weights, win
             return values.to(torch.float32).reshape(lead)
 
         @staticmethod
@@ -926,7 +929,7 @@ def _make_ms_function3d():
             d, h, w = x.shape[-3], x.shape[-2], x.shape[-1]
             want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             if not (want_x or want_y):
-                return None, None, None, None, None
+                return None, None, None, None, None, None
             params, n = _params3d(x, y)
             g = grad_out.to(torch.float32).reshape(-1).contiguous()
             gx = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_x else None     # the inputs' dtype: the kernel rounds once
@@ -939,26 +942,27 @@ def _make_ms_function3d():
                 gb = _grad_volumes(gy, n, d, h, w) if want_y else None
                 st = _sample_type(torch, x.dtype)
                 if st is None:
-                    _context(x.device, work).enqueue_msssim3f_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales, ctx.weights)
+                    _context(x.device, work).enqueue_msssim3f_grad(params, n, ctx.data_range, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales, ctx.weights,
+                                                                   **_win_kw(ctx.win))
                 else:
                     _context(x.device, work).enqueue_msssim3h_grad(params, n, ctx.data_range, st, means.data_ptr(), g.data_ptr(), ga, gb, ctx.scales,
-                                                                   ctx.weights)
+                                                                   ctx.weights, **_win_kw(ctx.win))
                 if work is not cur:
                     cur.wait_stream(work)
-            return gx, gy, None, None, None
+            return gx, gy, None, None, None, None
 
     return _MSSSIM3D
 
 
-def _ms_ssim3d(x, y, r, scales, weights, name):
+def _ms_ssim3d(x, y, r, scales, weights, name, win=None):
     global _ms_function3d
     scales, w = _check_scales(scales, weights, name)
     if _ms_function3d is None:
         _ms_function3d = _make_ms_function3d()
-    return _ms_function3d.apply(x, y, r, scales, w)
+    return _ms_function3d.apply(x, y, r, scales, w, win)
 
 
-def ms_ssim3d(x, y, data_range=1.0, scales=5, weights=None):
+def ms_ssim3d(x, y, data_range=1.0, scales=5, weights=None, win_size=11, win_sigma=1.5, window="gaussian"):
     """Per-volume multi-scale SSIM of two float32 GPU tensors of identical shape (..., D, H, W), any strides (each volume is addressed in
     place, no copy): a float32 tensor of shape x.shape[:-3].  The 11-tap Gaussian window (sigma 1.5, clamped edges) on all three axes at
     every scale; all three axes are halved from scale to scale, down to 1 x 1 x 1 if need be.  weights None: Wang's five (scales must be
@@ -966,15 +970,20 @@ def ms_ssim3d(x, y, data_range=1.0, scales=5, weights=None):
     need it, from x, y and the (volumes, scales, 2) float64 per-scale means the forward keeps.  It runs on torch's current stream through
     the cached context, as ssim() does.  TypeError / ValueError as ssim3d() and ms_ssim(), under this function's name; float16 and
     bfloat16 tensors are a TypeError here ("the 3-D multi-scale path is float32 for now": pinned by tests from the time there was no
-    16-bit path): ms_ssim3d_amp() and MSSSIM3DLoss take them."""
+    16-bit path): ms_ssim3d_amp() and MSSSIM3DLoss take them.
+    The window: win_size, win_sigma and window are ssim3d()'s keywords with ssim3d()'s errors, and mean the same window on all three axes
+    at EVERY scale (rmgr_ssim_hip_enqueue_msssim3f_win, _msssim3f_win_grad; pytorch-msssim's MS_SSIM(spatial_dims=3, win_size,
+    win_sigma)); the defaults are the engine's window and take exactly the path without these arguments.  Volumes smaller than the window
+    at coarse scales clamp: a 12-frame clip has depth 12, 6, 3, 2, 1, which is what a window of 7 or 3 taps is for."""
     import torch
     if isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and (x.dtype in (torch.float16, torch.bfloat16) or y.dtype in (torch.float16, torch.bfloat16)):
         raise TypeError("ms_ssim3d: the 3-D multi-scale path is float32 for now, got %s and %s; ms_ssim3d_amp() takes float16 / bfloat16 tensors"
                         % (x.dtype, y.dtype))
-    return _ms_ssim3d(x, y, _check3d(x, y, data_range, "ms_ssim3d"), scales, weights, "ms_ssim3d")
+    win = _window(x, y, win_size, win_sigma, window, "ms_ssim3d", fixed16=False)
+    return _ms_ssim3d(x, y, _check3d(x, y, data_range, "ms_ssim3d"), scales, weights, "ms_ssim3d", win)
 
 
-def ms_ssim3d_amp(x, y, data_range=1.0, scales=5, weights=None):
+def ms_ssim3d_amp(x, y, data_range=1.0, scales=5, weights=None, win_size=11, win_sigma=1.5, window="gaussian"):
     """ms_ssim3d() for tensors as they come under mixed precision: two GPU tensors of identical shape (..., D, H, W), both float32, both
     float16 or both bfloat16, any strides (each volume is addressed in place, no copy or widening): a float32 tensor of shape
     x.shape[:-3] at every input dtype.  float32 tensors: exactly ms_ssim3d().  float16 and bfloat16 (rmgr_ssim_hip_enqueue_msssim3h,
@@ -983,23 +992,29 @@ def ms_ssim3d_amp(x, y, data_range=1.0, scales=5, weights=None):
     and the float64 means.  Errors: as ms_ssim3d(), under this function's name, except that a mixed pair is a TypeError and two float16 or
     two bfloat16 CPU tensors are a TypeError too: 16-bit tensors are taken on a GPU only (one of the two on a GPU: the ValueError).  That
     message keeps the words "the 3-D multi-scale path is float32 for now", which tests/test_msssim3f_cpu.py pins for
-    MSSSIM3DLoss()(x16_cpu, x16_cpu) from the time there was no 16-bit path."""
+    MSSSIM3DLoss()(x16_cpu, x16_cpu) from the time there was no 16-bit path.  win_size, win_sigma, window: as ms_ssim3d(), at every input
+    dtype: with float16 and bfloat16 tensors (rmgr_ssim_hip_enqueue_msssim3h_win, _msssim3h_win_grad) the value has the bits of
+    ms_ssim3d(x.float(), y.float(), win_size=...) under the same window and the gradient is that call's, rounded once."""
+    win = _window(x, y, win_size, win_sigma, window, "ms_ssim3d_amp", fixed16=False)
     if _is_half_pair(x, y) and not x.is_cuda and not y.is_cuda:
         raise TypeError("ms_ssim3d_amp: float16 / bfloat16 tensors are taken on a GPU only (on the CPU the 3-D multi-scale path is float32 for "
                         "now), got %s on %s and %s" % (x.dtype, x.device, y.device))
-    return _ms_ssim3d(x, y, _check3d(x, y, data_range, "ms_ssim3d_amp", half=True), scales, weights, "ms_ssim3d_amp")
+    return _ms_ssim3d(x, y, _check3d(x, y, data_range, "ms_ssim3d_amp", half=True), scales, weights, "ms_ssim3d_amp", win)
 
 
 class MSSSIM3DLoss(object):
     """1 - ms_ssim3d_amp(x, y, data_range, scales, weights): reduction "mean" (a scalar) or "none" (one value per volume).  A plain
-    callable: it has no parameters.  float32, float16 or bfloat16 tensors, as ms_ssim3d_amp(); the loss is float32 at every input dtype."""
+    callable: it has no parameters.  float32, float16 or bfloat16 tensors, as ms_ssim3d_amp(); the loss is float32 at every input dtype.
+    win_size, win_sigma, window: the window of every scale, as ms_ssim3d(), checked here; GPU tensors take it at every dtype."""
 
-    def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean"):
+    def __init__(self, data_range=1.0, scales=5, weights=None, reduction="mean", win_size=11, win_sigma=1.5, window="gaussian"):
         if reduction not in ("mean", "none"):
             raise ValueError("MSSSIM3DLoss: reduction must be 'mean' or 'none', got %r" % (reduction,))
         _check_scales(scales, weights, "MSSSIM3DLoss")
+        _window(None, None, win_size, win_sigma, window, "MSSSIM3DLoss", fixed16=False)
         self.data_range, self.scales, self.weights, self.reduction = data_range, scales, weights, reduction
+        self.win_size, self.win_sigma, self.window = win_size, win_sigma, window
 
     def __call__(self, x, y):
-        loss = 1.0 - ms_ssim3d_amp(x, y, self.data_range, self.scales, self.weights)
+        loss = 1.0 - ms_ssim3d_amp(x, y, self.data_range, self.scales, self.weights, self.win_size, self.win_sigma, self.window)
         return loss.mean() if self.reduction == "mean" else loss
